@@ -15,12 +15,16 @@ is used for the barrier and the max-over-ranks reduction only.  `--gpus N`
 without a launcher (no WORLD_SIZE in the environment) starts the N ranks itself:
 N fresh child processes, spawned before this process touches a GPU.
 
-Prints ONE JSON line on rank 0 (contract in the task description) carrying
-`roofline` (dominant kernel, HIP-event timed on the handle's own stream) and
-`cpu_baseline` (the oracle's simplicial sparse LDL^T on the host, rank 0, N=1),
-plus what an unmodified SLEQP would see through the vtable (`boundary`), the
-real 1 : 100 factor : solve ratio (`sqp_iteration`), the cost of a changed
-working set (`working_set_change`), and the SpMV / solve roofline fractions.
+Prints ONE JSON line on rank 0 (the BASELINE.json metric).  A plain run
+sets up, warms up, times the --steps steps and reports the headline only
+(`value`, `ms_per_step`, the configuration).  `--full` goes on from there and adds
+the scaled residual of the timed solve, `roofline` (dominant kernel, HIP-event
+timed on the handle's own stream) and `cpu_baseline` (the oracle's simplicial
+sparse LDL^T on the host, rank 0, N=1), plus what an unmodified SLEQP would see
+through the vtable (`boundary`), the real 1 : 100 factor : solve ratio
+(`sqp_iteration`), the cost of a changed working set (`working_set_change`), and
+the SpMV / solve roofline fractions.  `--dump-outputs DIR` writes the solution of
+the last timed step (DIR/solution.npy) in either mode.
 """
 from __future__ import annotations
 
@@ -744,6 +748,65 @@ def working_set_change_bench(J, local_rank, steps=12):
     return out
 
 
+def headline(args, rep, fact, J, N, t_max, per_rank, ab):
+    """The result line's headline fields: the rate of the timed steps and the configuration they ran (ab: algorithmic_bytes)."""
+    world = rep.world
+    return {
+        "metric": "KKT factor+solve/sec (numeric refactor + 1 solve with device-controlled refinement, inputs resident in HBM)",
+        "value": rep.aggregate_rate(args.steps, t_max),
+        "unit": "factor+solve/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": t_max / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {"workload": args.workload, "n": int(fact.info("n")), "m": int(fact.info("m")), "N": N,
+                   "nnz_J": int(J.nnz), "nnz_tril_K": int(fact.info("nnzK")), "nnz_L": int(ab["nnzL"]),
+                   "nnz_L_stored": int(ab["nnzL_stored"]),
+                   "supernodes": int(fact.info("nsuper")), "etree_levels": int(fact.info("nlevels")),
+                   "refine_steps": args.refine, "refine_target": fact.info("refine_tol"),
+                   "equilibrate": bool(fact.info("equilibrate")), "hip_graphs": int(fact.info("num_graphs")),
+                   "solves_per_factor": args.solves_per_factor,
+                   "parallelism": f"replicas{world}" if world > 1 else "single"},
+        "per_rank_ms_per_step": {"min": min(per_rank) / args.steps * 1e3, "max": max(per_rank) / args.steps * 1e3,
+                                 "all": [t / args.steps * 1e3 for t in per_rank]},
+    }
+
+
+def summary(out):
+    """The figures a reader looks for first, once more at the END of the line (a driver that keeps the tail of a long
+    line keeps these); what a run did not measure is null."""
+    so = out.get("solve_only", {})
+    bd = out.get("boundary", {}) if isinstance(out.get("boundary"), dict) else {}
+    return {"value": out["value"], "ms_per_step": out["ms_per_step"], "factor_only_ms": out.get("factor_only_ms"),
+            "solve_only_ms": so.get("ms_per_solve"), "roofline_frac": out.get("roofline", {}).get("frac"),
+            "dominant_kernel": out.get("roofline", {}).get("kernel"),
+            "dominant_kernel_us": out.get("roofline", {}).get("avg_launch_us"),
+            "boundary_rate": bd.get("rate"), "boundary_ms_per_unit": bd.get("ms_per_unit"),
+            "boundary_solve_plus_solution_ms": bd.get("solve_plus_solution_ms"),
+            "sqp_iteration_ms": out.get("sqp_iteration", {}).get("ms") if isinstance(out.get("sqp_iteration"), dict) else None,
+            "dataflow_fallbacks": out.get("dataflow_fallbacks"), "dense_fallbacks": out.get("dense_fallbacks"),
+            "vtable_retries": out.get("vtable_retries"), "solve_timeouts": out.get("solve_timeouts")}
+
+
+def dump_outputs(directory, rank, z):
+    """--dump-outputs: the solution of the last timed step (N float64, 1.2 MB for the default workload), one file per rank."""
+    os.makedirs(directory, exist_ok=True)
+    name = "solution.npy" if rank == 0 else f"solution_rank{rank}.npy"
+    np.save(os.path.join(directory, name), np.ascontiguousarray(z, dtype=np.float64))
+
+
+def positive_int(text):
+    value = int(text)
+    if value < 1:
+        raise argparse.ArgumentTypeError(f"must be at least 1, got {value}")
+    return value
+
+
 def spawn_ranks(args):
     """`python bench.py --gpus N` without a launcher: N fresh child processes, one per GPU, started before this
     process has made any GPU call; rank 0's JSON line is relayed."""
@@ -770,7 +833,7 @@ def spawn_ranks(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=positive_int, default=200, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="banded_n1e5_m5e4")
     ap.add_argument("--refine", type=int, default=1)
@@ -779,6 +842,13 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip the boundary / working-set / SQP-ratio measurements")
     ap.add_argument("--solves-per-factor", type=int, default=1)
     ap.add_argument("--spmv-only", default=None, help="(profiling) run only this sparse product 20 times: J_x, JT_y or H_sym_x")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure also measure and check everything else: residual, spread, per-kernel "
+                         "roofline, solve-only rate, boundary / working-set / SQP-ratio extras, ceilings, CPU baseline "
+                         "(the --no-* switches above trim this)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the solution of the last timed step to DIR/solution.npy (float64; rank r > 0: "
+                         "solution_rank<r>.npy)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -841,12 +911,26 @@ def main():
     t_max = rep.max_over_ranks(t_local)
     per_rank = rep.gather(t_local)
     fact.check()  # singular / stalled / timed-out work surfaces here (the timed region is asynchronous)
+    z = d_sol.cpu().numpy()  # what the last timed step computed: the solution a caller of refactor + solve receives
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, z)
+
+    if not args.full:
+        # the headline figure only: everything below (checks, other measurements) is --full
+        if rank == 0:
+            out = headline(args, rep, fact, J, N, t_max, per_rank, algorithmic_bytes(fact))
+            for key in ("dataflow_fallbacks", "dense_fallbacks", "vtable_retries", "solve_timeouts"):
+                out[key] = int(fact.info(key))
+            out["summary"] = summary(out)
+            print(json.dumps(out), flush=True)
+        fact.free()
+        rep.close()
+        return
 
     # correctness of what was timed (scaled residual of the last solve)
     from sleqp_amd import synth
 
     K = synth.kkt_full_matrix(N, cp, ri, vx)
-    z = d_sol.cpu().numpy()
     resid = float(np.abs(K @ z - b).max() / (abs(K).sum(axis=1).max() * np.abs(z).max() + np.abs(b).max()))
 
     # spread: the same step in 10 chunks (each chunk synchronised once), sized so that timed region + spread keep the
@@ -1006,7 +1090,7 @@ def main():
 
     if rank == 0:
         ab = algorithmic_bytes(fact)
-        fbytes, sbytes, nnzL = ab["factor"], ab["solve"], ab["nnzL"]
+        fbytes, sbytes = ab["factor"], ab["solve"]
         dom = max(prof, key=lambda k: prof[k]["ms_per_step"]) if prof else "factor"
         kernel_names = {"factor": "k_factor_level", "factorA": "k_front_assemble", "factorB": "k_front_pivot",
                         "factorC": "k_front_panel", "factorD": "k_front_schur", "factorT": "k_factor_top",
@@ -1066,29 +1150,8 @@ def main():
         traffic, traffic_note = (None, "workload other than the profiled one")
         if args.workload == "banded_n1e5_m5e4":
             traffic, traffic_note = load_traffic(kernel_names.get(dom, dom), args.workload)
-        out = {
-            "metric": "KKT factor+solve/sec (numeric refactor + 1 solve with device-controlled refinement, inputs resident in HBM)",
-            "value": rep.aggregate_rate(args.steps, t_max),
-            "unit": "factor+solve/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": t_max / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": {"workload": args.workload, "n": int(fact.info("n")), "m": int(fact.info("m")), "N": N,
-                       "nnz_J": int(J.nnz), "nnz_tril_K": int(fact.info("nnzK")), "nnz_L": int(nnzL),
-                       "nnz_L_stored": int(ab["nnzL_stored"]),
-                       "supernodes": int(fact.info("nsuper")), "etree_levels": int(fact.info("nlevels")),
-                       "refine_steps": args.refine, "refine_target": fact.info("refine_tol"),
-                       "equilibrate": bool(fact.info("equilibrate")), "hip_graphs": int(fact.info("num_graphs")),
-                       "solves_per_factor": args.solves_per_factor,
-                       "parallelism": f"replicas{world}" if world > 1 else "single"},
-            "per_rank_ms_per_step": {"min": min(per_rank) / args.steps * 1e3, "max": max(per_rank) / args.steps * 1e3,
-                                     "all": [t / args.steps * 1e3 for t in per_rank]},
+        out = headline(args, rep, fact, J, N, t_max, per_rank, ab)
+        out.update({
             "spread_ms_per_step": {"chunks": 10, "steps_per_chunk": chunk, "min": min(chunks), "median": float(np.median(chunks)),
                                    "max": max(chunks)},
             "roofline": {"bound": "hbm", "kernel": kernel_names.get(dom, dom), "achieved": achieved,
@@ -1111,7 +1174,7 @@ def main():
             "cold_set_matrix_s": t_cold,
             "analysis_s": fact.info("analysis_s"),
             "scaled_residual": resid,
-        }
+        })
         # rocprof view of one solve (north_star: HBM GB/s on the triangular solves): bytes per launch of its kernels
         # from the PMC passes (tree with both sweeps and the right-hand side, x update, residual), when they match
         # the sources this run uses
@@ -1183,19 +1246,7 @@ def main():
             out["measured_ceilings"] = measured_ceilings(f"cuda:{local_rank}")
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(N, cp, ri, vx, b)
-        # the figures a reader looks for first, once more at the END of the line (a driver that keeps the tail of a long
-        # line keeps these)
-        so = out.get("solve_only", {})
-        bd = out.get("boundary", {}) if isinstance(out.get("boundary"), dict) else {}
-        out["summary"] = {"value": out["value"], "ms_per_step": out["ms_per_step"], "factor_only_ms": out.get("factor_only_ms"),
-                          "solve_only_ms": so.get("ms_per_solve"), "roofline_frac": out.get("roofline", {}).get("frac"),
-                          "dominant_kernel": out.get("roofline", {}).get("kernel"),
-                          "dominant_kernel_us": out.get("roofline", {}).get("avg_launch_us"),
-                          "boundary_rate": bd.get("rate"), "boundary_ms_per_unit": bd.get("ms_per_unit"),
-                          "boundary_solve_plus_solution_ms": bd.get("solve_plus_solution_ms"),
-                          "sqp_iteration_ms": out.get("sqp_iteration", {}).get("ms") if isinstance(out.get("sqp_iteration"), dict) else None,
-                          "dataflow_fallbacks": out.get("dataflow_fallbacks"), "dense_fallbacks": out.get("dense_fallbacks"),
-                          "vtable_retries": out.get("vtable_retries"), "solve_timeouts": out.get("solve_timeouts")}
+        out["summary"] = summary(out)
         print(json.dumps(out), flush=True)
     rep.close()
 

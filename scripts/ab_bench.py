@@ -15,7 +15,7 @@ for rnd in range(rounds):
         for kv in filter(None, v.split(",")):
             k, val = kv.split("=")
             env[k] = val
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-ceilings", "--no-extras",
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-ceilings", "--no-extras",
                               "--steps", "200", "--warmup", "20"], env=env, capture_output=True, text=True)
         try:
             d = json.loads(out.stdout.strip().splitlines()[-1])

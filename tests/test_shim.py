@@ -763,60 +763,36 @@ def test_mat_shim_products_against_oracle(shim, hipfact_lib):
     assert hipfact_lib.hipfact_free(C.byref(handle)) == 0
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src/main"), reason="reference tree not present")
-def test_shim_compiles_against_the_reference_headers(tmp_path):
-    """Boundary hygiene: the three shim files, WITHOUT HIPFACT_STANDALONE, type-check against the real
-    headers of chrhansk/sleqp (gcc -fsyntax-only).  The two CMake-generated headers the sources include
-    (sleqp/defs.h from defs.h.in, sleqp/export.h) are the only stand-ins, and they only hold macros."""
-    inc = tmp_path / "sleqp"
-    inc.mkdir()
-    # what CMake would configure from src/main/defs.h.in for -DSLEQP_FACT=HIPFACT (macros only)
-    (inc / "defs.h").write_text(
-        "#ifndef SLEQP_DEFS_H\n#define SLEQP_DEFS_H\n#define SLEQP_VERSION \"1.0.2\"\n"
-        "#define SLEQP_HAVE_ATTRIBUTE_WARN_UNUSED_RESULT\n#define SLEQP_HAVE_ATTRIBUTE_FORMAT\n"
-        "#define SLEQP_FORMAT_PRINTF(index, first) __attribute__((__format__(__printf__, index, first)))\n"
-        "#define SLEQP_FACT_NAME \"hipfact\"\n#define SLEQP_FACT_VERSION \"0.2.0\"\n"
-        "#define SLEQP_FACT_HIPFACT_NAME \"hipfact\"\n#define SLEQP_FACT_HIPFACT_VERSION \"0.2.0\"\n#endif\n")
-    (inc / "export.h").write_text("#ifndef SLEQP_EXPORT_H\n#define SLEQP_EXPORT_H\n#define SLEQP_EXPORT\n"
-                                  "#define SLEQP_NO_EXPORT\n#endif\n")
-    ref = "/root/reference/src/main"
-    # public headers are installed as <sleqp/pub_*.h>: mirror that with symlinks (no copies)
-    for name in os.listdir(ref):
-        if name.startswith("pub_") and name.endswith(".h"):
-            os.symlink(os.path.join(ref, name), inc / name)
-    for sub in ("sparse",):
-        (inc / sub).mkdir()
-        for name in os.listdir(os.path.join(ref, sub)):
-            if name.startswith("pub_") and name.endswith(".h"):
-                os.symlink(os.path.join(ref, sub, name), inc / sub / name)
-    for src in ("fact_hipfact.c", "aug_jac_hipfact.c", "tr_hipfact.c", "mat_hipfact.c"):
-        # the files live in src/main/{fact,aug_jac,tr}/ of a SLEQP checkout and include their neighbours by
-        # bare name, like fact_lapack.c / standard_aug_jac.c / steihaug_solver.c do
-        cmd = ["gcc", "-std=c11", "-fsyntax-only", "-Wall", "-I", str(tmp_path), "-I", str(inc), "-I", ref,
-               "-I", os.path.join(ref, "fact"), "-I", os.path.join(ref, "aug_jac"), "-I", os.path.join(ref, "tr"),
-               "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "shim"), os.path.join(ROOT, "shim", src)]
-        res = subprocess.run(cmd, capture_output=True, text=True)
-        assert res.returncode == 0, res.stderr
+def _overlay_inputs():
+    """Hand-written test inputs for scripts/overlay_sleqp.py, made only of what it looks for: add_fact(...) blocks
+    (LAPACK last) followed by the list they feed, and the AugJac create calls of its TRIAL_POINT_OLD pattern (one of
+    them wrapped) beside the reduced one it must leave alone."""
+    search = ('add_fact(NAME "ALPHA" SOURCES fact/fact_alpha.c)\n\n'
+              'add_fact(NAME "LAPACK"\n  SOURCES fact/fact_lapack.c)\n\n'
+              'set(_SLEQP_FACT_VALUES "")\n')
+    call = "sleqp_{}_aug_jac_create(&solver->aug_jac,{}problem, settings, solver->fact)"
+    trial_point = ('#include "aug_jac/standard_aug_jac.h"\n'
+                   f"a = {call.format('reduced', ' ')};\n"
+                   f"b = {call.format('standard', ' ')};\n"
+                   f"c = {call.format('standard', chr(10) + '    ')};\n")
+    return search, trial_point
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/cmake"), reason="reference tree not present")
 def test_overlay_script_registers_the_backend(tmp_path):
-    """scripts/overlay_sleqp.py against (a copy of the three files it edits of) the reference checkout: the backend
+    """scripts/overlay_sleqp.py on hand-written stand-ins for the two files it edits of a SLEQP checkout: the backend
     is registered through add_fact like the others (cmake/SearchFact.cmake:11-83), create_aug_jac is rerouted,
     running it twice changes nothing more."""
     import importlib.util
-    import shutil
 
     spec = importlib.util.spec_from_file_location("overlay_sleqp", os.path.join(ROOT, "scripts", "overlay_sleqp.py"))
     ov = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(ov)
-    text = open("/root/reference/cmake/SearchFact.cmake").read()
+    text, tp = _overlay_inputs()
     once = ov.register(text, ["fact/fact_hipfact.c", "aug_jac/aug_jac_hipfact.c"])
     assert once.count('NAME "HIPFACT"') == 1 and "fact/fact_hipfact.c" in once
     assert once.index('NAME "HIPFACT"') > once.index('NAME "LAPACK"')            # after the last existing backend
     assert once.index('NAME "HIPFACT"') < once.index("set(_SLEQP_FACT_VALUES")   # before the list is consumed
     assert ov.register(once, ["fact/fact_hipfact.c", "aug_jac/aug_jac_hipfact.c"]) == once  # idempotent
-    tp = open("/root/reference/src/main/trial_point.c").read()
     patched = ov.patch_trial_point(tp)
     assert patched.count("sleqp_hipfact_aug_jac_create(&solver->aug_jac, problem, settings, NULL") == 2  # AUTO and STANDARD
     assert "sleqp_standard_aug_jac_create" not in patched and '#include "aug_jac/aug_jac_hipfact.h"' in patched
@@ -825,8 +801,8 @@ def test_overlay_script_registers_the_backend(tmp_path):
     # end to end on a scratch tree holding just the touched paths
     for d in ("cmake", "src/main/fact", "src/main/aug_jac", "src/main/tr"):
         os.makedirs(tmp_path / d)
-    shutil.copy("/root/reference/cmake/SearchFact.cmake", tmp_path / "cmake")
-    shutil.copy("/root/reference/src/main/trial_point.c", tmp_path / "src/main")
+    (tmp_path / "cmake" / "SearchFact.cmake").write_text(text)
+    (tmp_path / "src" / "main" / "trial_point.c").write_text(tp)
     res = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "overlay_sleqp.py"), str(tmp_path), "--aug-jac", "--tr"],
                          capture_output=True, text=True)
     assert res.returncode == 0, res.stderr
