@@ -424,7 +424,9 @@ int hipfact_set_option(hipfact_handle* h, const char* name, double value);
 int hipfact_get_info(const hipfact_handle* h, const char* name, double* value);
 
 /* Debugging aid (tests, scripts): copies the first `bytes` of a named device buffer of the active plan
- * state to the host ("L", "SPf", "SPb", "sitems", "y", "xhat", "ysol", "uvec", "dscale"). */
+ * state to the host ("L", "SPf", "SPb", "sitems", "y", "xhat", "ysol", "uvec", "dscale"), or of one of the
+ * active host plan's front arrays ("perm", "sn_c0", "sn_r", "sn_rowptr", "sn_rows", "sn_Loff", "late_cols"; int32, except
+ * int64 for sn_rowptr and sn_Loff). */
 int hipfact_debug_copy(hipfact_handle* h, const char* name, void* out, size_t bytes);
 
 /* Host-only self-test of the worker pool behind the row dictionary's passes over K (no GPU needed): `callers` threads

@@ -261,6 +261,23 @@ int hipfact_debug_copy(hipfact_handle* h, const char* name, void* out, size_t by
   int rc = enter(h);
   if (rc) return rc;
   if (!name || !out) return HIPFACT_EINVAL;
+  // read-only copies of the active host plan's front structure (tests map the device factor onto its fronts)
+  auto host_copy = [&](const auto& v) {
+    if (bytes > v.size() * sizeof(v[0])) {
+      h->error = "hipfact_debug_copy: unknown buffer or size";
+      return HIPFACT_EINVAL;
+    }
+    if (bytes) memcpy(out, v.data(), bytes);
+    return HIPFACT_OK;
+  };
+  const Plan& P = h->plan;
+  if (!strcmp(name, "perm")) return host_copy(P.perm);
+  if (!strcmp(name, "sn_c0")) return host_copy(P.sn_c0);
+  if (!strcmp(name, "sn_r")) return host_copy(P.sn_r);
+  if (!strcmp(name, "sn_rowptr")) return host_copy(P.sn_rowptr);
+  if (!strcmp(name, "sn_rows")) return host_copy(P.sn_rows);
+  if (!strcmp(name, "sn_Loff")) return host_copy(P.sn_Loff);
+  if (!strcmp(name, "late_cols")) return host_copy(P.late_cols);
   const DevBuf* b = nullptr;
   if (!strcmp(name, "L")) b = &h->d_L;
   else if (!strcmp(name, "U")) b = &h->d_U;
