@@ -283,6 +283,67 @@ int hipfact_tr_solve_ex(hipfact_handle* h, int method, hipfact_spmat* hess, hipf
                         const double* gradient, double trust_radius, double rel_tol, int max_iter, double* newton_step,
                         double* tr_dual, int* iterations, hipfact_tr_extra* extra);
 
+/* ---- Gauss-Newton LSQR (least-squares problems, TR_SOLVER = LSQR) ------- */
+
+/* Residual Jacobian J_r (r x n) as a product on host vectors: trans = 0: out (r) = J_r in (n); trans = 1: out (n) =
+ * J_r' in (r).  Returns 0 on success.  The SLEQP side wraps sleqp_lsq_func_jac_forward / _adjoint (lsq.h:27-34). */
+typedef int (*hipfact_lsqr_prod_fn)(void* user, int trans, const double* in, double* out);
+
+/* The operator of the Gauss-Newton solver (gauss_newton.c:432-533, the forward_product / adjoint_product callbacks of
+ * the reference's SleqpLSQRSolver): A d = [J_r P d; J_v P d], A' u = P (J_r' u_r + J_v' u_v), P the null-space
+ * projection of the handle's factorisation (sleqp_aug_jac_project_nullspace, standard_aug_jac.c:396-435).
+ *   num_residuals  r = sleqp_lsq_func_num_residuals (lsq.h)
+ *   jac            J_r, r x n on this handle (SLEQP_FUNC_TYPE_LSQ with a known Jacobian), or NULL: prod / user
+ *   cons           J_v, the already-scaled violated constraint rows (compute_cons_matrix, gauss_newton.c:278-301),
+ *                  m_v x n on this handle, or NULL (m_v = 0) */
+typedef struct hipfact_lsqr_op
+{
+  int num_residuals;
+  hipfact_spmat* jac;
+  hipfact_lsqr_prod_fn prod;
+  void* user;
+  hipfact_spmat* cons;
+} hipfact_lsqr_op;
+
+enum
+{
+  HIPFACT_LSQR_CONVERGED = 0, /* phi_bar alpha |c| <= rel_tol (lsqr.c:298-311) */
+  HIPFACT_LSQR_BOUNDARY  = 1, /* the iterate left the trust region: the boundary point (lsqr.c:256-290) */
+  HIPFACT_LSQR_MAX_ITER  = 2, /* max_iter iterations (the reference's cap is n, lsqr.c:234): the iterate reached */
+  HIPFACT_LSQR_TIME      = 3, /* the time limit (lsqr.c:313-326): the iterate reached */
+  HIPFACT_LSQR_ZERO      = 4  /* b = 0 or A' b = 0: x = 0 without iterating */
+};
+
+/*   time_limit  in, seconds from the call's entry on a steady clock, < 0 (SLEQP_NONE) = none; looked at behind the
+ *               convergence test of every iteration (lsqr.c:313-318).  The reference's timer counts clock() CPU time
+ *               plus the previous run's duration (timer.c:100-147); that is not reproduced.
+ *   iterations  out, iterations performed;  status  out, HIPFACT_LSQR_*;  timed_out  out, 1 = the limit ended it
+ *   phi_bar     out, the last phi_bar (the residual norm estimate of lsqr.c:298) */
+typedef struct hipfact_lsqr_info
+{
+  double time_limit;
+  int iterations;
+  int status;
+  int timed_out;
+  double phi_bar;
+} hipfact_lsqr_info;
+
+/* Replaces sleqp_lsqr_solver_solve (tr/lsqr.c:173-330) as called by solve_lsqr (gauss_newton.c:535-554) with every
+ * vector in HBM: LSQR on the operator above from x = 0, two projections per iteration like the reference, one host
+ * synchronisation per iteration; with a matrix-free J_r the callback is called once per product (one vector down and
+ * one up through pinned staging).
+ *   rhs           host, r + m_v doubles (compute_rhs, gauss_newton.c:370-384)
+ *   rel_tol       stat_tol * 1e-2 (gauss_newton.c:20,541)
+ *   trust_radius  < 0: none; exit on sleqp_is_gt(||x||, trust_radius, eps) (cmp.c:8-17) with the boundary point of
+ *                 sleqp_tr_compute_bdry_sol (tr/tr_util.c:8-50)
+ *   eps           SLEQP_SETTINGS_REAL_EPS (default 1e-10)
+ *   max_iter      -1: n (forward_dim, the reference's cap)
+ *   step          host out, n doubles;  info  in / out, may be NULL (no time limit)
+ * The zero_eps filtering of the reference's sparse vector additions is not reproduced (dense vectors).  A failing
+ * callback returns HIPFACT_EINTERNAL. */
+int hipfact_lsqr_solve(hipfact_handle* h, const hipfact_lsqr_op* op, const double* rhs, double rel_tol,
+                       double trust_radius, double eps, int max_iter, double* step, hipfact_lsqr_info* info);
+
 /* Host-only: the tridiagonal trust-region subproblem of GLTR (exposed for the tests).
  * min 1/2 h'Th + gamma0 e1'h, ||h|| <= radius; delta[0..k) diagonal, gamma[1..k) off-diagonal. */
 int hipfact_tridiag_tr(int k, const double* delta, const double* gamma, double gamma0, double radius, double* h,

@@ -142,6 +142,13 @@ sleqp_settings_capture(SleqpSettings* settings)
 double
 sleqp_settings_stat_tol(const SleqpSettings* settings) { return settings ? settings->stat_tol : 1e-6; }
 
+double
+sleqp_settings_eps(const SleqpSettings* settings)
+{
+  (void)settings;
+  return 1e-10;
+}
+
 int
 sleqp_settings_max_newton_iterations(const SleqpSettings* settings) { return settings ? settings->max_newton_iterations : 100; }
 
@@ -476,6 +483,14 @@ sleqp_fact_release(SleqpFact** star)
 }
 
 /* ---- problem / working set / iterate ---- */
+struct SleqpFunc
+{
+  SleqpProblem* problem;
+  int num_residuals;
+  SleqpMiniLsqProd forward, adjoint;
+  void* data;
+};
+
 struct SleqpProblem
 {
   int refcount;
@@ -483,7 +498,79 @@ struct SleqpProblem
   bool nonlinear_cons;
   SleqpMiniHessProd hess_prod;
   void* hess_data;
+  SleqpFunc func;
 };
+
+void
+sleqp_problem_set_lsq_mini(SleqpProblem* p, int num_residuals, SleqpMiniLsqProd forward, SleqpMiniLsqProd adjoint,
+                           void* data)
+{
+  p->func.problem       = p;
+  p->func.num_residuals = num_residuals;
+  p->func.forward       = forward;
+  p->func.adjoint       = adjoint;
+  p->func.data          = data;
+}
+
+SleqpFunc*
+sleqp_problem_func(SleqpProblem* p)
+{
+  p->func.problem = p;
+  return &p->func;
+}
+
+int
+sleqp_lsq_func_num_residuals(SleqpFunc* func) { return func->num_residuals; }
+
+/* dense in (nin) -> callback -> sparse out (nout), as a user's SLEQP_LSQ_JAC_FORWARD / _ADJOINT would fill it */
+static SLEQP_RETCODE
+lsq_mini_prod(SleqpMiniLsqProd prod, void* data, const SleqpVec* in_vec, int nin, SleqpVec* product, int nout)
+{
+  if (!prod)
+  {
+    sleqp_raise(SLEQP_INTERNAL_ERROR, "mini problem: no least-squares Jacobian product installed");
+  }
+  if (in_vec->dim != nin)
+  {
+    sleqp_raise(SLEQP_ILLEGAL_ARGUMENT, "mini problem: direction of dimension %d, expected %d", in_vec->dim, nin);
+  }
+  double* in  = calloc((size_t)(nin > 0 ? nin : 1), sizeof(double));
+  double* out = calloc((size_t)(nout > 0 ? nout : 1), sizeof(double));
+  SLEQP_RETCODE status = SLEQP_OKAY;
+  if (!in || !out)
+  {
+    status = SLEQP_ERROR;
+  }
+  else
+  {
+    for (int k = 0; k < in_vec->nnz; ++k) in[in_vec->indices[k]] = in_vec->data[k];
+    if (prod(in, out, data) != 0)
+      status = SLEQP_ERROR;
+    else
+      status = sleqp_vec_set_from_raw(product, out, nout, 0.0);
+  }
+  free(in);
+  free(out);
+  if (status != SLEQP_OKAY)
+  {
+    sleqp_raise(SLEQP_FUNC_EVAL_ERROR, "mini problem: least-squares Jacobian product failed");
+  }
+  return SLEQP_OKAY;
+}
+
+SLEQP_RETCODE
+sleqp_lsq_func_jac_forward(SleqpFunc* func, const SleqpVec* forward_direction, SleqpVec* product)
+{
+  return lsq_mini_prod(func->forward, func->data, forward_direction, func->problem->num_vars, product,
+                       func->num_residuals);
+}
+
+SLEQP_RETCODE
+sleqp_lsq_func_jac_adjoint(SleqpFunc* func, const SleqpVec* adjoint_direction, SleqpVec* product)
+{
+  return lsq_mini_prod(func->adjoint, func->data, adjoint_direction, func->num_residuals, product,
+                       func->problem->num_vars);
+}
 
 void
 sleqp_problem_set_hess_prod_mini(SleqpProblem* p, SleqpMiniHessProd callback, void* data)
@@ -540,6 +627,7 @@ sleqp_problem_create_mini(SleqpProblem** star, int num_vars, int num_cons)
   (*star)->nonlinear_cons = true;
   (*star)->hess_prod      = NULL;
   (*star)->hess_data      = NULL;
+  (*star)->func           = (SleqpFunc){.problem = *star, .num_residuals = 0};
   (*star)->num_vars = num_vars;
   (*star)->num_cons = num_cons;
   return SLEQP_OKAY;

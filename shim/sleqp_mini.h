@@ -139,6 +139,8 @@ SLEQP_RETCODE
 sleqp_settings_capture(SleqpSettings* settings);
 double
 sleqp_settings_stat_tol(const SleqpSettings* settings); /* SLEQP_SETTINGS_REAL_STAT_TOL, default 1e-6 */
+double
+sleqp_settings_eps(const SleqpSettings* settings); /* SLEQP_SETTINGS_REAL_EPS, default 1e-10 */
 int
 sleqp_settings_max_newton_iterations(const SleqpSettings* settings); /* SLEQP_SETTINGS_INT_MAX_NEWTON_ITERATIONS, default 100 */
 SLEQP_RETCODE
@@ -303,6 +305,23 @@ SLEQP_RETCODE
 sleqp_problem_capture(SleqpProblem* problem);
 SLEQP_RETCODE
 sleqp_problem_release(SleqpProblem** star);
+
+/* The least-squares function of a SLEQP_FUNC_TYPE_LSQ problem (pub_problem.h:133, lsq.h:13, 27-34): the mini problem
+ * carries one, with the number of residuals and the forward / adjoint Jacobian products on dense arrays installed by
+ * the test (forward: in n values, out r; adjoint: in r, out n). */
+typedef struct SleqpFunc SleqpFunc;
+typedef int (*SleqpMiniLsqProd)(const double* in, double* out, void* data);
+void
+sleqp_problem_set_lsq_mini(SleqpProblem* problem, int num_residuals, SleqpMiniLsqProd forward,
+                           SleqpMiniLsqProd adjoint, void* data);
+SleqpFunc*
+sleqp_problem_func(SleqpProblem* problem);
+int
+sleqp_lsq_func_num_residuals(SleqpFunc* func);
+SLEQP_WARNUNUSED SLEQP_RETCODE
+sleqp_lsq_func_jac_forward(SleqpFunc* func, const struct SleqpVec* forward_direction, struct SleqpVec* product);
+SLEQP_WARNUNUSED SLEQP_RETCODE
+sleqp_lsq_func_jac_adjoint(SleqpFunc* func, const struct SleqpVec* adjoint_direction, struct SleqpVec* product);
 
 SLEQP_RETCODE
 sleqp_problem_hess_prod(SleqpProblem* problem, const struct SleqpVec* direction, const struct SleqpVec* cons_duals,

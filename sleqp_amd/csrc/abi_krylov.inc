@@ -676,3 +676,25 @@ int hipfact_tr_solve(hipfact_handle* h, int method, hipfact_spmat* hess, hipfact
                              iterations, nullptr);
 }
 
+#include "krylov_lsqr.inc"
+
+int hipfact_lsqr_solve(hipfact_handle* h, const hipfact_lsqr_op* op, const double* rhs, double rel_tol,
+                       double trust_radius, double eps, int max_iter, double* step, hipfact_lsqr_info* info) {
+  int rc = enter(h);
+  if (rc) return rc;
+  if (!op) {
+    h->error = "hipfact_lsqr_solve: no operator";
+    return HIPFACT_EINVAL;
+  }
+  hipfact_lsqr_info local;
+  memset(&local, 0, sizeof(local));
+  local.time_limit = -1.0;
+  hipfact_lsqr_info* inf = info ? info : &local;
+  h->tr.limit = inf->time_limit;
+  h->tr.t0 = std::chrono::steady_clock::now();
+  h->tr.timed_out = false;
+  rc = lsqr_impl(h, op, rhs, rel_tol, trust_radius, eps, max_iter, step, inf);
+  h->tr.limit = -1.0;
+  return rc;
+}
+

@@ -50,6 +50,9 @@ namespace hipfact {
 #define KRYLOV_DEVICE_KERNELS
 #include "krylov_device.inc"
 #undef KRYLOV_DEVICE_KERNELS
+#define KRYLOV_LSQR_KERNELS
+#include "krylov_lsqr.inc"
+#undef KRYLOV_LSQR_KERNELS
 
 // ---- the instances of the kernel templates the host runtime launches (it sees declarations only: kernels_decl.h)
 namespace hipfact {
@@ -79,6 +82,18 @@ INST_LZ(4)
 INST_LZ(16)
 INST_LZ(64)
 #undef INST_LZ
+#define INST_LSQR(L)                                                                                                  \
+  template __global__ void k_lsqr_forward<L>(int, int, const int*, const int*, const double*, const double*,         \
+                                             const int*, const int*, const double*, const double*, double, double,   \
+                                             double*, double*);                                                      \
+  template __global__ void k_lsqr_adjoint<L>(int, int, const int*, const int*, const double*, const double*,         \
+                                             const int*, const int*, const double*, const double*, const double*,    \
+                                             int, double*, double*);
+INST_LSQR(1)
+INST_LSQR(4)
+INST_LSQR(16)
+INST_LSQR(64)
+#undef INST_LSQR
 template __global__ void k_x_saddle<true>(int, int, const int*, const double*, const int*, const int*, SaddleMaps,
                                           const double*, const double*, double*, const int*, int*);
 template __global__ void k_x_saddle<false>(int, int, const int*, const double*, const int*, const int*, SaddleMaps,

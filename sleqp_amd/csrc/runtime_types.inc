@@ -435,6 +435,9 @@ struct hipfact_handle : PlanState {
   PinBuf h_lz_ctl;
   long lz_device_runs = 0, lz_device_fallbacks = 0, lz_device_iterations = 0;
   DevBuf d_lz_Q, d_lz_b, d_lz_coef;  // generalised Lanczos: basis (n x cap), three rotating right-hand sides, coefficients
+  DevBuf d_lsqr;                     // Gauss-Newton LSQR (krylov_lsqr.inc): right-hand sides, vectors, partials
+  PinBuf h_lsqr;                     // ... what the host reads at its synchronisation, the right-hand side's staging
+  long lsqr_runs = 0, lsqr_iters = 0;
 };
 
 struct hipfact_spmat {

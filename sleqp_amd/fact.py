@@ -193,6 +193,42 @@ class HipFact:
                         "max_rayleigh": extra.max_rayleigh}
         return step, dual.value, its.value
 
+    def lsqr(self, jac_r, cons, rhs, trust_radius: float, stat_tol: float = 1e-6, max_iter: int = -1,
+             time_limit: float = -1.0, eps: float = 1e-10):
+        """hipfact_lsqr_solve: the Gauss-Newton LSQR loop (tr/lsqr.c:173-330 on the operator of gauss_newton.c) on the
+        device.  `jac_r` is an SpMat (the residual Jacobian in HBM) or a pair (forward, adjoint) of callables on host
+        arrays, d -> J_r d and u -> J_r' u; `cons` the scaled violated constraint rows as an SpMat, or None; `rhs` has
+        r + m_v entries; `trust_radius` < 0: none.  Returns (step, info) with info: iterations, status (HIPFACT_LSQR_*:
+        0 converged, 1 boundary, 2 iteration cap, 3 time limit, 4 zero right-hand side), timed_out, phi_bar."""
+        b = np.ascontiguousarray(rhs, dtype=np.float64)
+        n = int(self.info("n"))
+        mv = cons.mat.num_rows if cons is not None else 0
+        r = b.size - mv
+        step = np.empty(n)
+        if isinstance(jac_r, SpMat):
+            assert jac_r.mat.num_rows == r, (jac_r.mat.num_rows, r)
+            jac, cb = jac_r._m, C.cast(None, LSQR_PROD)
+        else:
+            forward, adjoint = jac_r
+
+            def _prod(_user, trans, inp, out):
+                try:
+                    if trans:
+                        np.ctypeslib.as_array(out, shape=(n,))[:] = adjoint(np.ctypeslib.as_array(inp, shape=(r,)).copy())
+                    else:
+                        np.ctypeslib.as_array(out, shape=(r,))[:] = forward(np.ctypeslib.as_array(inp, shape=(n,)).copy())
+                    return 0
+                except Exception:  # noqa: BLE001
+                    return -1
+
+            jac, cb = None, LSQR_PROD(_prod)
+        op = LsqrOp(r, jac, cb, None, cons._m if cons is not None else None)
+        info = LsqrInfo(float(time_limit), 0, 0, 0, 0.0)
+        self._check(self._lib.hipfact_lsqr_solve(self._h, C.byref(op), _ptr(b), stat_tol * 1e-2, float(trust_radius),
+                                                 float(eps), int(max_iter), _ptr(step), C.byref(info)))
+        return step, {"iterations": info.iterations, "status": info.status, "timed_out": bool(info.timed_out),
+                      "phi_bar": info.phi_bar}
+
     def free(self):
         if self._h:
             self._lib.hipfact_free(C.byref(self._h))
@@ -209,6 +245,21 @@ class TrExtra(C.Structure):
     """hipfact_tr_extra (include/hipfact.h)"""
     _fields_ = [("time_limit", C.c_double), ("timed_out", C.c_int), ("min_rayleigh", C.c_double),
                 ("max_rayleigh", C.c_double)]
+
+
+LSQR_PROD = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double))
+
+
+class LsqrOp(C.Structure):
+    """hipfact_lsqr_op (include/hipfact.h)"""
+    _fields_ = [("num_residuals", C.c_int), ("jac", C.c_void_p), ("prod", LSQR_PROD), ("user", C.c_void_p),
+                ("cons", C.c_void_p)]
+
+
+class LsqrInfo(C.Structure):
+    """hipfact_lsqr_info (include/hipfact.h)"""
+    _fields_ = [("time_limit", C.c_double), ("iterations", C.c_int), ("status", C.c_int), ("timed_out", C.c_int),
+                ("phi_bar", C.c_double)]
 
 
 class SpMat:
