@@ -148,14 +148,7 @@ int hipfact_spmat_mult_device(hipfact_spmat* M, int trans, const double* d_x, do
     HCHECK(h, hipGetLastError());
     return HIPFACT_OK;
   }
-  if (avg <= 2.5)
-    launch_spmv<1>(st, nrows, ptr, idx, val, ptr2, idx2, val2, d_x, d_y);
-  else if (avg <= 10.0)
-    launch_spmv<4>(st, nrows, ptr, idx, val, ptr2, idx2, val2, d_x, d_y);
-  else if (avg <= 48.0)
-    launch_spmv<16>(st, nrows, ptr, idx, val, ptr2, idx2, val2, d_x, d_y);
-  else
-    launch_spmv<64>(st, nrows, ptr, idx, val, ptr2, idx2, val2, d_x, d_y);
+  launch_spmv(st, spmv_lanes(avg), nrows, ptr, idx, val, ptr2, idx2, val2, d_x, d_y);
   HCHECK(h, hipGetLastError());
   return HIPFACT_OK;
 }

@@ -27,8 +27,10 @@
 //   kernels_solve_wide.inc    wide fronts of the fallback solves
 //   kernels_solve_tree.inc    k_solve_tree (the whole solve in one launch), solve panels
 //   kernels_saddle.inc        row scaling, right-hand side, x update, residual, refinement verdict
-//   kernels_vector.inc        Krylov vector kernels, CSR SpMV, fill_aug_jac on the device
-// (dense_cols.inc and krylov_device.inc carry their own kernels next to the host code that launches them.)
+//   kernels_vector.inc        CSR row product / lane sum / block partial sums shared by the product and Krylov kernels,
+//                             Krylov vector kernels, CSR SpMV, fill_aug_jac on the device
+// (dense_cols.inc, krylov_device.inc and krylov_lsqr.inc carry their own kernels next to the host code that launches
+// them; the Krylov ones are built from the shared pieces of kernels_vector.inc.)
 #include <hip/hip_runtime.h>
 
 #include "device_types.h"

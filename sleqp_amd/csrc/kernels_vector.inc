@@ -1,5 +1,87 @@
-// kernels_vector.inc - vector kernels of the Krylov loops, CSR SpMV, KKT assembly (fill_aug_jac)
+// kernels_vector.inc - shared pieces of the product / Krylov kernels (row product, lane sum, block partial sums),
+// vector kernels of the Krylov loops, CSR SpMV, KKT assembly (fill_aug_jac)
 // (part of the translation unit kernels_solve.hip; included from there, in this order)
+
+// ---------------------------------------------------------------------------
+// The pieces every product / Krylov kernel (here, krylov_device.inc, krylov_lsqr.inc) is built from.  Each of them
+// fixes a summation order, and the results are promised bit for bit repeatable: a kernel calls these, it does not
+// restate them.
+// ---------------------------------------------------------------------------
+
+// Lane `sub` of the LANES lanes of a row adds its share of row `row` of the CSR matrix (ptr, idx, val) times x onto
+// the running sum s.  (Onto s, not from zero: a part summed on its own and added afterwards would change the order of
+// the additions, i.e. the bits.  The pointers are plain: the kernels' own arguments carry __restrict__.)
+template <int LANES>
+__device__ __forceinline__ double csr_row_add(double s, int row, int sub, const int* ptr, const int* idx,
+                                              const double* val, const double* x) {
+  const int p1 = ptr[row + 1];
+  for (int p = ptr[row] + sub; p < p1; p += LANES) s += val[p] * x[idx[p]];
+  return s;
+}
+// The same without the diagonal entry: the columns of a lower triangle, which complete its rows to the symmetric product
+template <int LANES>
+__device__ __forceinline__ double csr_offdiag_add(double s, int row, int sub, const int* ptr, const int* idx,
+                                                  const double* val, const double* x) {
+  const int q1 = ptr[row + 1];
+  for (int q = ptr[row] + sub; q < q1; q += LANES) {
+    const int col = idx[q];
+    if (col != row) s += val[q] * x[col];
+  }
+  return s;
+}
+// sum over the LANES lanes of a row (shuffle tree; the result is valid in the row's lane 0)
+template <int LANES>
+__device__ __forceinline__ double lanes_sum(double s) {
+#pragma unroll
+  for (int o = LANES / 2; o > 0; o >>= 1) s += __shfl_down(s, o, LANES);
+  return s;
+}
+
+// End of a kernel that leaves NK partial sums per block: the threads' sums t[k] -> shuffle tree inside the waves, one
+// LDS slot per wave, thread k adds the waves in wave order and writes out[NK * blockIdx.x + k].  Blocks of FB threads.
+// (block_sum_fixed of kernels_common.inc is the NK = 1 case with a barrier in front, for callers that reuse its LDS,
+// and the result in thread 0; it is left as it is, the kernels that call it are not part of the Krylov set.)
+template <int NK>
+__device__ __forceinline__ void block_partials(double (&t)[NK], double* __restrict__ out) {
+  __shared__ double sh[NK][FB / 64];
+#pragma unroll
+  for (int k = 0; k < NK; ++k) {
+    t[k] = wave_sum(t[k]);
+    if ((threadIdx.x & 63) == 0) sh[k][threadIdx.x >> 6] = t[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < NK) {
+    double a = 0.0;
+    for (int q = 0; q < FB / 64; ++q) a += sh[threadIdx.x][q];
+    (out + NK * blockIdx.x)[threadIdx.x] = a;  // (the block's base first: a kernel's row index is not kept alive for it)
+  }
+}
+// The reader of such partials: the sum of nblk partials part[stride * b + k], k < NK, by the whole block in a fixed
+// order (every block of a launch gets the same bits): thread t adds the partials t, t + FB, ...; shuffle tree; the
+// waves in order.  Every thread gets the totals.  A second call in the same kernel reuses the shared scratch: put a
+// barrier between the two.
+template <int NK>
+__device__ __forceinline__ void block_totals(const double* __restrict__ part, int nblk, int stride, double* tot) {
+  __shared__ double sh[NK][FB / 64];
+  double s[NK];
+#pragma unroll
+  for (int k = 0; k < NK; ++k) s[k] = 0.0;
+  for (int b = threadIdx.x; b < nblk; b += FB)
+#pragma unroll
+    for (int k = 0; k < NK; ++k) s[k] += part[stride * b + k];
+#pragma unroll
+  for (int k = 0; k < NK; ++k) {
+    s[k] = wave_sum(s[k]);
+    if ((threadIdx.x & 63) == 0) sh[k][threadIdx.x >> 6] = s[k];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < NK; ++k) {
+    double a = 0.0;
+    for (int q = 0; q < FB / 64; ++q) a += sh[k][q];
+    tot[k] = a;
+  }
+}
 
 // ---------------------------------------------------------------------------
 // Vector kernels of the device-resident projected CG (tr/steihaug_solver.c).
@@ -12,27 +94,13 @@ __global__ __launch_bounds__(FB) void k_dots3(int n, const double* __restrict__ 
                                               const double* __restrict__ x1, const double* __restrict__ y1,
                                               const double* __restrict__ x2, const double* __restrict__ y2,
                                               double* __restrict__ out) {
-  __shared__ double sh[3][FB / 64];
-  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+  double s[3] = {0.0, 0.0, 0.0};
   for (int i = blockIdx.x * FB + threadIdx.x; i < n; i += gridDim.x * FB) {
-    if (x0) s0 += x0[i] * y0[i];
-    if (x1) s1 += x1[i] * y1[i];
-    if (x2) s2 += x2[i] * y2[i];
+    if (x0) s[0] += x0[i] * y0[i];
+    if (x1) s[1] += x1[i] * y1[i];
+    if (x2) s[2] += x2[i] * y2[i];
   }
-  s0 = wave_sum(s0);
-  s1 = wave_sum(s1);
-  s2 = wave_sum(s2);
-  if ((threadIdx.x & 63) == 0) {
-    sh[0][threadIdx.x >> 6] = s0;
-    sh[1][threadIdx.x >> 6] = s1;
-    sh[2][threadIdx.x >> 6] = s2;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    double s = 0.0;
-    for (int q = 0; q < FB / 64; ++q) s += sh[threadIdx.x][q];
-    out[3 * blockIdx.x + threadIdx.x] = s;
-  }
+  block_partials<3>(s, out);
 }
 
 // y = a x
@@ -54,18 +122,6 @@ __global__ __launch_bounds__(FB) void k_combine(int n, int k, const double* __re
 __global__ __launch_bounds__(FB) void k_axpby(int n, double a, const double* __restrict__ x, double b,
                                               double* __restrict__ y) {
   for (int i = blockIdx.x * FB + threadIdx.x; i < n; i += gridDim.x * FB) y[i] = a * x[i] + b * y[i];
-}
-
-// Lanczos three-term recurrence in one pass: out = v + a x + b w, rounded like the copy and the two k_axpby it replaces
-// (b = 0: the first step has no t_{k-1}, w is not read)
-__global__ __launch_bounds__(FB) void k_lanczos_next(int n, const double* __restrict__ v, double a,
-                                                     const double* __restrict__ x, double b,
-                                                     const double* __restrict__ w, double* __restrict__ out) {
-  for (int i = blockIdx.x * FB + threadIdx.x; i < n; i += gridDim.x * FB) {
-    double t = a * x[i] + 1.0 * v[i];
-    if (w) t = b * w[i] + 1.0 * t;
-    out[i] = t;
-  }
 }
 
 // t := y and (q non-null) q := s y: the projected Lanczos vector and its normalised copy in the basis
@@ -155,18 +211,9 @@ __global__ __launch_bounds__(FB) void k_spmv_csr(int nrows, const int* __restric
   const int sub = threadIdx.x % LANES;
   const int rows_per_block = FB / LANES;
   for (int row = blockIdx.x * rows_per_block + threadIdx.x / LANES; row < nrows; row += gridDim.x * rows_per_block) {
-    double s = 0.0;
-    const int p1 = ptr[row + 1];
-    for (int p = ptr[row] + sub; p < p1; p += LANES) s += val[p] * x[idx[p]];
-    if (ptr2) {
-      const int q1 = ptr2[row + 1];
-      for (int q = ptr2[row] + sub; q < q1; q += LANES) {
-        const int c = idx2[q];
-        if (c != row) s += val2[q] * x[c];
-      }
-    }
-#pragma unroll
-    for (int o = LANES / 2; o > 0; o >>= 1) s += __shfl_down(s, o, LANES);
+    double s = csr_row_add<LANES>(0.0, row, sub, ptr, idx, val, x);
+    if (ptr2) s = csr_offdiag_add<LANES>(s, row, sub, ptr2, idx2, val2, x);
+    s = lanes_sum<LANES>(s);
     if (sub == 0) y[row] = s;
   }
 }

@@ -37,31 +37,6 @@ __device__ __forceinline__ void cg_ctl_copy(CgCtl* __restrict__ o, const CgCtl* 
   o->max_iter = i->max_iter;
 }
 
-// sum of nblk partials part[stride * b + k], k < NK, by the whole block in a fixed order (every block of a launch
-// gets the same bits): thread t adds the partials t, t + FB, ...; shuffle tree; the waves in order
-template <int NK>
-__device__ __forceinline__ void cg_block_totals(const double* __restrict__ part, int nblk, int stride, double* tot) {
-  __shared__ double sh[NK][FB / 64];
-  double s[NK];
-#pragma unroll
-  for (int k = 0; k < NK; ++k) s[k] = 0.0;
-  for (int b = threadIdx.x; b < nblk; b += FB)
-#pragma unroll
-    for (int k = 0; k < NK; ++k) s[k] += part[stride * b + k];
-#pragma unroll
-  for (int k = 0; k < NK; ++k) {
-    s[k] = wave_sum(s[k]);
-    if ((threadIdx.x & 63) == 0) sh[k][threadIdx.x >> 6] = s[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < NK; ++k) {
-    double a = 0.0;
-    for (int q = 0; q < FB / 64; ++q) a += sh[k][q];
-    tot[k] = a;
-  }
-}
-
 // B d (symmetric product from lower storage, like k_spmv_csr in mode 2) and, on the way, the block partials of
 // d.Bd, z.d, d.d, grad.d, z.Bd: one launch instead of two
 template <int LANES>
@@ -72,21 +47,12 @@ __global__ __launch_bounds__(FB) void k_cg_spmv_dots(int n, const CgCtl* __restr
                                                      const double* __restrict__ z, const double* __restrict__ grad,
                                                      double* __restrict__ Bd, double* __restrict__ out) {
   if (c->stop) return;
-  __shared__ double sh[5][FB / 64];
   const int sub = threadIdx.x % LANES;
   const int rows_per_block = FB / LANES;
   double t[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
   for (int row = blockIdx.x * rows_per_block + threadIdx.x / LANES; row < n; row += gridDim.x * rows_per_block) {
-    double s = 0.0;
-    const int p1 = ptr[row + 1];
-    for (int p = ptr[row] + sub; p < p1; p += LANES) s += val[p] * d[idx[p]];
-    const int q1 = ptr2[row + 1];
-    for (int q = ptr2[row] + sub; q < q1; q += LANES) {
-      const int col = idx2[q];
-      if (col != row) s += val2[q] * d[col];
-    }
-#pragma unroll
-    for (int o = LANES / 2; o > 0; o >>= 1) s += __shfl_down(s, o, LANES);
+    double s = csr_row_add<LANES>(0.0, row, sub, ptr, idx, val, d);
+    s = lanes_sum<LANES>(csr_offdiag_add<LANES>(s, row, sub, ptr2, idx2, val2, d));
     if (sub == 0) {
       Bd[row] = s;
       const double di = d[row], zi = z[row];
@@ -97,17 +63,7 @@ __global__ __launch_bounds__(FB) void k_cg_spmv_dots(int n, const CgCtl* __restr
       t[4] += zi * s;
     }
   }
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    t[k] = wave_sum(t[k]);
-    if ((threadIdx.x & 63) == 0) sh[k][threadIdx.x >> 6] = t[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < 5) {
-    double a = 0.0;
-    for (int q = 0; q < FB / 64; ++q) a += sh[threadIdx.x][q];
-    out[5 * blockIdx.x + threadIdx.x] = a;
-  }
+  block_partials<5>(t, out);
 }
 
 // steihaug_collect_rayleigh (steihaug_solver.c:150-182): the Rayleigh quotient of the direction whose product has just
@@ -135,7 +91,7 @@ __global__ __launch_bounds__(FB) void k_cg_step_update1(int n, const CgCtl* __re
     return;
   }
   double tot[5];
-  cg_block_totals<5>(part, nblk, 5, tot);
+  block_totals<5>(part, nblk, 5, tot);
   const double dBd = tot[0], z_dot_d = tot[1], d_nrm_sq = tot[2], gd = tot[3], zBd = tot[4];
   double coef = 0.0;
   bool final_step = false;
@@ -205,7 +161,7 @@ __global__ __launch_bounds__(FB) void k_cg_head(int n, const CgCtl* __restrict__
     return;
   }
   double tot[1];
-  cg_block_totals<1>(part_rg, nblk_rg, stride, tot);
+  block_totals<1>(part_rg, nblk_rg, stride, tot);
   const double beta = tot[0] / ci->rg;
   if (writer) {
     cg_ctl_copy(co, ci);
@@ -213,21 +169,12 @@ __global__ __launch_bounds__(FB) void k_cg_head(int n, const CgCtl* __restrict__
     co->rg = tot[0];
     co->it = ci->it + 1;
   }
-  __shared__ double sh[5][FB / 64];
   const int sub = threadIdx.x % LANES;
   const int rows_per_block = FB / LANES;
   double t[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
   for (int row = blockIdx.x * rows_per_block + threadIdx.x / LANES; row < n; row += gridDim.x * rows_per_block) {
-    double s = 0.0;
-    const int p1 = ptr[row + 1];
-    for (int p = ptr[row] + sub; p < p1; p += LANES) s += val[p] * g[idx[p]];
-    const int q1 = ptr2[row + 1];
-    for (int q = ptr2[row] + sub; q < q1; q += LANES) {
-      const int col = idx2[q];
-      if (col != row) s += val2[q] * g[col];
-    }
-#pragma unroll
-    for (int o = LANES / 2; o > 0; o >>= 1) s += __shfl_down(s, o, LANES);
+    double s = csr_row_add<LANES>(0.0, row, sub, ptr, idx, val, g);
+    s = lanes_sum<LANES>(csr_offdiag_add<LANES>(s, row, sub, ptr2, idx2, val2, g));
     if (sub == 0) {
       const double bd = -1.0 * s + beta * Bd[row];
       const double di = -1.0 * g[row] + beta * d[row];
@@ -241,17 +188,7 @@ __global__ __launch_bounds__(FB) void k_cg_head(int n, const CgCtl* __restrict__
       t[4] += zi * bd;
     }
   }
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    t[k] = wave_sum(t[k]);
-    if ((threadIdx.x & 63) == 0) sh[k][threadIdx.x >> 6] = t[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < 5) {
-    double a = 0.0;
-    for (int q = 0; q < FB / 64; ++q) a += sh[threadIdx.x][q];
-    out[5 * blockIdx.x + threadIdx.x] = a;
-  }
+  block_partials<5>(t, out);
 }
 
 // ---- GLTR, device-controlled phase -----------------------------------------------------------------------------------
@@ -278,34 +215,18 @@ __global__ __launch_bounds__(FB) void k_lz_spmv_dot(int n, const LzCtl* __restri
                                                     const double* __restrict__ val2, const double* __restrict__ y,
                                                     double* __restrict__ Hy, double* __restrict__ out) {
   if (c->stop) return;
-  __shared__ double sh[FB / 64];
   const int sub = threadIdx.x % LANES;
   const int rows_per_block = FB / LANES;
-  double t = 0.0;
+  double t[1] = {0.0};
   for (int row = blockIdx.x * rows_per_block + threadIdx.x / LANES; row < n; row += gridDim.x * rows_per_block) {
-    double s = 0.0;
-    const int p1 = ptr[row + 1];
-    for (int p = ptr[row] + sub; p < p1; p += LANES) s += val[p] * y[idx[p]];
-    const int q1 = ptr2[row + 1];
-    for (int q = ptr2[row] + sub; q < q1; q += LANES) {
-      const int col = idx2[q];
-      if (col != row) s += val2[q] * y[col];
-    }
-#pragma unroll
-    for (int o = LANES / 2; o > 0; o >>= 1) s += __shfl_down(s, o, LANES);
+    double s = csr_row_add<LANES>(0.0, row, sub, ptr, idx, val, y);
+    s = lanes_sum<LANES>(csr_offdiag_add<LANES>(s, row, sub, ptr2, idx2, val2, y));
     if (sub == 0) {
       Hy[row] = s;
-      t += y[row] * s;
+      t[0] += y[row] * s;
     }
   }
-  t = wave_sum(t);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = t;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double a = 0.0;
-    for (int q = 0; q < FB / 64; ++q) a += sh[q];
-    out[blockIdx.x] = a;
-  }
+  block_partials<1>(t, out);
 }
 
 __device__ __forceinline__ void lz_ctl_copy(LzCtl* __restrict__ o, const LzCtl* __restrict__ i) {
@@ -344,7 +265,7 @@ __global__ __launch_bounds__(FB) void k_lz_step(int n, const LzCtl* __restrict__
   int state = 0;
   if (k > 0) {
     double tx[1];
-    cg_block_totals<1>(part_x, xb, xstride, tx);
+    block_totals<1>(part_x, xb, xstride, tx);
     __syncthreads();  // (the totals of the second sum below reuse the shared scratch)
     gk = tx[0] > 0.0 ? sqrt(tx[0]) : 0.0;
     // close iteration k-1: delta_{k-1}, gamma_{k-1} -> pivot, last component of the Newton step of T, CG quantities
@@ -380,7 +301,7 @@ __global__ __launch_bounds__(FB) void k_lz_step(int n, const LzCtl* __restrict__
     return;
   }
   double td[1];
-  cg_block_totals<1>(part, nblk, 1, td);
+  block_totals<1>(part, nblk, 1, td);
   const double inv = 1.0 / gk;
   const double dk = td[0] * inv * inv;
   if (writer) {
@@ -419,7 +340,7 @@ __global__ __launch_bounds__(FB) void k_lanczos_next_dev(int n, const double* __
                                                          const double* __restrict__ w, double* __restrict__ out,
                                                          double* __restrict__ delta_out) {
   double tot[1];
-  cg_block_totals<1>(part, nblk, 3, tot);
+  block_totals<1>(part, nblk, 3, tot);
   if (blockIdx.x == 0 && threadIdx.x == 0) *delta_out = tot[0];
   const double a = -tot[0] / gamma_k;
   for (int i = blockIdx.x * FB + threadIdx.x; i < n; i += gridDim.x * FB) {
@@ -432,34 +353,84 @@ __global__ __launch_bounds__(FB) void k_lanczos_next_dev(int n, const double* __
 }  // namespace hipfact
 #else
 
+// lanes per row of the products with the symmetric Hessian (both triangles from lower storage)
+static int hess_lanes(const hipfact_spmat* hess, int n) { return spmv_lanes(2.0 * (double)hess->nnz / std::max(n, 1)); }
 
-extern "C++" {
-template <int LANES>
-static int launch_cg_spmv(hipStream_t st, int n, const CgCtl* c, hipfact_spmat* M, const double* d, const double* z,
+// The launches of the product-with-dots kernels, L lanes per row; they return the number of blocks (= partials).
+static int launch_cg_spmv(hipStream_t st, int L, int n, const CgCtl* c, hipfact_spmat* M, const double* d, const double* z,
                           const double* grad, double* Bd, double* part) {
-  const int nblk = std::max(1, std::min(CG_BLOCKS, (n + FB / LANES - 1) / (FB / LANES)));
-  hipLaunchKernelGGL(k_cg_spmv_dots<LANES>, dim3(nblk), dim3(FB), 0, st, n, c, M->tp.as<int>(), M->ti.as<int>(),
-                     M->tval.as<double>(), M->cp.as<int>(), M->ri.as<int>(), M->val.as<double>(), d, z, grad, Bd, part);
+  const int nblk = row_blocks(n, L, CG_BLOCKS);
+  with_lanes(L, [&](auto lanes) {
+    hipLaunchKernelGGL(k_cg_spmv_dots<decltype(lanes)::value>, dim3(nblk), dim3(FB), 0, st, n, c, M->tp.as<int>(),
+                       M->ti.as<int>(), M->tval.as<double>(), M->cp.as<int>(), M->ri.as<int>(), M->val.as<double>(), d, z,
+                       grad, Bd, part);
+  });
   return nblk;
 }
-template <int LANES>
-static int launch_cg_head(hipStream_t st, int n, const CgCtl* ci, CgCtl* co, const double* part_rg, int nblk_rg, int stride,
-                          hipfact_spmat* M, const double* g, double* d, double* Bd, const double* z, const double* grad,
+static int launch_cg_head(hipStream_t st, int L, int n, const CgCtl* ci, CgCtl* co, const double* part_rg, int nblk_rg,
+                          int stride, hipfact_spmat* M, const double* g, double* d, double* Bd, const double* z,
+                          const double* grad, double* part) {
+  const int nblk = row_blocks(n, L, CG_BLOCKS);
+  with_lanes(L, [&](auto lanes) {
+    hipLaunchKernelGGL(k_cg_head<decltype(lanes)::value>, dim3(nblk), dim3(FB), 0, st, n, ci, co, part_rg, nblk_rg, stride,
+                       M->tp.as<int>(), M->ti.as<int>(), M->tval.as<double>(), M->cp.as<int>(), M->ri.as<int>(),
+                       M->val.as<double>(), g, d, Bd, z, grad, part);
+  });
+  return nblk;
+}
+static int launch_lz_spmv(hipStream_t st, int L, int n, const LzCtl* c, hipfact_spmat* M, const double* y, double* Hy,
                           double* part) {
-  const int nblk = std::max(1, std::min(CG_BLOCKS, (n + FB / LANES - 1) / (FB / LANES)));
-  hipLaunchKernelGGL(k_cg_head<LANES>, dim3(nblk), dim3(FB), 0, st, n, ci, co, part_rg, nblk_rg, stride, M->tp.as<int>(),
-                     M->ti.as<int>(), M->tval.as<double>(), M->cp.as<int>(), M->ri.as<int>(), M->val.as<double>(), g, d, Bd, z,
-                     grad, part);
+  const int nblk = row_blocks(n, L, CG_BLOCKS);
+  with_lanes(L, [&](auto lanes) {
+    hipLaunchKernelGGL(k_lz_spmv_dot<decltype(lanes)::value>, dim3(nblk), dim3(FB), 0, st, n, c, M->tp.as<int>(),
+                       M->ti.as<int>(), M->tval.as<double>(), M->cp.as<int>(), M->ri.as<int>(), M->val.as<double>(), y, Hy,
+                       part);
+  });
   return nblk;
 }
-template <int LANES>
-static int launch_lz_spmv(hipStream_t st, int n, const LzCtl* c, hipfact_spmat* M, const double* y, double* Hy, double* part) {
-  const int nblk = std::max(1, std::min(CG_BLOCKS, (n + FB / LANES - 1) / (FB / LANES)));
-  hipLaunchKernelGGL(k_lz_spmv_dot<LANES>, dim3(nblk), dim3(FB), 0, st, n, c, M->tp.as<int>(), M->ti.as<int>(),
-                     M->tval.as<double>(), M->cp.as<int>(), M->ri.as<int>(), M->val.as<double>(), y, Hy, part);
-  return nblk;
+
+// The device loops run their projections without a residual check (no host in between to continue a refinement):
+// only on a factorisation that has been judged - no correction pass in its solves
+static bool unchecked_solves_ok(const hipfact_handle* h) {
+  return h->refine_steps == 0 || (h->refine_adaptive && h->refine_inline == 0 && !h->inline_probe);
 }
-}  // extern "C++"
+
+// ... and the last of those projections (right-hand side b, result in d_cg_z, both untouched since) is verified when
+// the loop has ended, like every k-th solve.  *ok = false: the first pass alone does not meet the tolerance on this
+// factorisation after all - its solves carry a correction pass from here on, and the caller redoes the step with the
+// host in the loop.
+static int last_unchecked_solve_ok(hipfact_handle* h, const double* b, bool* ok) {
+  *ok = true;
+  if (h->refine_steps == 0) return HIPFACT_OK;
+  residual_async(h, b, h->d_cg_z.as<double>(), h->d_res.as<double>(), true);  // (with its verdict launch)
+  HCHECK(h, hipStreamSynchronize(h->stream));
+  RefineCtl rcx;
+  memcpy(&rcx, h->h_ctl.p, sizeof(rcx));
+  h->solve_seq++;  // (the device counted a first residual)
+  *ok = rcx.done && rcx.status == 0;
+  if (!*ok) {
+    h->wc_hint = false;
+    h->refine_inline = std::max(h->refine_inline, std::min(h->refine_steps, 1));
+  }
+  return HIPFACT_OK;
+}
+
+// d_cg_z = P b (skipped on the device when *skip is set) together with the block partials of b_x . z_x in `part`: the
+// x-update workgroups of the tree launch leave them (XupdIn::dot_out), or - dense columns outside the tree, unfused x
+// update - a launch of k_dots3 behind it.  Returns where they are: part[stride * b], b < blocks.
+struct DotPartials {
+  int blocks, stride;
+};
+static DotPartials project_with_dot(hipfact_handle* h, int n, const double* b, const int* skip, double* part) {
+  h->x_dot_out = part;
+  h->x_dot_blocks = 0;
+  solve_once_async(h, b, h->d_cg_z.as<double>(), false, skip);
+  h->x_dot_out = nullptr;
+  if (h->x_dot_blocks > 0) return {h->x_dot_blocks, 1};
+  hipLaunchKernelGGL(k_dots3, dim3(DOT_BLOCKS), dim3(FB), 0, h->stream, n, b, h->d_cg_z.as<double>(), nullptr, nullptr,
+                     nullptr, nullptr, part);
+  return {DOT_BLOCKS, 3};
+}
 
 // The device-controlled phase of GLTR behind the first projection (kernels above).  Q[0], tb[0] = y_0 and gamma_0 are
 // in place and y_0 still sits in d_cg_z.  On return with *used: iterations 0 .. *k_done - 1 are complete, delta[0 ..
@@ -473,9 +444,7 @@ static int lz_device_phase(hipfact_handle* h, hipfact_spmat* hess, int n, double
                            std::vector<double>& gamma, int* k_done, bool* used, bool* touched) {
   *used = false;
   *touched = false;
-  if (!h->lz_device_loop || !hess || kmax < 2 ||
-      !(h->refine_steps == 0 || (h->refine_adaptive && h->refine_inline == 0 && !h->inline_probe)))
-    return HIPFACT_OK;
+  if (!h->lz_device_loop || !hess || kmax < 2 || !unchecked_solves_ok(h)) return HIPFACT_OK;
   hipStream_t st = h->stream;
   *touched = true;
   const int vb = nblocks(n);
@@ -498,47 +467,31 @@ static int lz_device_phase(hipfact_handle* h, hipfact_spmat* hess, int n, double
   double* part = h->d_cg_dots.as<double>();
   double* part_x = part + 5 * CG_BLOCKS;
   const double* y = h->d_cg_z.as<double>();
-  const double avg = 2.0 * (double)hess->nnz / std::max(n, 1);
+  const int L = hess_lanes(hess, n);
   // (the solves below go past solve_async: its count of solves towards the dense top block of the tree is kept here)
   int rc;
   h->solves_this_factor += 2;
   if ((rc = top_block_touch(h))) return rc;
   LzCtl host;
   memset(&host, 0, sizeof(host));
-  int xb = 0, xstride = 1, solves = 0, written = 0, nblk = 0;
+  DotPartials px = {0, 1};
+  int solves = 0, written = 0;
   for (int k = 0; k <= kmax && !host.stop;) {
     for (int j = 0; j < CG_CHUNK && k <= kmax; ++j, ++k) {
       const LzCtl* ci = c + (k & 1);
       LzCtl* co = c + ((k + 1) & 1);
-      if (avg <= 2.5)
-        nblk = launch_lz_spmv<1>(st, n, ci, hess, y, Hy, part);
-      else if (avg <= 10.0)
-        nblk = launch_lz_spmv<4>(st, n, ci, hess, y, Hy, part);
-      else if (avg <= 48.0)
-        nblk = launch_lz_spmv<16>(st, n, ci, hess, y, Hy, part);
-      else
-        nblk = launch_lz_spmv<64>(st, n, ci, hess, y, Hy, part);
+      const int nblk = launch_lz_spmv(st, L, n, ci, hess, y, Hy, part);
       double* tn = tb[(k + 1) % 3];
-      hipLaunchKernelGGL(k_lz_step, dim3(std::min(vb, 128)), dim3(FB), 0, st, n, ci, co, k, part, nblk, part_x, xb, xstride,
-                         h->d_cg_z.as<double>(), Hy, tb[(k + 2) % 3], tb[k % 3],
+      hipLaunchKernelGGL(k_lz_step, dim3(std::min(vb, 128)), dim3(FB), 0, st, n, ci, co, k, part, nblk, part_x, px.blocks,
+                         px.stride, h->d_cg_z.as<double>(), Hy, tb[(k + 2) % 3], tb[k % 3],
                          Q + (size_t)std::min(k, kmax - 1) * n, tn, gam, del);
       written = (k + 1) & 1;
       if (k == kmax) {  // (that step only closes iteration kmax - 1)
         ++k;
         break;
       }
-      h->x_dot_out = part_x;
-      h->x_dot_blocks = 0;
-      solve_once_async(h, tn, h->d_cg_z.as<double>(), false, &co->stop);
-      h->x_dot_out = nullptr;
+      px = project_with_dot(h, n, tn, &co->stop, part_x);
       ++solves;
-      xb = h->x_dot_blocks;
-      xstride = 1;
-      if (xb == 0) {  // (dense columns outside the tree, unfused x update: the partials from a launch of their own)
-        hipLaunchKernelGGL(k_dots3, dim3(DOT_BLOCKS), dim3(FB), 0, st, n, tn, y, nullptr, nullptr, nullptr, nullptr, part_x);
-        xb = DOT_BLOCKS;
-        xstride = 3;
-      }
     }
     HCHECK(h, hipGetLastError());
     // (both copies of the block and the coefficients in one transfer)
@@ -565,21 +518,9 @@ static int lz_device_phase(hipfact_handle* h, hipfact_spmat* hess, int n, double
     return HIPFACT_EINTERNAL;
   }
   const int kd = host.k;
-  // the projections ran unchecked: the last one (right-hand side tb[kd % 3], untouched by the stopping step) is verified
-  if (h->refine_steps > 0) {
-    residual_async(h, tb[kd % 3], h->d_cg_z.as<double>(), h->d_res.as<double>(), true);  // (with its verdict launch)
-    HCHECK(h, hipStreamSynchronize(st));
-    RefineCtl rcx;
-    memcpy(&rcx, h->h_ctl.p, sizeof(rcx));
-    h->solve_seq++;  // (the device counted a first residual)
-    if (!(rcx.done && rcx.status == 0)) {
-      // (the first pass alone does not meet the tolerance on this factorisation after all: its solves carry a
-      // correction pass from here on, and *used stays false - the caller redoes the step with the host in the loop)
-      h->wc_hint = false;
-      h->refine_inline = std::max(h->refine_inline, std::min(h->refine_steps, 1));
-      return HIPFACT_OK;
-    }
-  }
+  // the last projection (right-hand side tb[kd % 3], untouched by the stopping step); on a failure *used stays false
+  bool ok;
+  if ((rc = last_unchecked_solve_ok(h, tb[kd % 3], &ok)) || !ok) return rc;
   const double* hc = reinterpret_cast<const double*>(h->h_lz_ctl.as<LzCtl>() + 2);
   h->num_solve += std::min(solves, kd);
   gamma.assign(hc, hc + kd + 1);
@@ -598,33 +539,15 @@ static int cg_chunk_enqueue(hipfact_handle* h, hipfact_spmat* hess, int n, CgCtl
   const int vb = nblocks(n);
   double* part = h->d_cg_dots.as<double>();
   double* part2 = part + 5 * CG_BLOCKS;
-  const double avg = 2.0 * (double)hess->nnz / std::max(n, 1);
-  auto lanes_of = [&] { return avg <= 2.5 ? 1 : avg <= 10.0 ? 4 : avg <= 48.0 ? 16 : 64; };
   // three launches per iteration: tests + z, r | projection | beta, d, B d (by recurrence) and the partials of the NEXT
   // iteration (k_cg_head).  The product of the first iteration was queued in front of the first chunk.
-  const int L = lanes_of();
-  const int nblk = std::max(1, std::min(CG_BLOCKS, (n + FB / L - 1) / (FB / L)));
+  const int L = hess_lanes(hess, n);
+  const int nblk = row_blocks(n, L, CG_BLOCKS);
   for (int k = 0; k < iterations; ++k) {
     hipLaunchKernelGGL(k_cg_step_update1, dim3(std::min(vb, 128)), dim3(FB), 0, st, n, c, c + 1, part, nblk, d, Bd, z, r,
                        h->cg_residual_update ? g : nullptr);
-    h->x_dot_out = part2;
-    h->x_dot_blocks = 0;
-    solve_once_async(h, h->d_cg_b.as<double>(), h->d_cg_z.as<double>(), false, &c[1].stop);
-    h->x_dot_out = nullptr;
-    int nb_rg = h->x_dot_blocks, stride = 1;
-    if (nb_rg == 0) {
-      hipLaunchKernelGGL(k_dots3, dim3(DOT_BLOCKS), dim3(FB), 0, st, n, r, g, nullptr, nullptr, nullptr, nullptr, part2);
-      nb_rg = DOT_BLOCKS;
-      stride = 3;
-    }
-    if (L == 1)
-      launch_cg_head<1>(st, n, c + 1, c, part2, nb_rg, stride, hess, g, d, Bd, z, grad, part);
-    else if (L == 4)
-      launch_cg_head<4>(st, n, c + 1, c, part2, nb_rg, stride, hess, g, d, Bd, z, grad, part);
-    else if (L == 16)
-      launch_cg_head<16>(st, n, c + 1, c, part2, nb_rg, stride, hess, g, d, Bd, z, grad, part);
-    else
-      launch_cg_head<64>(st, n, c + 1, c, part2, nb_rg, stride, hess, g, d, Bd, z, grad, part);
+    const DotPartials rg = project_with_dot(h, n, h->d_cg_b.as<double>(), &c[1].stop, part2);  // g = P[r], and r.g
+    launch_cg_head(st, L, n, c + 1, c, part2, rg.blocks, rg.stride, hess, g, d, Bd, z, grad, part);
   }
   HCHECK(h, hipGetLastError());
   return HIPFACT_OK;
@@ -637,10 +560,7 @@ static int steihaug_device_loop(hipfact_handle* h, hipfact_spmat* hess, int n, d
                                 double* Bd, const double* grad, bool* used, bool* touched, int* state_out, int* it_out) {
   *used = false;
   *touched = false;
-  // a factorisation that has been judged: no correction pass in its solves (else every projection may need the
-  // host to continue its refinement)
-  if (!h->cg_device_loop || !hess || !(h->refine_steps == 0 || (h->refine_adaptive && h->refine_inline == 0 && !h->inline_probe)))
-    return HIPFACT_OK;
+  if (!h->cg_device_loop || !hess || !unchecked_solves_ok(h)) return HIPFACT_OK;
   hipStream_t st = h->stream;
   *touched = true;
   HCHECK(h, h->d_cg_ctl.ensure(2 * sizeof(CgCtl)));
@@ -659,18 +579,8 @@ static int steihaug_device_loop(hipfact_handle* h, hipfact_spmat* hess, int n, d
   CgCtl* c = h->d_cg_ctl.as<CgCtl>();
   CgCtl host;
   int rc;
-  {  // the product B d of the first iteration (the later ones ride in k_cg_head)
-    const double avg = 2.0 * (double)hess->nnz / std::max(n, 1);
-    double* part = h->d_cg_dots.as<double>();
-    if (avg <= 2.5)
-      launch_cg_spmv<1>(st, n, c, hess, d, z, grad, Bd, part);
-    else if (avg <= 10.0)
-      launch_cg_spmv<4>(st, n, c, hess, d, z, grad, Bd, part);
-    else if (avg <= 48.0)
-      launch_cg_spmv<16>(st, n, c, hess, d, z, grad, Bd, part);
-    else
-      launch_cg_spmv<64>(st, n, c, hess, d, z, grad, Bd, part);
-  }
+  // the product B d of the first iteration (the later ones ride in k_cg_head)
+  launch_cg_spmv(st, hess_lanes(hess, n), n, c, hess, d, z, grad, Bd, h->d_cg_dots.as<double>());
   const int budget = (max_iter == -1) ? (1 << 20) : max_iter + 1;
   for (int done = 0; done < budget; done += CG_CHUNK) {
     // (direct launches - a captured graph of a chunk measured slower -, no more iterations than the cap allows: the last
@@ -692,19 +602,9 @@ static int steihaug_device_loop(hipfact_handle* h, hipfact_spmat* hess, int n, d
   }
   h->tr.ray_min = host.ray_min;
   h->tr.ray_max = host.ray_max;
-  // the projections ran unchecked: the last one (r has not changed since) is verified now, like every k-th solve
-  if (h->refine_steps > 0) {
-    residual_async(h, h->d_cg_b.as<double>(), h->d_cg_z.as<double>(), h->d_res.as<double>(), true);  // (with its verdict launch)
-    HCHECK(h, hipStreamSynchronize(st));
-    RefineCtl rcx;
-    memcpy(&rcx, h->h_ctl.p, sizeof(rcx));
-    h->solve_seq++;  // (the device counted a first residual)
-    if (!(rcx.done && rcx.status == 0)) {  // not converged: *used stays false, the host loop redoes the step
-      h->wc_hint = false;
-      h->refine_inline = std::max(h->refine_inline, std::min(h->refine_steps, 1));
-      return HIPFACT_OK;
-    }
-  }
+  // the last projection (r has not changed since); on a failure *used stays false, the host loop redoes the step
+  bool ok;
+  if ((rc = last_unchecked_solve_ok(h, h->d_cg_b.as<double>(), &ok)) || !ok) return rc;
   h->num_solve += host.it + 1;
   *state_out = h->tr.timed_out ? 5 : host.state;  // (5: the time limit; z holds the iterate reached)
   *it_out = host.it;

@@ -36,41 +36,26 @@ __global__ __launch_bounds__(FB) void k_lsqr_forward(int r, int mv, const int* _
                                                      const int* __restrict__ jv_idx, const double* __restrict__ jv_val,
                                                      const double* __restrict__ z, double s1, double s2,
                                                      double* __restrict__ u, double* __restrict__ part) {
-  __shared__ double sh[FB / 64];
   const int sub = threadIdx.x % LANES;
   const int rows_per_block = FB / LANES;
   const int rows = r + mv;
-  double t = 0.0;
+  double t[1] = {0.0};
   for (int row = blockIdx.x * rows_per_block + threadIdx.x / LANES; row < rows; row += gridDim.x * rows_per_block) {
     double s = 0.0;
-    if (row < r) {
-      if (jr_ptr) {
-        const int p1 = jr_ptr[row + 1];
-        for (int p = jr_ptr[row] + sub; p < p1; p += LANES) s += jr_val[p] * z[jr_idx[p]];
-      } else if (sub == 0) {
-        s = yr[row];
-      }
-    } else {
-      const int q = row - r;
-      const int p1 = jv_ptr[q + 1];
-      for (int p = jv_ptr[q] + sub; p < p1; p += LANES) s += jv_val[p] * z[jv_idx[p]];
-    }
-#pragma unroll
-    for (int o = LANES / 2; o > 0; o >>= 1) s += __shfl_down(s, o, LANES);
+    if (row >= r)
+      s = csr_row_add<LANES>(s, row - r, sub, jv_ptr, jv_idx, jv_val, z);
+    else if (jr_ptr)
+      s = csr_row_add<LANES>(s, row, sub, jr_ptr, jr_idx, jr_val, z);
+    else if (sub == 0)
+      s = yr[row];
+    s = lanes_sum<LANES>(s);
     if (sub == 0) {
       const double un = s1 * s + s2 * u[row];
       u[row] = un;
-      t += un * un;
+      t[0] += un * un;
     }
   }
-  t = wave_sum(t);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = t;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double a = 0.0;
-    for (int q = 0; q < FB / 64; ++q) a += sh[q];
-    part[blockIdx.x] = a;
-  }
+  block_partials<1>(t, part);
 }
 
 // bt[j] = (J_r' u^_r + J_v' u^_v)_j / beta over the n rows of the transposes (the CSC of J_r / J_v is the CSR of its
@@ -85,7 +70,7 @@ __global__ __launch_bounds__(FB) void k_lsqr_adjoint(int n, int r, const int* __
                                                      const double* __restrict__ u, const double* __restrict__ upart,
                                                      int nub, double* __restrict__ bt, double* __restrict__ beta_out) {
   double tot[1];
-  cg_block_totals<1>(upart, nub, 1, tot);
+  block_totals<1>(upart, nub, 1, tot);
   const double beta = sqrt(tot[0]);
   const double inv = beta != 0.0 ? 1.0 / beta : 1.0;
   if (blockIdx.x == 0 && threadIdx.x == 0) beta_out[0] = beta;
@@ -94,18 +79,12 @@ __global__ __launch_bounds__(FB) void k_lsqr_adjoint(int n, int r, const int* __
   const double* __restrict__ uv = u + r;
   for (int row = blockIdx.x * rows_per_block + threadIdx.x / LANES; row < n; row += gridDim.x * rows_per_block) {
     double s = 0.0;
-    if (jr_ptr) {
-      const int p1 = jr_ptr[row + 1];
-      for (int p = jr_ptr[row] + sub; p < p1; p += LANES) s += jr_val[p] * u[jr_idx[p]];
-    } else if (yt && sub == 0) {
+    if (jr_ptr)
+      s = csr_row_add<LANES>(s, row, sub, jr_ptr, jr_idx, jr_val, u);
+    else if (yt && sub == 0)
       s = yt[row];
-    }
-    if (jv_ptr) {
-      const int p1 = jv_ptr[row + 1];
-      for (int p = jv_ptr[row] + sub; p < p1; p += LANES) s += jv_val[p] * uv[jv_idx[p]];
-    }
-#pragma unroll
-    for (int o = LANES / 2; o > 0; o >>= 1) s += __shfl_down(s, o, LANES);
+    if (jv_ptr) s = csr_row_add<LANES>(s, row, sub, jv_ptr, jv_idx, jv_val, uv);
+    s = lanes_sum<LANES>(s);
     if (sub == 0) bt[row] = s * inv;
   }
 }
@@ -115,29 +94,20 @@ __global__ __launch_bounds__(FB) void k_lsqr_adjoint(int n, int r, const int* __
 __global__ __launch_bounds__(FB) void k_lsqr_vupd(int n, const double* __restrict__ z, const double* __restrict__ beta_in,
                                                   double inv_alpha, int first, double* __restrict__ v,
                                                   double* __restrict__ part) {
-  __shared__ double sh[FB / 64];
   const double cb = first ? 0.0 : beta_in[0] * inv_alpha;
-  double t = 0.0;
+  double t[1] = {0.0};
   for (int i = blockIdx.x * FB + threadIdx.x; i < n; i += gridDim.x * FB) {
     const double vi = first ? z[i] : z[i] - cb * v[i];
     v[i] = vi;
-    t += vi * vi;
+    t[0] += vi * vi;
   }
-  t = wave_sum(t);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = t;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double a = 0.0;
-    for (int q = 0; q < FB / 64; ++q) a += sh[q];
-    part[blockIdx.x] = a;
-  }
+  block_partials<1>(t, part);
 }
 
 // x <- x + a w, w <- s v^ - b w; block partials of x.x, x.w, w.w of the new vectors in part[3 * blockIdx.x + k]
 __global__ __launch_bounds__(FB) void k_lsqr_xw(int n, double a, double s, double b, const double* __restrict__ v,
                                                 double* __restrict__ x, double* __restrict__ w,
                                                 double* __restrict__ part) {
-  __shared__ double sh[3][FB / 64];
   double t[3] = {0.0, 0.0, 0.0};
   for (int i = blockIdx.x * FB + threadIdx.x; i < n; i += gridDim.x * FB) {
     const double wi = w[i];
@@ -149,17 +119,7 @@ __global__ __launch_bounds__(FB) void k_lsqr_xw(int n, double a, double s, doubl
     t[1] += xn * wn;
     t[2] += wn * wn;
   }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    t[k] = wave_sum(t[k]);
-    if ((threadIdx.x & 63) == 0) sh[k][threadIdx.x >> 6] = t[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    double acc = 0.0;
-    for (int q = 0; q < FB / 64; ++q) acc += sh[threadIdx.x][q];
-    part[3 * blockIdx.x + threadIdx.x] = acc;
-  }
+  block_partials<3>(t, part);
 }
 
 }  // namespace hipfact
@@ -184,11 +144,6 @@ static int lsqr_callback(hipfact_handle* h, const hipfact_lsqr_op* op, int trans
   return HIPFACT_OK;
 }
 
-static int lsqr_lanes(long long nnz, int rows) {
-  const double avg = (double)nnz / std::max(rows, 1);
-  return avg <= 2.5 ? 1 : avg <= 10.0 ? 4 : avg <= 48.0 ? 16 : 64;
-}
-
 // the device side of one solve: matrices, vectors, and the area the host reads at the synchronisation
 struct LsqrDev {
   int n, r, mv, N;
@@ -198,42 +153,22 @@ struct LsqrDev {
   int nub, vb;
 };
 
-extern "C++" {
-template <int L>
-static int launch_lsqr_forward(hipStream_t st, const LsqrDev& D, const double* z, double s1, double s2) {
-  const int nblk = std::max(1, std::min(LSQR_BLOCKS, (D.r + D.mv + FB / L - 1) / (FB / L)));
-  hipLaunchKernelGGL(k_lsqr_forward<L>, dim3(nblk), dim3(FB), 0, st, D.r, D.mv, D.jr ? D.jr->tp.as<int>() : nullptr,
-                     D.jr ? D.jr->ti.as<int>() : nullptr, D.jr ? D.jr->tval.as<double>() : nullptr, D.yr,
-                     D.jv ? D.jv->tp.as<int>() : nullptr, D.jv ? D.jv->ti.as<int>() : nullptr,
-                     D.jv ? D.jv->tval.as<double>() : nullptr, z, s1, s2, D.u, D.part_u);
-  return nblk;
-}
-template <int L>
-static void launch_lsqr_adjoint(hipStream_t st, const LsqrDev& D, const double* yt) {
-  const int nblk = std::max(1, std::min(LSQR_BLOCKS, (D.n + FB / L - 1) / (FB / L)));
-  hipLaunchKernelGGL(k_lsqr_adjoint<L>, dim3(nblk), dim3(FB), 0, st, D.n, D.r, D.jr ? D.jr->cp.as<int>() : nullptr,
-                     D.jr ? D.jr->ri.as<int>() : nullptr, D.jr ? D.jr->val.as<double>() : nullptr, yt,
-                     D.jv ? D.jv->cp.as<int>() : nullptr, D.jv ? D.jv->ri.as<int>() : nullptr,
-                     D.jv ? D.jv->val.as<double>() : nullptr, D.u, D.part_u, D.nub, D.bt, D.sc);
-}
-}  // extern "C++"
-
 // u^ <- s1 [J_r; J_v] (P v^) + s2 u^ (P v^ in the head of d_cg_z)
 static int lsqr_forward(hipfact_handle* h, const hipfact_lsqr_op* op, LsqrDev& D, double s1, double s2) {
   const double* z = h->d_cg_z.as<double>();
   int rc;
   if (!D.jr && D.r > 0 && (rc = lsqr_callback(h, op, 0, z, D.n, D.yr, D.r))) return rc;
   const long long nnz = (D.jr ? D.jr->nnz : D.r) + (D.jv ? D.jv->nnz : 0);
-  const int L = lsqr_lanes(nnz, D.r + D.mv);
-  hipStream_t st = h->stream;
-  if (L == 1)
-    D.nub = launch_lsqr_forward<1>(st, D, z, s1, s2);
-  else if (L == 4)
-    D.nub = launch_lsqr_forward<4>(st, D, z, s1, s2);
-  else if (L == 16)
-    D.nub = launch_lsqr_forward<16>(st, D, z, s1, s2);
-  else
-    D.nub = launch_lsqr_forward<64>(st, D, z, s1, s2);
+  const int rows = D.r + D.mv;
+  const int L = spmv_lanes((double)nnz / std::max(rows, 1));
+  D.nub = row_blocks(rows, L, LSQR_BLOCKS);
+  with_lanes(L, [&](auto lanes) {
+    hipLaunchKernelGGL(k_lsqr_forward<decltype(lanes)::value>, dim3(D.nub), dim3(FB), 0, h->stream, D.r, D.mv,
+                       D.jr ? D.jr->tp.as<int>() : nullptr, D.jr ? D.jr->ti.as<int>() : nullptr,
+                       D.jr ? D.jr->tval.as<double>() : nullptr, D.yr, D.jv ? D.jv->tp.as<int>() : nullptr,
+                       D.jv ? D.jv->ti.as<int>() : nullptr, D.jv ? D.jv->tval.as<double>() : nullptr, z, s1, s2, D.u,
+                       D.part_u);
+  });
   HCHECK(h, hipGetLastError());
   return HIPFACT_OK;
 }
@@ -244,17 +179,15 @@ static int lsqr_adjoint(hipfact_handle* h, const hipfact_lsqr_op* op, LsqrDev& D
   const bool cb = !D.jr && D.r > 0;
   if (cb && (rc = lsqr_callback(h, op, 1, D.u, D.r, D.yt, D.n))) return rc;
   const long long nnz = (D.jr ? D.jr->nnz : 0) + (D.jv ? D.jv->nnz : 0);
-  const int L = lsqr_lanes(nnz, D.n);
-  hipStream_t st = h->stream;
+  const int L = spmv_lanes((double)nnz / std::max(D.n, 1));
   const double* yt = cb ? D.yt : nullptr;
-  if (L == 1)
-    launch_lsqr_adjoint<1>(st, D, yt);
-  else if (L == 4)
-    launch_lsqr_adjoint<4>(st, D, yt);
-  else if (L == 16)
-    launch_lsqr_adjoint<16>(st, D, yt);
-  else
-    launch_lsqr_adjoint<64>(st, D, yt);
+  with_lanes(L, [&](auto lanes) {
+    hipLaunchKernelGGL(k_lsqr_adjoint<decltype(lanes)::value>, dim3(row_blocks(D.n, L, LSQR_BLOCKS)), dim3(FB), 0,
+                       h->stream, D.n, D.r, D.jr ? D.jr->cp.as<int>() : nullptr, D.jr ? D.jr->ri.as<int>() : nullptr,
+                       D.jr ? D.jr->val.as<double>() : nullptr, yt, D.jv ? D.jv->cp.as<int>() : nullptr,
+                       D.jv ? D.jv->ri.as<int>() : nullptr, D.jv ? D.jv->val.as<double>() : nullptr, D.u, D.part_u, D.nub,
+                       D.bt, D.sc);
+  });
   HCHECK(h, hipGetLastError());
   return HIPFACT_OK;
 }

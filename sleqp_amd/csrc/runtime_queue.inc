@@ -1164,14 +1164,37 @@ static int enter(hipfact_handle* h) {
   return HIPFACT_OK;
 }
 
-template <int LANES>
-static void launch_spmv(hipStream_t st, int nrows, const int* ptr, const int* idx, const double* val, const int* ptr2,
-                        const int* idx2, const double* val2, const double* x, double* y) {
-  const int rows_per_block = FB / LANES;
-  long long blocks = ((long long)nrows + rows_per_block - 1) / rows_per_block;
-  if (blocks < 1) blocks = 1;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(k_spmv_csr<LANES>, dim3((int)blocks), dim3(FB), 0, st, nrows, ptr, idx, val, ptr2, idx2, val2,
-                     x, y);
+// ---- launch geometry of the CSR product kernels (k_spmv_csr and the fused product-with-dots kernels of the Krylov
+// loops): LANES lanes per row, instances for 1, 4, 16 and 64
+// lanes per row from the average number of entries per row
+static inline int spmv_lanes(double avg_per_row) {
+  return avg_per_row <= 2.5 ? 1 : avg_per_row <= 10.0 ? 4 : avg_per_row <= 48.0 ? 16 : 64;
+}
+// f(std::integral_constant<int, L>()) for a lane count L that spmv_lanes gives
+template <class F>
+static inline void with_lanes(int L, F&& f) {
+  if (L == 1)
+    f(std::integral_constant<int, 1>());
+  else if (L == 4)
+    f(std::integral_constant<int, 4>());
+  else if (L == 16)
+    f(std::integral_constant<int, 16>());
+  else
+    f(std::integral_constant<int, 64>());
+}
+// blocks of FB threads for `rows` rows with L lanes each, one pass over the rows when `cap` blocks suffice.  Where the
+// kernel leaves a partial sum per block this is the number of partials, i.e. part of the summation order.
+static inline int row_blocks(long long rows, int L, int cap) {
+  const int rows_per_block = FB / L;
+  const long long blocks = (rows + rows_per_block - 1) / rows_per_block;
+  return (int)std::max(1LL, std::min<long long>(cap, blocks));
+}
+
+static void launch_spmv(hipStream_t st, int L, int nrows, const int* ptr, const int* idx, const double* val,
+                        const int* ptr2, const int* idx2, const double* val2, const double* x, double* y) {
+  with_lanes(L, [&](auto lanes) {
+    hipLaunchKernelGGL(k_spmv_csr<decltype(lanes)::value>, dim3(row_blocks(nrows, L, 8192)), dim3(FB), 0, st, nrows, ptr,
+                       idx, val, ptr2, idx2, val2, x, y);
+  });
 }
 
