@@ -127,7 +127,10 @@ int hipfact_condition(hipfact_handle* h, double* condition);
  * layout of THAT matrix (the caller's K, unit rows of active bounds included:
  * the backend scatters them into its own structure).  HIPFACT_ESTATE when the
  * active plan was assembled from a Jacobian (hipfact_assemble_kkt is its
- * refactorisation). */
+ * refactorisation).  The handle takes its own copy of the values as part of
+ * the factorisation this call queues: `d_vals` must not change until the
+ * stream has reached the end of that factorisation; from then on the caller
+ * may overwrite it, later solves and residuals use the handle's copy. */
 int hipfact_refactor_device(hipfact_handle* h, const double* d_vals);
 
 /* Solve with the right-hand side resident in HBM (`d_rhs`, N doubles) and

@@ -289,6 +289,7 @@ int hipfact_debug_copy(hipfact_handle* h, const char* name, void* out, size_t by
   else if (!strcmp(name, "ysol")) b = &h->d_ysol;
   else if (!strcmp(name, "uvec")) b = &h->d_uvec;
   else if (!strcmp(name, "dscale")) b = &h->d_dscale;
+  else if (!strcmp(name, "Kval")) b = &h->d_Kval;
   if (!b || !b->p || bytes > b->bytes) {
     h->error = "hipfact_debug_copy: unknown buffer or size";
     return HIPFACT_EINVAL;
@@ -389,6 +390,11 @@ int hipfact_get_info(const hipfact_handle* h, const char* name, double* value) {
   INFO("device", h->device) INFO("nnzM", P.Mi.size()) INFO("nnzA", P.Ar_src.size())
   INFO("rows_total", P.sn_rows.size()) INFO("ent_fused", h->ent_fused) INFO("ent_split", h->ent_split)
   INFO("rows_fused", h->rows_fused) INFO("rows_split", h->rows_split)
+  INFO("long_row_segments", h->n_rseg) INFO("row_scale_blocks", row_scale_in_sequence(h) ? row_scale_grid(P) : 0)
+  INFO("arena_fill_bytes", arena_fill_bytes(P))
+  // (hipfact_refactor_device takes the caller's values as the structure's own, entry by entry)
+  INFO("values_in_place",
+       h->have_plan && (!h->from_jacobian || (virtual_current(h) && h->vj->identity))) INFO("inactive_rows", h->maps_on ? h->n_inactive : 0)
 #undef INFO
   return HIPFACT_EINVAL;
 }

@@ -131,6 +131,9 @@ static int superset_refactor(hipfact_handle* h, int n, int m_total, const int* j
     cold_tick("superset plan: other uploads");
   }
   h->maps_on = true;
+  // (rows the structure covers and this working set leaves out: k_struct_fill gives them cmap = -1 below)
+  h->n_inactive = 0;
+  for (int i = 0; i < m_total; ++i) h->n_inactive += (h->sidx[(size_t)i] >= 0 && cons_index[i] < 0);
   // (a solve graph whose right-hand side and solution alias captured a copy of N_ext doubles)
   if (h->N_ext != N) drop_solve_graphs(h);
   h->N_ext = N;

@@ -41,9 +41,22 @@
 // there are active bounds, whose columns do not enter the products).  Every off-diagonal entry of
 // a column < n of K belongs to exactly one row of A, so the scatter through Ar_src covers them
 // all (the unit diagonal is never read).  norm^2 is taken over the columns that enter the products.
-// The first nbz blocks carry the zero fill of the factor arena (and of the info words) along: this
-// kernel is bound by dependent gathers and leaves the memory system idle, the fill is pure
-// bandwidth, and as two graph nodes they would run one after the other on the critical path.
+// The zero fill of the factor arena (and of the dependency counters behind it) rides in this kernel: as two graph
+// nodes fill and equilibration run one after the other on the critical path, with a kernel boundary in between.
+// Every workgroup equilibrates its rows first and then stores its grid-strided share of the zeros.  The order matters:
+// loads and stores of a wave return through one in-order counter (vmcnt), so a gather chain issued behind the stores
+// waits for them too (fill first: every dependent load of the chain then sits behind a saturated write stream); stores
+// issued last are waited for by nobody, and a workgroup that is still gathering shares its compute unit with
+// workgroups that are already storing.  Dedicated fill workgroups do not overlap the two halves either: in FRONT of
+// the grid (the arrangement up to round 6) they take every wave slot of the chip - workgroups are dispatched in index
+// order -, carry equal shares and retire together before the first equilibration workgroup is resident; BEHIND it or
+// interleaved they start late or are too few to saturate the write path.  The overlap is worth a few us only
+// (EXPERIMENTS.md, "the front of the factorisation"): the equilibration's scattered 8-byte stores and gathers keep the
+// memory system busier than its dependent gathers look - the kernel moves 228 MB in all, close to what the chip writes.
+// The grid is never smaller than the arena alone would get (row_scale_grid): workgroups beyond the rows only fill.
+// When the caller's values are still in its own array (Kcopy != null: hipfact_refactor_device) the kernel reads them
+// there and leaves the handle's copy in Kcopy on the way (it is not read inside this launch): one pass over the values
+// instead of a device-to-device copy in front and a second read here.
 // Late variables (late_my >= 0: dense_mode 1, rows perm[k] >= late_my are the late variables' own unit rows): the
 // masked columns stay out of Ar_val (the right-hand side of the constraint rows: x_d is an unknown of M) and out of
 // the products of S, but their scaled values are what the entries of M between a row and a late variable are
@@ -54,30 +67,25 @@ __global__ __launch_bounds__(FB) void k_row_scale(int m, const int* __restrict__
                                                   const int* __restrict__ dmask, const int* __restrict__ perm,
                                                   int late_my, int enable, double* __restrict__ dscale,
                                                   double* __restrict__ Ar_val, double* __restrict__ Ar_full,
-                                                  double* __restrict__ Ksc, double* __restrict__ Kprod, int nbz,
+                                                  double* __restrict__ Ksc, double* __restrict__ Kprod,
+                                                  double* __restrict__ Kcopy, long long nnzK,
                                                   double2* __restrict__ zero,
                                                   long long nzero, int* __restrict__ info, int nrseg,
                                                   const LongSeg* __restrict__ rseg, DecideIn D, int decide) {
-  if ((int)blockIdx.x < nbz) {
-    if (blockIdx.x == 0) {
-      // The deferred verdict of the previous factorisation's last solve (a residual kernel has left its partial maxima,
-      // nobody has judged them: in a loop of one solve per factorisation no tree launch follows that could) is judged
-      // against the pivot range of the factorisation it belongs to - the words behind `info`, which this block clears
-      // next.  As a one-block launch of its own in front of this kernel it cost 7 us per factorisation.
-      if (decide && D.ctl->pending) dev_refine_decide(D, 1);
-      __syncthreads();
-      if (threadIdx.x < INFO_BYTES / 4) info[threadIdx.x] = 0;
-    }
-    // (non-temporal: 107 MB of zeros that the equilibration and the product lists beside and behind this fill do not
-    // want in their L2s: -8 us on the factorisation)
-    typedef double fill_d2 __attribute__((ext_vector_type(2)));
-    for (long long i = blockIdx.x * (long long)FB + threadIdx.x; i < nzero; i += (long long)nbz * FB)
-      __builtin_nontemporal_store(fill_d2{0.0, 0.0}, reinterpret_cast<fill_d2*>(zero + i));
-    return;
+  const int nbw = gridDim.x, bid = blockIdx.x;
+  if (bid == 0) {
+    // The deferred verdict of the previous factorisation's last solve (a residual kernel has left its partial maxima,
+    // nobody has judged them: in a loop of one solve per factorisation no tree launch follows that could) is judged
+    // against the pivot range of the factorisation it belongs to - the words behind `info`, which this block clears
+    // next.  As a one-block launch of its own in front of this kernel it cost 7 us per factorisation.
+    if (decide && D.ctl->pending) dev_refine_decide(D, 1);
+    __syncthreads();
+    if (threadIdx.x < INFO_BYTES / 4) info[threadIdx.x] = 0;
   }
+  if (Kcopy)
+    for (long long i = bid * (long long)FB + threadIdx.x; i < nnzK; i += (long long)nbw * FB) Kcopy[i] = Kval[i];
   const int sub = threadIdx.x % RL;
   const int rpb = FB / RL;
-  const int nbw = gridDim.x - nbz, bid = blockIdx.x - nbz;
   const int iters = (m + nbw * rpb - 1) / (nbw * rpb);
   for (int it = 0; it < iters; ++it) {  // uniform trip count (the shuffles need whole groups)
     const int k = (it * nbw + bid) * rpb + threadIdx.x / RL;
@@ -169,6 +177,12 @@ __global__ __launch_bounds__(FB) void k_row_scale(int m, const int* __restrict__
       if (Kprod != Ksc) Kprod[e] = fixed ? 0.0 : kept;
     }
   }
+  // the fill last (16-byte units, grid-strided): nothing in this wave waits for these stores
+  // (non-temporal: 107 MB of zeros that the equilibration and the product lists beside and behind this fill do not
+  // want in their L2s: -8 us on the factorisation)
+  typedef double fill_d2 __attribute__((ext_vector_type(2)));
+  for (long long i = bid * (long long)FB + threadIdx.x; i < nzero; i += (long long)nbw * FB)
+    __builtin_nontemporal_store(fill_d2{0.0, 0.0}, reinterpret_cast<fill_d2*>(zero + i));
 }
 
 // the scales of the long rows (in front of k_row_scale): partial norms per segment, the last workgroup of a row

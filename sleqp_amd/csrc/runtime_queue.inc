@@ -71,16 +71,38 @@ static void turn_leave(hipfact_handle* h) {
   }
 }
 
-// queue the numeric factorisation on the stream (values already in d_Kval)
+// queue the numeric factorisation on the stream (values already in d_Kval, or still in h->vals_ride)
 static DecideIn decide_in(hipfact_handle* h);
+// k_diag_inactive has something to write: a row of the structure outside the working set, or a late variable
+static inline bool diag_inactive_needed(const hipfact_handle* h) {
+  const Plan& P = h->plan;
+  return P.saddle && P.m > 0 && ((h->maps_on && h->n_inactive > 0) || P.n_late > 0);
+}
+// k_row_scale is part of the factorisation sequence: it then carries the zero fill of the arena and the info words,
+// a pending refinement verdict, and the copy of values the caller hands over on the device (ONE predicate: a rider
+// announced while the kernel is not launched would silently vanish)
+static inline bool row_scale_in_sequence(const hipfact_handle* h) {
+  const Plan& P = h->plan;
+  return P.saddle && P.n > 0 && P.m > 0;
+}
+// bytes k_row_scale clears: the dependency counters of k_factor_top live behind the arena, one fill clears both
+static inline size_t arena_fill_bytes(const Plan& P) {
+  return (size_t)P.L_size * sizeof(double) + (size_t)4 * P.nsuper * sizeof(int);
+}
+// grid of k_row_scale: 16 rows per workgroup, and not fewer workgroups than the arena alone would get (every workgroup
+// stores its share of the fill: a plan with few rows and a dense S would otherwise fill ~m^2 / 2 doubles on m / 16
+// workgroups; workgroups beyond the rows only fill, the row loop's trip count is uniform)
+static inline int row_scale_grid(const Plan& P) {
+  const long long nz16 = (long long)((arena_fill_bytes(P) + 15) / 16);
+  const int for_fill = (int)std::min<long long>(2048, std::max<long long>(1, nz16 / (FB * 8)));
+  return std::max(nblocks((long long)P.m * 16), for_fill);
+}
 static int factor_enqueue(hipfact_handle* h) {
   Turn turn(h);
   const Plan& P = h->plan;
   hipStream_t st = h->stream;
-  // the dependency counters of k_factor_top live behind the arena: one fill clears both
-  const size_t fill_all = (size_t)P.L_size * sizeof(double) + (size_t)4 * P.nsuper * sizeof(int);
-  const size_t fill_bytes = fill_all;
-  const bool fill_rides = P.saddle && P.n > 0 && P.m > 0;  // inside k_row_scale (with the info words)
+  const size_t fill_bytes = arena_fill_bytes(P);
+  const bool fill_rides = row_scale_in_sequence(h);  // inside k_row_scale (with the info words)
   if (!fill_rides) {
     HCHECK(h, hipMemsetAsync(h->d_info.p, 0, INFO_BYTES, st));
     if (P.L_size > 0 && fill_bytes > 0) {
@@ -92,24 +114,26 @@ static int factor_enqueue(hipfact_handle* h) {
   const long long nM = (long long)P.Mi.size();
   const int* vmap = h->maps_on ? h->d_vmap.as<int>() : nullptr;
   double* kprod = h->maps_on ? h->d_Kprod.as<double>() : h->d_Ksc.as<double>();
-  if (P.saddle && P.n > 0) {
+  if (fill_rides) {
     // row equilibration (exact powers of two), A^ in pivot order for the solves' SpMVs, scaled
     // copy of K's values for the Schur-complement products and the x update
-    if (P.m > 0) {
+    {
       const long long nz16 = (long long)((fill_bytes + 15) / 16);
-      const int nbz = (int)std::min<long long>(2048, std::max<long long>(1, nz16 / (FB * 8)));  // (at least one block: it clears the info words)
       const bool masked = h->nd > 0 || P.n_late > 0;
+      // (the caller's array, while its values are not in d_Kval yet: k_row_scale leaves the copy there)
+      const double* kin = h->vals_ride ? h->vals_ride : h->d_Kval.as<double>();
       if (h->n_rseg > 0)  // the scales of the long rows first (segments, the last workgroup of a row decides)
         LAUNCH(PC_GATHER, k_long_row_norm, dim3(std::min(h->n_rseg, 4096)), dim3(FB), 0, h->n_rseg, h->d_rseg.as<LongSeg>(),
-               h->d_Ar_col.as<int>(), h->d_Ar_src.as<int>(), h->d_Kval.as<double>(), vmap,
+               h->d_Ar_col.as<int>(), h->d_Ar_src.as<int>(), kin, vmap,
                masked ? h->d_dmask.as<int>() : nullptr, P.n_late > 0 ? 1 : 0, h->equilibrate ? 1 : 0,
                h->d_dscale.as<double>(), h->d_segpart.as<double>(), h->d_segcnt.as<unsigned int>());
-      LAUNCH(PC_GATHER, k_row_scale, dim3(nbz + nblocks((long long)P.m * 16)), dim3(FB), 0, P.m,
-             h->d_Ar_ptr.as<int>(), h->d_Ar_col.as<int>(), h->d_Ar_src.as<int>(), h->d_Kval.as<double>(), vmap,
+      LAUNCH(PC_GATHER, k_row_scale, dim3(row_scale_grid(P)), dim3(FB), 0, P.m,
+             h->d_Ar_ptr.as<int>(), h->d_Ar_col.as<int>(), h->d_Ar_src.as<int>(), kin, vmap,
              masked ? h->d_dmask.as<int>() : nullptr, h->d_perm.as<int>(), P.n_late > 0 ? P.my : -1,
              h->equilibrate ? 1 : 0, h->d_dscale.as<double>(),
              h->d_Ar_val.as<double>(), masked ? h->d_Ar_full.as<double>() : nullptr, h->d_Ksc.as<double>(), kprod,
-             nbz, reinterpret_cast<double2*>(h->d_L.p), nz16, h->d_info.as<int>(), h->n_rseg,
+             h->vals_ride ? h->d_Kval.as<double>() : nullptr, (long long)P.nnzK,
+             reinterpret_cast<double2*>(h->d_L.p), nz16, h->d_info.as<int>(), h->n_rseg,
              h->d_rseg.as<LongSeg>(), decide_in(h), h->decide_rides ? 1 : 0);
     }
   }
@@ -134,7 +158,7 @@ static int factor_enqueue(hipfact_handle* h) {
                          h->d_Mtarget.as<long long>(), h->d_Kval.as<double>(), h->d_L.as<double>());
     }
   }
-  if (P.saddle && (h->maps_on || P.n_late > 0) && P.m > 0)
+  if (diag_inactive_needed(h))
     LAUNCH(PC_GATHER, k_diag_inactive, dim3(nblocks(P.m)), dim3(FB), 0, P.m, h->d_perm.as<int>(), h->d_cmap.as<int>(),
            h->d_diag_target.as<long long>(), h->d_L.as<double>());
   if (P.saddle && h->reg_delta > 0.0 && P.m > 0)  // static pivoting behind a singular verdict (static_pivot_retry)
@@ -244,20 +268,26 @@ static int factor_async(hipfact_handle* h, const double* src = nullptr) {
     h->reg_delta = 0.0;
     h->num_perturbed = 0;
   }
+  // (with k_row_scale in the sequence the copy is that kernel's: it reads the caller's array and writes d_Kval)
+  const bool ride = src && src_bytes > 0 && row_scale_in_sequence(h);
+  const bool copy_first = src && src_bytes > 0 && !ride;
   if (!graphed) {
     flush_decide(h);
-    if (src && src_bytes > 0) HCHECK(h, hipMemcpyAsync(h->d_Kval.p, src, src_bytes, hipMemcpyDeviceToDevice, h->stream));
+    if (copy_first) HCHECK(h, hipMemcpyAsync(h->d_Kval.p, src, src_bytes, hipMemcpyDeviceToDevice, h->stream));
   }
   const bool with_decide = graphed && h->decide_deferred;  // (two variants of the graph: + 4 in its key)
+  const bool with_inactive = diag_inactive_needed(h);      // (k_diag_inactive comes and goes with the working set: + 16)
   auto enqueue_all = [&]() -> int {
     if (graphed) {
       // (a pending verdict rides in the first block of k_row_scale when that kernel is part of the sequence)
-      h->decide_rides = with_decide && P.saddle && P.n > 0 && P.m > 0;
+      h->decide_rides = with_decide && row_scale_in_sequence(h);
       if (with_decide && !h->decide_rides) hipLaunchKernelGGL(k_refine_decide, dim3(1), dim3(FB), 0, h->stream, decide_in(h), 1, 1);
-      if (src && src_bytes > 0) HCHECK(h, hipMemcpyAsync(h->d_Kval.p, src, src_bytes, hipMemcpyDeviceToDevice, h->stream));
+      if (copy_first) HCHECK(h, hipMemcpyAsync(h->d_Kval.p, src, src_bytes, hipMemcpyDeviceToDevice, h->stream));
     }
+    h->vals_ride = ride ? src : nullptr;
     const int frc = factor_enqueue(h);
     h->decide_rides = false;
+    h->vals_ride = nullptr;
     return frc;
   };
   // (the solves a factorisation may carry inside its own sequence - dense_cols.inc - belong to the NEW factor: the
@@ -265,10 +295,11 @@ static int factor_async(hipfact_handle* h, const double* src = nullptr) {
   h->tb_valid = false;
   if (h->factored) h->solves_prev_factor = h->solves_this_factor;
   h->solves_this_factor = 0;
-  // (variants of the captured sequence: with / without the delivery of a pending verdict, with the static-pivot shift)
-  h->note('F', (with_decide ? 4 : 0) + (h->reg_delta > 0.0 ? 8 : 0) + (graphed ? 0 : 16));
-  const int rc = run_cached(h, 0, graphed ? src : nullptr, nullptr, enqueue_all,
-                                        (with_decide ? 4 : 0) + (h->reg_delta > 0.0 ? 8 : 0));
+  // (variants of the captured sequence: with / without the delivery of a pending verdict, with the static-pivot shift,
+  // with / without k_diag_inactive)
+  const int variant = (with_decide ? 4 : 0) + (h->reg_delta > 0.0 ? 8 : 0) + (with_inactive ? 16 : 0);
+  h->note('F', variant + (graphed ? 0 : 32));
+  const int rc = run_cached(h, 0, graphed ? src : nullptr, nullptr, enqueue_all, variant);
   if (graphed && rc == HIPFACT_OK) h->decide_deferred = false;
   if (rc) return rc;
   h->num_factor++;

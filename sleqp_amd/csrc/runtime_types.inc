@@ -177,6 +177,7 @@ struct PlanState {
   int m_struct = 0;           // rows covered
   bool maps_on = false;       // d_vmap / d_cmap translate between the caller's numbering and the structure
   int N_ext = 0;              // dimension of the caller's vectors (n + |W|); == plan.N without maps
+  int n_inactive = 0;         // rows of the structure outside the current working set (cmap == -1): k_diag_inactive writes their unit pivots
   int n_bounds = 0;           // active bounds of the current working set
   unsigned long long use_stamp = 0;  // LRU clock
   int refine_inline = 1;      // correction passes currently carried by the solve graphs
@@ -320,6 +321,7 @@ struct hipfact_handle : PlanState {
   long solves_since_check = 0;
   bool decide_deferred = false;  // ... and such a verdict is outstanding
   bool decide_rides = false;     // (during factor_enqueue) it is delivered by the first block of k_row_scale
+  const double* vals_ride = nullptr;  // (during factor_enqueue) the caller's device values: k_row_scale reads them there and writes d_Kval
   bool ctl_pending = false;      // the control block of the last solve has not been looked at yet
   const double* last_b = nullptr;
   double* last_z = nullptr;
