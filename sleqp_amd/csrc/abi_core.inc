@@ -139,23 +139,27 @@ static bool dense_treatment_probe_fails(hipfact_handle* h, int rc) {
   return false;
 }
 
-int hipfact_set_matrix(hipfact_handle* h, int N, const int* colptr, const int* rowidx, const double* vals) {
-  RoctxRange range("hipfact_set_matrix");
-  int rc = set_matrix_impl(h, N, colptr, rowidx, vals);
-  if (h && (dense_treatment_suspect(h, rc) || dense_treatment_probe_fails(h, rc))) {
+// impl (an entry point that ends in a factorisation) with the two retries behind its verdict: once more without the
+// dense-column treatment where that is suspect (clear_dictionary: the row dictionary starts over too), then static pivoting
+static int with_dense_retry(hipfact_handle* h, bool clear_dictionary, const std::function<int()>& impl) {
+  int rc = impl();
+  if (!h) return rc;
+  if (dense_treatment_suspect(h, rc) || dense_treatment_probe_fails(h, rc)) {
     const int mode = h->prm.dense_mode;
     h->prm.dense_mode = 0;
     invalidate_plans(h);
-    h->vj->clear();
+    if (clear_dictionary) h->vj->clear();
     h->dense_fallbacks++;
-    rc = set_matrix_impl(h, N, colptr, rowidx, vals);
+    rc = impl();
     h->prm.dense_mode = mode;  // (the plan of this pattern stays as analysed just now; new patterns get the treatment again)
   }
-  if (h) {
-    h->warning.clear();
-    rc = static_pivot_retry(h, rc);  // a rank-deficient working set: like MA57, factor it and say so (hipfact_last_warning)
-  }
-  return rc;
+  h->warning.clear();
+  return static_pivot_retry(h, rc);  // a rank-deficient working set: like MA57, factor it and say so (hipfact_last_warning)
+}
+
+int hipfact_set_matrix(hipfact_handle* h, int N, const int* colptr, const int* rowidx, const double* vals) {
+  RoctxRange range("hipfact_set_matrix");
+  return with_dense_retry(h, true, [&] { return set_matrix_impl(h, N, colptr, rowidx, vals); });
 }
 
 const char* hipfact_last_warning(const hipfact_handle* h) { return (h && !h->warning.empty()) ? h->warning.c_str() : nullptr; }
@@ -182,7 +186,6 @@ static int set_matrix_impl(hipfact_handle* h, int N, const int* colptr, const in
   if (h->speculate && h->have_plan && !h->from_jacobian && h->plan.N == N && h->plan.nnzK == nnz_in &&
       (size_t)nnz_in * sizeof(double) >= (64u << 10)) {
     const int analyses = h->analyses, swaps = h->plan_swaps;
-    const bool could_fall_back = !h->no_dataflow;
     HCHECK(h, hipStreamSynchronize(h->stream));
     HCHECK(h, hipMemcpyAsync(h->d_Kval.p, vals, (size_t)nnz_in * sizeof(double), hipMemcpyHostToDevice, h->stream));
     // (the copy reads the caller's array: no return, error or not, while it may be in flight; and the queued work
@@ -199,7 +202,7 @@ static int set_matrix_impl(hipfact_handle* h, int N, const int* colptr, const in
       (void)hipStreamSynchronize(h->stream);
       return rc;
     }
-    if (h->analyses == analyses && h->plan_swaps == swaps) return check_factor(h, could_fall_back);
+    if (h->analyses == analyses && h->plan_swaps == swaps) return await_factor(h);
     HCHECK(h, hipStreamSynchronize(h->stream));  // another plan is active now: start over on it
   } else if ((rc = ensure_plan(h, N, colptr, rowidx, vals))) {
     return rc;
@@ -221,7 +224,8 @@ static int set_matrix_impl(hipfact_handle* h, int N, const int* colptr, const in
     }
     HCHECK(h, hipMemcpyAsync(h->d_Kval.p, src, bytes, hipMemcpyHostToDevice, h->stream));
   }
-  return factor_and_check(h);
+  rc = factor_async(h);
+  return rc ? rc : await_factor(h);
 }
 
 int hipfact_refactor_device(hipfact_handle* h, const double* d_vals) {
@@ -548,19 +552,13 @@ static int solution_range(hipfact_handle* h, double* out, const double** view, i
     dst = direct ? out : h->h_stage.as<double>();
   }
   HCHECK(h, hipMemcpyAsync(dst, h->d_sol.as<double>() + begin, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  const bool could_fall_back = !h->no_dataflow;
-  rc = check_info(h, "solve");  // synchronises
-  if (rc == HIPFACT_EINTERNAL && could_fall_back && h->no_dataflow && h->last_b && h->last_z) {
-    // the sweep timed out: the same solve once more through the per-level kernels - behind a fresh factorisation
-    // when the timed-out wait may have been the (unchecked) factorisation's own
-    if (!h->factored) {
-      if ((rc = factor_async(h))) return rc;
-      if ((rc = check_info(h))) return rc;
-    }
-    if ((rc = solve_async(h, h->last_b, h->last_z))) return rc;
-    if ((rc = finish_solve(h))) return rc;
+  bool switched = false;
+  rc = check_info(h, Phase::solve, &switched);  // synchronises
+  if (rc == HIPFACT_EINTERNAL && switched && h->last_b && h->last_z) {
+    // the sweep timed out: the same solve once more through the per-level kernels
+    if ((rc = repeat_on_per_level(h, true, h->last_b, h->last_z))) return rc;
     HCHECK(h, hipMemcpyAsync(dst, h->d_sol.as<double>() + begin, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    rc = check_info(h, "solve");
+    rc = check_info(h, Phase::solve);
   }
   if (rc) return rc;
   if (view)
@@ -587,28 +585,17 @@ int hipfact_check(hipfact_handle* h) {
   if (rc) return rc;
   if (!h->have_plan) return HIPFACT_OK;
   if ((rc = finish_solve(h))) return rc;
-  const bool could_fall_back = !h->no_dataflow, was_solve = h->solved;
-  const double* b = h->last_b;
-  double* z = h->last_z;
-  rc = check_info(h, was_solve ? "solve" : "factorisation");
-  if (rc == HIPFACT_EINTERNAL && could_fall_back && h->no_dataflow) {
+  const bool was_solve = h->solved && h->last_b && h->last_z;
+  bool switched = false;
+  rc = check_info(h, h->solved ? Phase::solve : Phase::factor, &switched);
+  if (rc == HIPFACT_EINTERNAL && switched) {
     // A dataflow launch whose waits ran out (seen when two PROCESSES share one GPU: workgroups are handed to the eight
     // XCDs in turn, and while another process saturates one XCD the launch's higher-indexed workgroups on the other
     // seven spin for blocks that are still queued there - both processes can hold each other's producers out until
     // the bounded spins give up).  The handle has switched to the per-level launches for good; what the caller has
-    // queued is repeated there - the factorisation from the values still on the device when its own verdict had not
-    // been seen, then the last solve into the caller's buffer - as hipfact_solution does for the host boundary.
-    if (!h->factored) {
-      if ((rc = factor_async(h))) return rc;
-      if ((rc = check_info(h))) return rc;
-    }
-    if (was_solve && b && z) {
-      if ((rc = solve_async(h, b, z))) return rc;
-      if ((rc = finish_solve(h))) return rc;
-      rc = check_info(h, "solve");
-    } else {
-      rc = HIPFACT_OK;
-    }
+    // queued is repeated there, the last solve into the caller's buffer - as hipfact_solution does for the host boundary.
+    if ((rc = repeat_on_per_level(h, was_solve, h->last_b, h->last_z))) return rc;
+    if (was_solve) rc = check_info(h, Phase::solve);
     if (rc == HIPFACT_OK) h->error.clear();
   }
   return rc;

@@ -370,7 +370,7 @@ static int steihaug_impl(hipfact_handle* h, const HessOp& op, const double* grad
   }
   HCHECK(h, hipGetLastError());
   HCHECK(h, hipMemcpyAsync(h->h_stage.p, z, nb, hipMemcpyDeviceToHost, st));
-  if ((rc = check_info(h, "solve"))) return rc;  // synchronises; a timed-out sweep invalidates the step
+  if ((rc = check_info(h, Phase::solve))) return rc;  // synchronises; a timed-out sweep invalidates the step
   memcpy(newton_step, h->h_stage.p, nb);
   if (iterations) *iterations = it;
   return HIPFACT_OK;
@@ -624,7 +624,7 @@ static int gltr_impl(hipfact_handle* h, const HessOp& op, const double* gradient
   HCHECK(h, hipGetLastError());
   HCHECK(h, hipStreamSynchronize(st));
   HCHECK(h, hipMemcpyAsync(h->h_stage.p, s, nb, hipMemcpyDeviceToHost, st));
-  if ((rc = check_info(h, "solve"))) return rc;  // synchronises
+  if ((rc = check_info(h, Phase::solve))) return rc;  // synchronises
   memcpy(newton_step, h->h_stage.p, nb);
   if (tr_dual) *tr_dual = lambda;
   if (iterations) *iterations = h->tr.timed_out ? dim : std::min(k, dim);

@@ -67,6 +67,17 @@ static int build_superset_plan(hipfact_handle* h, int n, int m_total, const int*
   return HIPFACT_OK;
 }
 
+// The values of the structure K_s from the Jacobian on the device, and the maps of this working set (rows the structure
+// covers and the working set leaves out: cmap = -1)
+static int struct_fill_async(hipfact_handle* h, int n, int jnnz) {
+  hipLaunchKernelGGL(k_struct_fill, dim3(nblocks(std::max({n, h->m_struct, jnnz}))), dim3(FB), 0, h->stream, n, h->m_struct,
+                     jnnz, h->d_ji.as<int>(), h->d_jx.as<double>(), h->d_jtarget.as<int>(), h->d_vi.as<int>(),
+                     h->d_ci.as<int>(), h->d_srow.as<int>(), h->d_Kp.as<int>(), h->d_Kval.as<double>(), h->d_vmap.as<int>(),
+                     h->d_cmap.as<int>());
+  HCHECK(h, hipGetLastError());
+  return HIPFACT_OK;
+}
+
 // ---------------------------------------------------------------------------
 // Superset path of the device assembly: finds (or analyses) a plan whose structure [I J_s^T; J_s 0] covers the working
 // set's constraint rows, then a numeric refactorisation.  The Jacobian (d_jp / d_ji / d_jx) and the working-set maps
@@ -75,7 +86,6 @@ static int superset_refactor(hipfact_handle* h, int n, int m_total, const int* j
                              const int* cons_index, int nav, int nac, int N, unsigned long long jhash, bool known) {
   int rc;
   const int jnnz = n > 0 ? j_colptr[n] : 0;
-  hipStream_t st = h->stream;
   // ---- superset path: find a plan whose structure covers the working set's constraint rows
   auto covers = [&](const PlanState& s) {
     if (!(&s == static_cast<const PlanState*>(h) && known) &&
@@ -138,17 +148,10 @@ static int superset_refactor(hipfact_handle* h, int n, int m_total, const int* j
   if (h->N_ext != N) drop_solve_graphs(h);
   h->N_ext = N;
   h->n_bounds = nav;
-  const Plan& P = h->plan;
-  hipLaunchKernelGGL(k_struct_fill, dim3(nblocks(std::max({n, h->m_struct, jnnz}))), dim3(FB), 0, st, n, h->m_struct, jnnz,
-                     h->d_ji.as<int>(), h->d_jx.as<double>(), h->d_jtarget.as<int>(), h->d_vi.as<int>(), h->d_ci.as<int>(),
-                     h->d_srow.as<int>(), h->d_Kp.as<int>(), h->d_Kval.as<double>(),
-                     h->d_vmap.as<int>(), h->d_cmap.as<int>());
-  HCHECK(h, hipGetLastError());
-  (void)P;
-  const bool could_fall_back = !h->no_dataflow;
+  if ((rc = struct_fill_async(h, n, jnnz))) return rc;
   if ((rc = factor_async(h))) return rc;
   cold_tick("factorisation queued");
-  rc = check_factor(h, could_fall_back);
+  rc = await_factor(h);
   cold_tick("factorisation awaited");
   return rc;
 }
@@ -162,22 +165,10 @@ static int assemble_kkt_impl(hipfact_handle* h, int n, int m_total, const int* j
 int hipfact_assemble_kkt(hipfact_handle* h, int n, int m_total, const int* j_colptr, const int* j_rowidx,
                          const double* j_vals, const int* var_index, const int* cons_index, int working_set_size,
                          int* k_nnz, int* k_colptr, int* k_rowidx, double* k_vals) {
-  int rc = assemble_kkt_impl(h, n, m_total, j_colptr, j_rowidx, j_vals, var_index, cons_index, working_set_size, k_nnz,
+  return with_dense_retry(h, false, [&] {
+    return assemble_kkt_impl(h, n, m_total, j_colptr, j_rowidx, j_vals, var_index, cons_index, working_set_size, k_nnz,
                              k_colptr, k_rowidx, k_vals);
-  if (h && (dense_treatment_suspect(h, rc) || dense_treatment_probe_fails(h, rc))) {  // (see hipfact_set_matrix)
-    const int mode = h->prm.dense_mode;
-    h->prm.dense_mode = 0;
-    invalidate_plans(h);
-    h->dense_fallbacks++;
-    rc = assemble_kkt_impl(h, n, m_total, j_colptr, j_rowidx, j_vals, var_index, cons_index, working_set_size, k_nnz,
-                           k_colptr, k_rowidx, k_vals);
-    h->prm.dense_mode = mode;
-  }
-  if (h) {
-    h->warning.clear();
-    rc = static_pivot_retry(h, rc);  // (see hipfact_set_matrix)
-  }
-  return rc;
+  });
 }
 
 static int assemble_kkt_impl(hipfact_handle* h, int n, int m_total, const int* j_colptr, const int* j_rowidx,
@@ -278,7 +269,8 @@ static int assemble_kkt_impl(hipfact_handle* h, int n, int m_total, const int* j
     h->N_ext = N;
     if (nnz > 0)
       HCHECK(h, hipMemcpyAsync(h->d_Kval.p, h->d_akx.p, (size_t)nnz * sizeof(double), hipMemcpyDeviceToDevice, st));
-    return factor_and_check(h);
+    rc = factor_async(h);
+    return rc ? rc : await_factor(h);
   }
   return superset_refactor(h, n, m_total, j_colptr, j_rowidx, cons_index, nav, nac, N, jhash, known);
 }

@@ -269,7 +269,7 @@ static int lsqr_impl(hipfact_handle* h, const hipfact_lsqr_op* op, const double*
     if (read_x) {
       HCHECK(h, h->h_stage.ensure((size_t)n * sizeof(double)));
       HCHECK(h, hipMemcpyAsync(h->h_stage.p, D.x, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-      if ((rc = check_info(h, "solve"))) return rc;  // synchronises; a timed-out sweep invalidates the step
+      if ((rc = check_info(h, Phase::solve))) return rc;  // synchronises; a timed-out sweep invalidates the step
       memcpy(step, h->h_stage.p, (size_t)n * sizeof(double));
     } else {
       memset(step, 0, (size_t)n * sizeof(double));

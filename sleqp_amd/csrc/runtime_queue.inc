@@ -85,6 +85,18 @@ static inline bool row_scale_in_sequence(const hipfact_handle* h) {
   const Plan& P = h->plan;
   return P.saddle && P.n > 0 && P.m > 0;
 }
+// The launch routes of a handle, each decided HERE only.  dataflow_factor: the top levels (and the pivot blocks of chain
+// levels) are single dataflow launches; tree_solve: the sweeps of a solve are the one tree launch (k_solve_tree), not the
+// per-level kernels; tree_delivers_verdict: ... and every solve has it (its extra workgroup delivers a deferred
+// refinement verdict); graph_route: sequences are replayed from captured graphs (run_cached)
+static inline bool dataflow_factor(const hipfact_handle* h) { return h->debug_phases == 15 && !h->no_dataflow; }
+static inline bool tree_solve(const hipfact_handle* h) { return h->fused_solve && !h->no_dataflow; }
+static inline bool tree_delivers_verdict(const hipfact_handle* h) { return tree_solve(h) && h->plan.m > 0 && h->plan.saddle; }
+static inline bool graph_route(const hipfact_handle* h) { return h->use_graph && !h->prof.on && h->debug_phases == 15; }
+// the map of constraint rows, where one is in force (rows outside the working set: -1, late variables: -2)
+static inline const int* cmap_or_null(const hipfact_handle* h) { return (h->maps_on || h->plan.n_late > 0) ? h->d_cmap.as<int>() : nullptr; }
+// rows of A carry entries the factorisation leaves out (dense columns, late variables): d_dmask, d_Ar_full
+static inline bool masked_rows(const hipfact_handle* h) { return h->nd > 0 || h->plan.n_late > 0; }
 // bytes k_row_scale clears: the dependency counters of k_factor_top live behind the arena, one fill clears both
 static inline size_t arena_fill_bytes(const Plan& P) {
   return (size_t)P.L_size * sizeof(double) + (size_t)4 * P.nsuper * sizeof(int);
@@ -96,6 +108,19 @@ static inline int row_scale_grid(const Plan& P) {
   const long long nz16 = (long long)((arena_fill_bytes(P) + 15) / 16);
   const int for_fill = (int)std::min<long long>(2048, std::max<long long>(1, nz16 / (FB * 8)));
   return std::max(nblocks((long long)P.m * 16), for_fill);
+}
+// the Schur items of a level whose pivot blocks and panels are done (CH: a chain level)
+template <bool CH>
+static void launch_schur(hipfact_handle* h, const LevelInfo& li, int pull) {
+  h->prof.next_fl = li.schur_flops;
+  if (li.nD <= 0) return;
+  const FrontItem* fit = h->d_fitems.as<FrontItem>() + li.itD;
+  if (li.pair == 2)
+    LAUNCH(PC_FACTOR_D, k_front_schur_pair, dim3(li.nD), dim3(FB), li.lds_schur, fit, h->d_L.as<double>(),
+           h->d_U.as<double>(), li.pd);
+  else
+    LAUNCH(PC_FACTOR_D, k_front_schur<CH>, dim3(li.nD), dim3(FB), li.lds_schur, fit, h->d_L.as<double>(),
+           h->d_U.as<double>(), h->d_inv.as<int>(), h->d_rel.as<int>(), h->d_pullx.as<PullDesc>(), pull);
 }
 static int factor_enqueue(hipfact_handle* h) {
   Turn turn(h);
@@ -119,7 +144,7 @@ static int factor_enqueue(hipfact_handle* h) {
     // copy of K's values for the Schur-complement products and the x update
     {
       const long long nz16 = (long long)((fill_bytes + 15) / 16);
-      const bool masked = h->nd > 0 || P.n_late > 0;
+      const bool masked = masked_rows(h);
       // (the caller's array, while its values are not in d_Kval yet: k_row_scale leaves the copy there)
       const double* kin = h->vals_ride ? h->vals_ride : h->d_Kval.as<double>();
       if (h->n_rseg > 0)  // the scales of the long rows first (segments, the last workgroup of a row decides)
@@ -162,11 +187,11 @@ static int factor_enqueue(hipfact_handle* h) {
     LAUNCH(PC_GATHER, k_diag_inactive, dim3(nblocks(P.m)), dim3(FB), 0, P.m, h->d_perm.as<int>(), h->d_cmap.as<int>(),
            h->d_diag_target.as<long long>(), h->d_L.as<double>());
   if (P.saddle && h->reg_delta > 0.0 && P.m > 0)  // static pivoting behind a singular verdict (static_pivot_retry)
-    LAUNCH(PC_GATHER, k_diag_shift, dim3(nblocks(P.m)), dim3(FB), 0, P.m, h->d_perm.as<int>(),
-           (h->maps_on || P.n_late > 0) ? h->d_cmap.as<int>() : nullptr, h->d_diag_target.as<long long>(), h->d_L.as<double>(),
-           h->reg_delta);
-  const int lsplit = (h->debug_phases == 15 && !h->no_dataflow) ? std::min(h->ftop_level, P.nlevels) : P.nlevels;
-  if (h->mini_x_bytes > 0 && h->debug_phases == 15 && !h->no_dataflow)
+    LAUNCH(PC_GATHER, k_diag_shift, dim3(nblocks(P.m)), dim3(FB), 0, P.m, h->d_perm.as<int>(), cmap_or_null(h),
+           h->d_diag_target.as<long long>(), h->d_L.as<double>(), h->reg_delta);
+  const bool dataflow = dataflow_factor(h);
+  const int lsplit = dataflow ? std::min(h->ftop_level, P.nlevels) : P.nlevels;
+  if (h->mini_x_bytes > 0 && dataflow)
     HCHECK(h, hipMemsetAsync(h->d_xarena.as<double>() + h->mini_x_off, 0xFF, h->mini_x_bytes, st));
   for (int l = 0; l < lsplit; ++l) {
     const LevelInfo& li = h->levels[l];
@@ -175,22 +200,15 @@ static int factor_enqueue(hipfact_handle* h) {
     if (li.nA > 0 && (h->debug_phases & 1) && !pull)
       LAUNCH(PC_FACTOR_A, k_front_assemble, dim3(li.nA), dim3(1024), li.lds_asm, h->d_sn.as<SnDesc>(), it + li.itA, li.nparts,
              h->d_L.as<double>(), h->d_U.as<double>(), h->d_rel.as<int>(), h->d_child.as<int>());
-    if (li.split && h->debug_phases == 15 && li.mini_cnt > 0 && !h->no_dataflow && h->ftop_count > 0) {
+    if (li.split && li.mini_cnt > 0 && dataflow && h->ftop_count > 0) {
       // dense chain: pivot block and panel of the level's one front in ONE small dataflow launch (the panel
       // workgroups follow the posted pivot block tile by tile), then its Schur items at three workgroups per CU
-      const FrontItem* fit = h->d_fitems.as<FrontItem>();
       int* flm = reinterpret_cast<int*>(h->d_L.as<double>() + P.L_size);
       LAUNCH(PC_FACTOR_B, k_factor_top, dim3(li.mini_cnt), dim3(512), li.mini_lds,
              h->d_tfitems.as<TopFItem>() + li.mini_off, h->d_L.as<double>(), h->d_U.as<double>(), h->d_info.as<int>(),
              h->d_inv.as<int>(), h->d_rel.as<int>(), flm, flm + P.nsuper, flm + 2 * P.nsuper, h->d_xarena.as<double>(),
              nullptr, nullptr, nullptr);
-      h->prof.next_fl = li.schur_flops;
-      if (li.nD > 0 && li.pair == 2)
-        LAUNCH(PC_FACTOR_D, k_front_schur_pair, dim3(li.nD), dim3(FB), li.lds_schur, fit + li.itD, h->d_L.as<double>(),
-               h->d_U.as<double>(), li.pd);
-      else if (li.nD > 0)
-        LAUNCH(PC_FACTOR_D, k_front_schur<false>, dim3(li.nD), dim3(FB), li.lds_schur, fit + li.itD, h->d_L.as<double>(),
-               h->d_U.as<double>(), h->d_inv.as<int>(), h->d_rel.as<int>(), h->d_pullx.as<PullDesc>(), pull);
+      launch_schur<false>(h, li, pull);
     } else if (li.split && h->debug_phases == 15) {
       const FrontItem* fit = h->d_fitems.as<FrontItem>();
 #define SPLIT_LAUNCHES(CH)                                                                                              \
@@ -201,13 +219,7 @@ static int factor_enqueue(hipfact_handle* h) {
     LAUNCH(PC_FACTOR_C, k_front_panel<CH>, dim3(li.nC), dim3(li.panel_threads), li.lds_panel, fit + li.itC,            \
            h->d_L.as<double>(), h->d_U.as<double>(), h->d_inv.as<int>(), h->d_rel.as<int>(),                          \
            h->d_pullx.as<PullDesc>(), pull);                                                                           \
-  h->prof.next_fl = li.schur_flops;                                                                                    \
-  if (li.nD > 0 && li.pair == 2)                                                                                       \
-    LAUNCH(PC_FACTOR_D, k_front_schur_pair, dim3(li.nD), dim3(FB), li.lds_schur, fit + li.itD, h->d_L.as<double>(),    \
-           h->d_U.as<double>(), li.pd);                                                                          \
-  else if (li.nD > 0)                                                                                                  \
-    LAUNCH(PC_FACTOR_D, k_front_schur<CH>, dim3(li.nD), dim3(FB), li.lds_schur, fit + li.itD, h->d_L.as<double>(),     \
-           h->d_U.as<double>(), h->d_inv.as<int>(), h->d_rel.as<int>(), h->d_pullx.as<PullDesc>(), pull);
+  launch_schur<CH>(h, li, pull);
       if (li.chain) {
         SPLIT_LAUNCHES(true)
       } else {
@@ -228,7 +240,7 @@ static int factor_enqueue(hipfact_handle* h) {
            h->sp_folded ? h->d_sitems.as<SolveItem>() : nullptr, h->sp_folded ? h->d_SPf.as<double>() : nullptr,
            h->sp_folded ? h->d_SPb.as<double>() : nullptr);
   }
-  if (h->fused_solve && !h->no_dataflow && !(h->sp_folded && lsplit < P.nlevels) && h->n_sitems > 0)
+  if (tree_solve(h) && !(h->sp_folded && lsplit < P.nlevels) && h->n_sitems > 0)
     LAUNCH(PC_SPANEL, k_build_solve_panels, dim3(h->n_sitems), dim3(SPB), h->sp_lds, h->d_sitems.as<SolveItem>(),
            h->d_L.as<double>(), h->d_SPf.as<double>(), h->d_SPb.as<double>());
   HCHECK(h, hipGetLastError());
@@ -262,7 +274,7 @@ static int factor_async(hipfact_handle* h, const double* src = nullptr) {
     h->cache.clear();
     if (const int rrc = reset_dataflow_state(h)) return rrc;
   }
-  const bool graphed = h->use_graph && !h->prof.on && h->debug_phases == 15;
+  const bool graphed = graph_route(h);
   const size_t src_bytes = (size_t)P.nnzK * sizeof(double);
   if (!h->reg_retry) {  // a new factorisation starts unperturbed (the shift belongs to the retry behind a singular verdict)
     h->reg_delta = 0.0;
@@ -356,15 +368,55 @@ static int reset_dataflow_state(hipfact_handle* h) {
   return HIPFACT_OK;
 }
 
+// HIPFACT_TRACE_TIMEOUT: what a timed-out wait left behind, on stderr (msg: the error the caller gets)
+static void trace_timeout(hipfact_handle* h, const char* msg) {
+  static const bool on = getenv("HIPFACT_TRACE_TIMEOUT") != nullptr;
+  if (!on) return;
+  const Plan& P = h->plan;
+  // which fronts of the single-launch factorisation never posted their pivot block (bdone == 0), level by level
+  std::vector<int> fl((size_t)4 * P.nsuper);
+  if (h->d_L.p && hipMemcpy(fl.data(), h->d_L.as<double>() + P.L_size, fl.size() * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess)
+    for (int l = 0; l < P.nlevels; ++l) {
+      int open = 0, nb = 0, nc = 0, nd = 0;
+      for (int q = P.level_ptr[l]; q < P.level_ptr[l + 1]; ++q) {
+        const int sn = P.level_sn[q];
+        open += fl[sn] == 0;
+        nb += fl[sn];
+        nc += fl[P.nsuper + sn];
+        nd += fl[2 * P.nsuper + sn];
+      }
+      fprintf(stderr, "   level %2d fronts %4d  without pivot flag %4d  sums bdone %d cdone %d ddone %d\n", l,
+              P.level_ptr[l + 1] - P.level_ptr[l], open, nb, nc, nd);
+    }
+  fprintf(stderr, "[hipfact %p] %s; factorisation %ld, solve %ld, turn waits %lld, handles on the device %d\n", (void*)h, msg,
+          (long)h->num_factor, (long)h->solve_seq, h->turn_waits, g_turn[h->device & 15].live.load());
+  fprintf(stderr, "   first solve workgroup that timed out: %d (items %d, top block %d: %d below)\n",
+          h->info_host[INFO_TIMEOUT_WG] ? (1 << 30) - h->info_host[INFO_TIMEOUT_WG] : -1, h->n_sitems, (int)h->tb_valid, h->tb_nfb);
+  for (hipfact_handle* o : g_trace_handles)
+    if (o && o != h) {
+      fprintf(stderr, "   other handle %p: factorisations %ld, analyses %ld, turn waits %lld, launches %u, last:", (void*)o,
+              (long)o->num_factor, (long)o->analyses, o->turn_waits, o->n_notes);
+      for (unsigned k = o->n_notes > 6 ? o->n_notes - 6 : 0; k < o->n_notes; ++k) fprintf(stderr, " %c%d", o->notes[k & 63].kind, o->notes[k & 63].key);
+      fprintf(stderr, "\n");
+    }
+  fprintf(stderr, "   last launches:");
+  for (unsigned k = h->n_notes > 64 ? h->n_notes - 64 : 0; k < h->n_notes; ++k)
+    fprintf(stderr, " %c%d", h->notes[k & 63].kind, h->notes[k & 63].key);
+  fprintf(stderr, "\n");
+}
+
 // Reads back the info words of the last factorisation (blocking).  Zero / non-finite pivots, a
 // negative pivot of the Schur complement A A^T (saddle mode: it is SPD unless the working set is
 // rank deficient) and dependency-wait timeouts all invalidate the factorisation.
-static int check_info(hipfact_handle* h, const char* phase = "factorisation") {
+// switched: a timeout found here has moved the handle to the per-level launches (await_factor, repeat_on_per_level)
+enum class Phase { factor, solve };
+static int check_info(hipfact_handle* h, Phase phase = Phase::factor, bool* switched = nullptr) {
+  if (switched) *switched = false;
   // (the info words and, behind them, the smallest / largest positive pivot: one transfer)
   HCHECK(h, hipMemcpyAsync(h->h_info.p, h->d_info.p, INFO_BYTES, hipMemcpyDeviceToHost, h->stream));
   HCHECK(h, hipStreamSynchronize(h->stream));
   memcpy(h->info_host, h->h_info.p, INFO_WORDS * sizeof(int));
-  if (!strcmp(phase, "factorisation")) {
+  if (phase == Phase::factor) {
     unsigned long long mm[2];
     memcpy(mm, h->h_info.as<char>() + INFO_WORDS * sizeof(int), sizeof(mm));
     const unsigned long long nlo = ~mm[0];
@@ -384,49 +436,14 @@ static int check_info(hipfact_handle* h, const char* phase = "factorisation") {
   }
   char buf[200];
   if (h->info_host[INFO_TIMEOUT] != 0) {
-    snprintf(buf, sizeof buf, "dependency wait timed out inside the single-launch %s kernels (%d waits)", phase,
-             h->info_host[INFO_TIMEOUT]);
-    const bool in_solve = !strcmp(phase, "solve") && factor_was_checked;
+    snprintf(buf, sizeof buf, "dependency wait timed out inside the single-launch %s kernels (%d waits)",
+             phase == Phase::solve ? "solve" : "factorisation", h->info_host[INFO_TIMEOUT]);
+    const bool in_solve = phase == Phase::solve && factor_was_checked;
     if (!in_solve) h->factored = false;  // (a solve does not touch the factor)
     h->solved = false;
-    if (getenv("HIPFACT_TRACE_TIMEOUT") && h->d_L.p) {
-      // which fronts of the single-launch factorisation never posted their pivot block (bdone == 0), level by level
-      const Plan& P = h->plan;
-      std::vector<int> fl((size_t)4 * P.nsuper);
-      if (hipMemcpy(fl.data(), h->d_L.as<double>() + P.L_size, fl.size() * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess)
-        for (int l = 0; l < P.nlevels; ++l) {
-          int open = 0, nb = 0, nc = 0, nd = 0;
-          for (int q = P.level_ptr[l]; q < P.level_ptr[l + 1]; ++q) {
-            const int sn = P.level_sn[q];
-            open += fl[sn] == 0;
-            nb += fl[sn];
-            nc += fl[P.nsuper + sn];
-            nd += fl[2 * P.nsuper + sn];
-          }
-          fprintf(stderr, "   level %2d fronts %4d  without pivot flag %4d  sums bdone %d cdone %d ddone %d\n", l,
-                  P.level_ptr[l + 1] - P.level_ptr[l], open, nb, nc, nd);
-        }
-    }
     const int rc = reset_dataflow_state(h);
     h->error = buf;
-    if (getenv("HIPFACT_TRACE_TIMEOUT"))
-      fprintf(stderr, "[hipfact %p] %s; factorisation %d, solve %ld, turn waits %lld, handles on the device %d\n", (void*)h, buf,
-              h->num_factor, (long)h->solve_seq, h->turn_waits, g_turn[h->device & 15].live.load());
-    if (getenv("HIPFACT_TRACE_TIMEOUT")) {
-      fprintf(stderr, "   first solve workgroup that timed out: %d (items %d, top block %d: %d below)\n",
-              h->info_host[INFO_TIMEOUT_WG] ? (1 << 30) - h->info_host[INFO_TIMEOUT_WG] : -1, h->n_sitems, (int)h->tb_valid, h->tb_nfb);
-      for (hipfact_handle* o : g_trace_handles)
-        if (o && o != h) {
-          fprintf(stderr, "   other handle %p: factorisations %d, analyses %d, turn waits %lld, launches %u, last:", (void*)o, o->num_factor,
-                  o->analyses, o->turn_waits, o->n_notes);
-          for (unsigned k = o->n_notes > 6 ? o->n_notes - 6 : 0; k < o->n_notes; ++k) fprintf(stderr, " %c%d", o->notes[k & 63].kind, o->notes[k & 63].key);
-          fprintf(stderr, "\n");
-        }
-      fprintf(stderr, "   last launches:");
-      for (unsigned k = h->n_notes > 64 ? h->n_notes - 64 : 0; k < h->n_notes; ++k)
-        fprintf(stderr, " %c%d", h->notes[k & 63].kind, h->notes[k & 63].key);
-      fprintf(stderr, "\n");
-    }
+    trace_timeout(h, buf);
     if (!h->no_dataflow) {
       // from now on: per-level launches only (captured graphs hold the dataflow launches: drop them all)
       h->no_dataflow = true;
@@ -434,8 +451,8 @@ static int check_info(hipfact_handle* h, const char* phase = "factorisation") {
       h->df_retry_at = h->df_retry_every > 0
                            ? h->num_factor + ((long)h->df_retry_every << std::min<long>(h->dataflow_fallbacks - 1, 8))
                            : -1;
-      h->graphs.clear();
-      for (auto& st2 : h->cache) st2->graphs.clear();
+      drop_graphs(h);
+      if (switched) *switched = true;
     }
     return rc ? rc : HIPFACT_EINTERNAL;
   }
@@ -459,7 +476,7 @@ static int check_info(hipfact_handle* h, const char* phase = "factorisation") {
 static inline SaddleMaps saddle_maps(const hipfact_handle* h) {
   SaddleMaps M;
   M.vmap = h->maps_on ? h->d_vmap.as<int>() : nullptr;
-  M.cmap = (h->maps_on || h->plan.n_late > 0) ? h->d_cmap.as<int>() : nullptr;  // (late variables: -2 in their slots)
+  M.cmap = cmap_or_null(h);
   M.dscale = h->d_dscale.as<double>();
   M.n = h->plan.n;
   M.nrseg = h->n_rseg;
@@ -475,7 +492,7 @@ static inline SaddleMaps saddle_maps(const hipfact_handle* h) {
 // every launch into a no-op (correction passes of a solve that has already converged)
 static void solve_m_async(hipfact_handle* h, const int* skip, const RhsIn* rhs = nullptr, const XupdIn* xup = nullptr) {
   const Plan& P = h->plan;
-  if (h->fused_solve && !h->no_dataflow) {
+  if (tree_solve(h)) {
     // (one workgroup more than items: it delivers the deferred verdict of the previous solve, if any; behind it the
     // workgroups of the x update, when it rides in this launch)
     XupdIn X;
@@ -508,7 +525,7 @@ static void solve_m_async(hipfact_handle* h, const int* skip, const RhsIn* rhs =
            h->d_SPb.as<double>(), h->d_sxuoff.as<long long>(), h->d_sxinvoff.as<int>(),
            h->d_inv.as<int>(), h->d_rows.as<int>(), h->d_y.as<double>(),
            h->d_xhat.as<double>(), h->d_uvec.as<double>(), h->d_ysol.as<double>(), P.m, h->d_epoch.as<int>(),
-           h->d_info.as<int>(), skip, rhs ? *rhs : RhsIn{nullptr, nullptr, nullptr, nullptr, SaddleMaps{nullptr, nullptr, nullptr, 0}, nullptr},
+           h->d_info.as<int>(), skip, rhs ? *rhs : RhsIn{},
            decide_in(h), h->d_spart.as<double>(), X);
     return;
   }
@@ -539,6 +556,23 @@ static void solve_m_async(hipfact_handle* h, const int* skip, const RhsIn* rhs =
   }
 }
 
+// y = the right-hand side of M y = t in pivot order, from b in the caller's numbering (saddle mode)
+static void launch_rhs_saddle(hipfact_handle* h, const SaddleMaps& M, const double* b, const int* skip) {
+  const Plan& P = h->plan;
+  LAUNCH(PC_RHS, k_rhs_saddle, dim3(nblocks((long long)P.m * 16)), dim3(FB), 0, P.m, h->d_Ar_ptr.as<int>(),
+         h->d_Ar_col.as<int>(), h->d_Ar_val.as<double>(), h->d_perm.as<int>(), M, b, h->d_y.as<double>(), skip);
+}
+// z = (acc: z +) the solution in the caller's numbering, from y and the leaf columns of K (saddle mode)
+static void launch_x_saddle(hipfact_handle* h, const SaddleMaps& M, const double* b, double* z, bool acc, const int* skip,
+                            int* epoch) {
+  const Plan& P = h->plan;
+  auto go = [&](auto ACC) {
+    LAUNCH(PC_XUPD, k_x_saddle<decltype(ACC)::value>, dim3(nblocks((long long)P.n * 8)), dim3(FB), 0, P.n, P.m, h->d_Kp.as<int>(),
+           h->d_Ksc.as<double>(), h->d_Kc_y.as<int>(), h->d_perm.as<int>(), M, h->d_y.as<double>(), b, z, skip, epoch);
+  };
+  acc ? go(std::true_type()) : go(std::false_type());
+}
+
 // z = K^-1 b (acc: z += K^-1 b) without refinement; b, z device vectors in the caller's
 // numbering, b != z
 static void solve_once_async(hipfact_handle* h, const double* b, double* z, bool acc, const int* skip, bool raw = false) {
@@ -556,23 +590,23 @@ static void solve_once_async(hipfact_handle* h, const double* b, double* z, bool
     dense_correct_async(h, z, acc, skip);
     return;
   }
+  const bool tree = tree_solve(h);
   // fused solve launch: the kernel behind it advances the epoch of its double-buffered exchange slots
-  int* epoch = (h->fused_solve && !h->no_dataflow && P.m > 0) ? h->d_epoch.as<int>() : nullptr;
+  int* epoch = (tree && P.m > 0) ? h->d_epoch.as<int>() : nullptr;
   if (P.saddle) {
     const SaddleMaps M = saddle_maps(h);
+    // The shape of the launches: the forward items of the tree launch form their own rows of the right-hand side,
+    // unless A has long rows (dense constraint rows are formed by whole workgroups of k_rhs_saddle, not by the 16 lanes
+    // a forward item gives a row); and its last workgroups do the back substitution of the leaf columns - the whole
+    // solve is then ONE launch (two with long rows).  Otherwise: right-hand side, sweeps, x update.
+    const bool rhs_in_tree = tree && h->rhs_fused && h->n_lrows == 0;
+    const bool whole = tree && h->rhs_fused && h->xupd_fused && P.n > 0 && P.m > 0;
     if (P.m > 0) {
-      // (long rows of A - dense constraint rows - are formed by whole workgroups of k_rhs_saddle, not by the 16 lanes
-      // a forward item of the tree launch gives a row)
-      const bool rhs_in_tree = h->rhs_fused && h->n_lrows == 0;
-      if (h->fused_solve && !h->no_dataflow && (rhs_in_tree || h->n_lrows > 0) && h->rhs_fused && h->xupd_fused && P.n > 0) {
-        // ... and its last workgroups the back substitution of the leaf columns: the whole solve is ONE launch
-        // (two with long rows: their right-hand side comes from k_rhs_saddle in front)
-        if (!rhs_in_tree)
-          LAUNCH(PC_RHS, k_rhs_saddle, dim3(nblocks((long long)P.m * 16)), dim3(FB), 0, P.m, h->d_Ar_ptr.as<int>(),
-                 h->d_Ar_col.as<int>(), h->d_Ar_val.as<double>(), h->d_perm.as<int>(), M, b, h->d_y.as<double>(), skip);
-        const RhsIn R{rhs_in_tree ? h->d_Ar_ptr.as<int>() : nullptr, h->d_Ar_col.as<int>(), h->d_Ar_val.as<double>(), h->d_perm.as<int>(), M, b};
-        XupdIn X;
-        memset(&X, 0, sizeof(X));
+      if (!rhs_in_tree) launch_rhs_saddle(h, M, b, skip);
+      const RhsIn R{rhs_in_tree ? h->d_Ar_ptr.as<int>() : nullptr, h->d_Ar_col.as<int>(), h->d_Ar_val.as<double>(), h->d_perm.as<int>(), M, b};
+      XupdIn X;
+      memset(&X, 0, sizeof(X));
+      if (whole) {
         X.n = P.n;
         X.Kp = h->d_Kp.as<int>();
         X.Ksc = h->d_Ksc.as<double>();
@@ -587,25 +621,10 @@ static void solve_once_async(hipfact_handle* h, const double* b, double* z, bool
           X.dot_out = h->x_dot_out;
           h->x_dot_blocks = X.nblocks;
         }
-        solve_m_async(h, skip, &R, &X);
-        return;
       }
-      if (h->fused_solve && !h->no_dataflow && rhs_in_tree) {
-        // the forward items of the single launch form their own rows of the right-hand side
-        const RhsIn R{h->d_Ar_ptr.as<int>(), h->d_Ar_col.as<int>(), h->d_Ar_val.as<double>(), h->d_perm.as<int>(), M, b};
-        solve_m_async(h, skip, &R);
-      } else {
-        LAUNCH(PC_RHS, k_rhs_saddle, dim3(nblocks((long long)P.m * 16)), dim3(FB), 0, P.m, h->d_Ar_ptr.as<int>(),
-               h->d_Ar_col.as<int>(), h->d_Ar_val.as<double>(), h->d_perm.as<int>(), M, b, h->d_y.as<double>(), skip);
-        solve_m_async(h, skip);
-      }
+      solve_m_async(h, skip, (rhs_in_tree || whole) ? &R : nullptr, whole ? &X : nullptr);
     }
-    if (acc)
-      LAUNCH(PC_XUPD, k_x_saddle<true>, dim3(nblocks((long long)P.n * 8)), dim3(FB), 0, P.n, P.m, h->d_Kp.as<int>(),
-             h->d_Ksc.as<double>(), h->d_Kc_y.as<int>(), h->d_perm.as<int>(), M, h->d_y.as<double>(), b, z, skip, epoch);
-    else
-      LAUNCH(PC_XUPD, k_x_saddle<false>, dim3(nblocks((long long)P.n * 8)), dim3(FB), 0, P.n, P.m, h->d_Kp.as<int>(),
-             h->d_Ksc.as<double>(), h->d_Kc_y.as<int>(), h->d_perm.as<int>(), M, h->d_y.as<double>(), b, z, skip, epoch);
+    if (!whole) launch_x_saddle(h, M, b, z, acc, skip, epoch);
   } else {
     LAUNCH(PC_PERM, k_gather_skip, dim3(nblocks(P.m)), dim3(FB), 0, (long long)P.m, h->d_perm.as<int>(), b,
            h->d_y.as<double>(), skip);
@@ -641,7 +660,7 @@ static void residual_async(hipfact_handle* h, const double* b, const double* z, 
   if (P.saddle) {
     LAUNCH(PC_RESID, k_residual_saddle, dim3(resid_blocks(P)), dim3(FB), 0, P.n, P.m, h->d_Kp.as<int>(),
            h->d_Ki.as<int>(), h->d_Kval.as<double>(), h->d_Ar_ptr.as<int>(), h->d_Ar_col.as<int>(),
-           ((h->nd > 0 || P.n_late > 0) ? h->d_Ar_full : h->d_Ar_val).as<double>(), h->d_perm.as<int>(), saddle_maps(h), b, z, res, ctl,
+           (masked_rows(h) ? h->d_Ar_full : h->d_Ar_val).as<double>(), h->d_perm.as<int>(), saddle_maps(h), b, z, res, ctl,
            h->d_norms.as<double>(),
            first ? 1 : 0, dflag);
   } else {
@@ -700,7 +719,7 @@ static int run_cached(hipfact_handle* h, int kind, const void* b, void* z, F enq
     HCHECK(h, hipGraphLaunch(exec, h->stream));
     return HIPFACT_OK;
   };
-  if (!h->use_graph || h->prof.on || h->debug_phases != 15) return direct();
+  if (!graph_route(h)) return direct();
   for (auto& g : h->graphs)
     if (g.kind == kind && g.b == b && g.z == z && g.passes == passes) return launch(g.exec);
   // (the turn is held from here to the launch: no other handle may queue a wait for this stream's event while the
@@ -750,8 +769,7 @@ static int correct_enqueue(hipfact_handle* h, const double* bb, double* z, int p
 // A solve without correction passes in its graph leaves its verdict to the tree launch of the NEXT solve (a
 // workgroup of that launch instead of a one-block launch and its kernel boundary behind every solve).
 static bool defers_decide(const hipfact_handle* h) {
-  return h->decide_lazy && h->refine_steps > 0 && h->refine_adaptive && h->refine_inline == 0 && h->fused_solve &&
-         !h->no_dataflow && h->plan.m > 0 && h->plan.saddle;
+  return h->decide_lazy && h->refine_steps > 0 && h->refine_adaptive && h->refine_inline == 0 && tree_delivers_verdict(h);
 }
 
 // first pass z = K^-1 b, residual, and the in-graph correction passes
@@ -826,7 +844,7 @@ static int top_block_touch(hipfact_handle* h) {
   const int after = (h->solves_prev_factor >= h->top_block_breakeven) ? h->top_block_after
                                                                        : std::max(h->top_block_after, h->top_block_breakeven);
   if (!h->tb_valid && h->tb_nT > 0 && h->top_block_after > 0 && h->solves_this_factor >= after &&
-      h->fused_solve && !h->no_dataflow && !h->prof.on && h->debug_phases == 15)
+      tree_solve(h) && !h->prof.on && h->debug_phases == 15)
     return top_block_build(h);
   return HIPFACT_OK;
 }
@@ -868,7 +886,7 @@ static int solve_async(hipfact_handle* h, const double* b, double* z) {
     h->check_interval_now = std::min(std::max(h->refine_check_max, h->refine_check_every), h->check_interval_now * h->refine_check_backoff);
   h->solves_since_check = unchecked ? h->solves_since_check + 1 : 1;
   h->num_checked += (!unchecked && h->refine_steps > 0);
-  if (!(h->fused_solve && !h->no_dataflow && h->plan.m > 0 && h->plan.saddle)) flush_decide(h);  // no tree launch to deliver it
+  if (!tree_delivers_verdict(h)) flush_decide(h);  // no tree launch to deliver it
   h->skip_resid_now = unchecked;
   h->last_solve_checked = !unchecked;
   // (an unchecked steady-state solve is two launches: queued directly - replaying a two-node graph measures 4-5 us
@@ -1082,23 +1100,28 @@ static int ensure_plan(hipfact_handle* h, int N, const int* colptr, const int* r
   return HIPFACT_OK;
 }
 
-// factorisation + verdict; a timed-out dataflow launch is repeated once on the per-level path (fresh launches,
-// same process)
-static int check_factor(hipfact_handle* h, bool could_fall_back);
-static int factor_and_check(hipfact_handle* h) {
-  const bool could_fall_back = !h->no_dataflow;
-  int rc = factor_async(h);
-  if (rc) return rc;
-  return check_factor(h, could_fall_back);
-}
-// the verdict on a queued factorisation (synchronises); a timed-out dataflow launch is repeated on the per-level path
-static int check_factor(hipfact_handle* h, bool could_fall_back) {
-  int rc = check_info(h);
-  if (rc == HIPFACT_EINTERNAL && could_fall_back && h->no_dataflow && h->info_host[INFO_TIMEOUT] != 0) {
+// The verdict on a queued factorisation (synchronises).  retry: a launch whose timeout moved the handle to the per-level
+// kernels is repeated there once (fresh launches, same process), like every first timeout.
+static int await_factor(hipfact_handle* h, bool retry = true) {
+  bool switched = false;
+  int rc = check_info(h, Phase::factor, &switched);
+  if (rc == HIPFACT_EINTERNAL && switched && retry) {
     if ((rc = factor_async(h))) return rc;
     rc = check_info(h);
   }
   return rc;
+}
+// Behind a timeout that moved the handle to the per-level kernels, what the caller had queued once more: the factorisation
+// from the values still on the device when its own verdict had not been seen, then the solve (its verdict: the caller's)
+static int repeat_on_per_level(hipfact_handle* h, bool was_solve, const double* b, double* z) {
+  int rc;
+  if (!h->factored) {
+    if ((rc = factor_async(h))) return rc;
+    if ((rc = check_info(h))) return rc;
+  }
+  if (!was_solve) return HIPFACT_OK;
+  if ((rc = solve_async(h, b, z))) return rc;
+  return finish_solve(h);
 }
 
 // MA57 factors a rank-deficient K and says so with a positive status that the reference lets pass (fact_ma57.c:41-42,
@@ -1130,7 +1153,7 @@ static int static_pivot_retry(hipfact_handle* h, int rc) {
   h->reg_delta = h->static_delta;
   h->reg_retry = true;
   int r2 = factor_async(h);
-  if (!r2) r2 = check_info(h);
+  if (!r2) r2 = await_factor(h, false);  // (a timeout here is reported, not repeated)
   h->reg_retry = false;
   if (r2 != HIPFACT_OK) {
     h->reg_delta = 0.0;

@@ -246,11 +246,7 @@ static int virtual_numeric_async(hipfact_handle* h) {
   if (jnnz > 0)
     hipLaunchKernelGGL(k_virtual_values, dim3(nblocks(jnnz)), dim3(FB), 0, st, jnnz, h->d_vsrc.as<int>(),
                        h->d_kin.as<double>(), h->d_jx.as<double>());
-  hipLaunchKernelGGL(k_struct_fill, dim3(nblocks(std::max({n, h->m_struct, jnnz}))), dim3(FB), 0, st, n, h->m_struct, jnnz,
-                     h->d_ji.as<int>(), h->d_jx.as<double>(), h->d_jtarget.as<int>(), h->d_vi.as<int>(), h->d_ci.as<int>(),
-                     h->d_srow.as<int>(), h->d_Kp.as<int>(), h->d_Kval.as<double>(),
-                     h->d_vmap.as<int>(), h->d_cmap.as<int>());
-  HCHECK(h, hipGetLastError());
+  if (const int rc = struct_fill_async(h, n, jnnz)) return rc;
   return factor_async(h);
 }
 // (hipfact_refactor_device: is the active plan the one of the last K that came through the dictionary?)
@@ -299,7 +295,6 @@ static int set_matrix_virtual(hipfact_handle* h, int N, const int* kp, const int
   };
   auto queue_numeric = [&]() -> int { return virtual_numeric_async(h); };
   if (maybe_same) {
-    const bool could_fall_back = !h->no_dataflow;
     if ((rc = queue_numeric())) return sync_fail(rc);
     bool same = memcmp(V.lastKp.data(), kp, (size_t)(N + 1) * sizeof(int)) == 0 &&
                 memcmp(V.lastKi.data(), ki, (size_t)nnzK * sizeof(int)) == 0;
@@ -309,7 +304,7 @@ static int set_matrix_virtual(hipfact_handle* h, int N, const int* kp, const int
       h->use_stamp = ++h->use_clock;
       h->cache_hits++;
       *handled = true;
-      return check_factor(h, could_fall_back);
+      return await_factor(h);
     }
     HCHECK(h, hipStreamSynchronize(st));  // what was queued ran on the old maps: discarded
   }
