@@ -140,6 +140,48 @@ int hipfact_solve_device(hipfact_handle* h, const double* d_rhs, double* d_sol);
 /* Device pointer to the last solution (N doubles, owned by the handle). */
 int hipfact_solution_device(hipfact_handle* h, const double** d_sol);
 
+/* K Z = B for `nrhs` right-hand sides, the factor read once per block of up to 16 columns (both sweeps of a block
+ * run on the fp64 matrix cores with the 16 right-hand sides as the 16-wide operand).  Column j of B is at
+ * d_rhs + j*ld_rhs, column j of Z at d_sol + j*ld_sol (device, caller's numbering, N doubles each; ld_* >= N).
+ * d_sol may be d_rhs with ld_sol == ld_rhs (in place); any other overlap is HIPFACT_EINVAL.  The bytes between N and
+ * ld of every column, and B itself when the solve is not in place, are not written.
+ * `omega`: host out, nrhs doubles, may be NULL - the backward error of every column as "last_omega" defines it (NaN
+ * with refine_steps = 0, where no residual is formed).
+ * The call BLOCKS.  On entry it does what hipfact_check does (the pending refinement of an earlier single solve is
+ * finished, HIPFACT_ESINGULAR / HIPFACT_ENOMEM / HIPFACT_EDEVICE are reported); it does not become "the last solve":
+ * hipfact_solution, hipfact_solution_view and hipfact_solution_device still return the earlier single solve, and a
+ * single solve issued afterwards gives the bits it would have given without this call.  nrhs == 0 returns
+ * HIPFACT_OK; HIPFACT_EINVAL for nrhs < 0, ld < N, NULL arrays or a partial overlap; HIPFACT_ESTATE before a
+ * factorisation.  The workspace is allocated by the first call of a plan; when that fails
+ * the call returns HIPFACT_ENOMEM and the handle stays usable for single solves.
+ * Numerics: the single solve's target (backward-error tolerance refine_tol / condition estimate clamped to
+ * [4.5e-16, 1e-12], at most refine_max correction passes, fail_omega).  refine_steps = 0: a plain blocked solve.
+ * Otherwise the residual of EVERY column is formed against the caller's K on every call; correction passes run while
+ * a column of the block is above its tolerance, and a column that has converged is frozen.  The bits of a column's
+ * solution depend on that column, K and the options only - not on its position, on nrhs or on what the other columns
+ * hold.  A column with a NaN or an Inf comes back non-finite and is NOT an error (HIPFACT_OK, as the single solve
+ * answers such a right-hand side); its neighbours are solved as if it were not there.  A column that stalls above
+ * fail_omega, or lies outside the range of a statically pivoted rank-deficient K, makes the call return
+ * HIPFACT_ESINGULAR; info "multi_failed_col" names the first such column (-1: none) and d_sol is then unspecified.
+ * A plan with the low-rank dense-column correction (dense_mode = 2 and dense columns present) solves its columns one
+ * by one through the single-solve path inside this call (info "multi_single_cols" counts them), same contract:
+ * every column is a checked solve (no refine_check_every skipping), and the single path's last solve, check cadence
+ * and counters are put back afterwards.  Unlike the single solve, the blocked path does not re-analyse a superset
+ * plan of the vtable when a column stagnates above 16 x its tolerance: that column returns with omega[j] above the
+ * tolerance (HIPFACT_OK below fail_omega) - read omega on such plans.
+ * Info: "multi_solves" calls, "multi_cols" columns, "multi_blocks" blocks of up to 16 columns, "multi_passes" passes
+ * over the factor (a block's first solve and each of its correction passes count one).
+ * From which nrhs the call pays (measured on the MI355X, EXPERIMENTS.md, "Blocked solve"): a block costs the same
+ * whatever it holds, so use full blocks; on the headline workload (banded, 150 000 unknowns) the break-even against
+ * back-to-back hipfact_solve_device calls is nrhs = 16 (0.88 x their time per column for one full block, 0.90 / 0.91 x
+ * at nrhs = 32 / 64: the margin is about 10 % and shrinks a little over several blocks).  On plans whose top is a chain
+ * of tall fronts (thousands of rows) there is NO break-even yet (1.85 x): issue single solves there. */
+int hipfact_solve_device_multi(hipfact_handle* h, int nrhs, const double* d_rhs, long long ld_rhs,
+                               double* d_sol, long long ld_sol, double* omega);
+
+/* The same for host arrays, both N x nrhs column-major with leading dimension N (sol may be rhs). */
+int hipfact_solve_multi(hipfact_handle* h, int nrhs, const double* rhs, double* sol);
+
 /* Blocks until the queued work has finished and reports what the asynchronous
  * entry points above could not: a singular / rank-deficient factorisation
  * (HIPFACT_ESINGULAR), a solve whose iterative refinement stalled far above its

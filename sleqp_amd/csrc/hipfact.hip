@@ -12,6 +12,7 @@
 //   runtime_queue.inc   factor / solve queues, graphs, cache     abi_krylov.inc       products, Steihaug CG, GLTR
 //   vtable_superset.inc row dictionary (plain vtable)            abi_options.inc      options, info, debug copies
 //   dense_cols.inc      dense Jacobian columns                   krylov_device.inc    device-controlled CG
+//   runtime_multi.inc   blocked solve, 16 right-hand sides       abi_multi.inc        hipfact_solve[_device]_multi
 #include <hip/hip_runtime.h>
 
 #include <dlfcn.h>
@@ -45,9 +46,11 @@
 #include "runtime_types.inc"
 #include "runtime_plan.inc"
 #include "runtime_queue.inc"
+#include "runtime_multi.inc"
 
 extern "C" {
 #include "abi_core.inc"
+#include "abi_multi.inc"
 #include "abi_working_set.inc"
 #include "abi_krylov.inc"
 #include "abi_options.inc"

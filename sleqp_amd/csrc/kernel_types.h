@@ -22,6 +22,9 @@ constexpr int ZS = 512;  // ... pivots per segment of a tile's sum (k_top_syrk_m
 constexpr int CG_BLOCKS = 2048;  // most blocks (= partial sums) of the product kernel: one pass over the rows per block when they suffice
 constexpr int CG_CHUNK = 8;  // iterations per graph launch (= per look of the host at the control block)
 
+constexpr int MR = 16;    // right-hand sides per block of the blocked solve: the 16-wide operand dimension of the fp64 MFMA
+constexpr int MB = 1024;  // most threads of a workgroup of its sweeps (levels of small fronts run with 256)
+
 // ---- refinement control block (described with the residual kernels below)
 struct RefineCtl {
   int done;     // 1: stop (converged, stagnated or non-finite)
@@ -43,6 +46,18 @@ struct DecideIn {
   int nblk;
   double target;
   const unsigned long long* minmax;
+};
+// what a level launch of the blocked sweeps needs (kernels_solve_multi.inc); level_sn points at the level's fronts
+struct MultiIn {
+  const SnDesc* __restrict__ sn;
+  const int* __restrict__ level_sn;
+  const double* __restrict__ L;
+  const int* __restrict__ inv;        // inverse relative indices of every front as a child (SnDesc::pad1)
+  const int* __restrict__ child_idx;
+  const int* __restrict__ rows;
+  double* __restrict__ Y;             // m x MR, column-major, leading dimension ldy
+  long long ldy;
+  double* __restrict__ U;             // update blocks, MR doubles per update row
 };
 // (working-set maps and equilibration of the saddle-point front end: described with the saddle kernels below)
 struct SaddleMaps {

@@ -25,6 +25,7 @@
 //   kernels_solve_level.inc   level-scheduled / one-launch-per-direction solves (fallback)
 //   kernels_factor_top.inc    k_factor_top: the upper levels of the factorisation as one dataflow launch
 //   kernels_solve_wide.inc    wide fronts of the fallback solves
+//   kernels_solve_multi.inc   blocked level-scheduled sweeps: 16 right-hand sides per pass over the factor panels
 //   kernels_solve_tree.inc    k_solve_tree (the whole solve in one launch), solve panels
 //   kernels_saddle.inc        row scaling, right-hand side, x update, residual, refinement verdict
 //   kernels_vector.inc        CSR row product / lane sum / block partial sums shared by the product and Krylov kernels,
@@ -40,6 +41,7 @@ namespace hipfact {
 #include "kernels_common.inc"
 #include "kernels_solve_level.inc"
 #include "kernels_solve_wide.inc"
+#include "kernels_solve_multi.inc"
 #include "kernels_solve_tree.inc"
 #include "kernels_saddle.inc"
 #include "kernels_vector.inc"

@@ -1,0 +1,267 @@
+// runtime_multi.inc - the blocked solve: up to MR = 16 right-hand sides per pass over the factor panels
+// (part of the single translation unit hipfact.hip; included from there, in this order)
+//
+// K Z = B for nrhs columns in blocks of MR.  A pass over a block is: the right-hand side of M Y = T column by column
+// (the single-vector front end writes into a column of the m x MR block), ONE forward and ONE backward sweep over the
+// panels of d_L for all MR columns (kernels_solve_multi.inc: a launch per level and direction, no waits between
+// workgroups), the back end and the residual against the caller's K column by column, each column with a control
+// block of its own.  The host looks at the MR verdicts once per pass; columns that have met the tolerance are frozen
+// (nothing of theirs is launched again), correction passes run while any column of the block is still open.  Every
+// column goes through the same launches with the same arguments wherever it sits and whatever its neighbours hold: its
+// bits depend on the column, K and the options alone.
+// The path has a workspace of its own (the block Y, the update blocks, residuals, a copy of B for the in-place case,
+// control blocks): it touches neither d_y nor d_uvec nor the epoch, the exchange slots, the flags or the top block of
+// the single solve, and it does not become "the last solve".
+
+// workspace of the active plan state, MR columns; the handle stays usable for single solves when this fails
+static int multi_workspace(hipfact_handle* h) {
+  const Plan& P = h->plan;
+  const size_t N = (size_t)h->N_ext;
+  auto need = [](size_t doubles) { return std::max<size_t>(doubles * sizeof(double), 16); };
+  hipError_t e = h->d_mY.ensure(need((size_t)MR * P.m));
+  if (e == hipSuccess) e = h->d_mU.ensure(need((size_t)MR * (size_t)P.u_size));
+  if (e == hipSuccess) e = h->d_mR.ensure(need((size_t)MR * N));
+  if (e == hipSuccess) e = h->d_mB.ensure(need((size_t)MR * N));
+  if (e == hipSuccess) e = h->d_mctl.ensure(MR * sizeof(RefineCtl));
+  if (e == hipSuccess) e = h->d_mnorms.ensure((size_t)MR * 3 * g_resid_cap * sizeof(double));
+  if (e == hipSuccess && !h->h_mctl.p) {
+    e = h->h_mctl.ensure(MR * sizeof(RefineCtl));
+    if (e == hipSuccess) e = hipHostGetDevicePointer(&h->h_mctl_dev, h->h_mctl.p, 0);
+  }
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    h->d_mY.release();
+    h->d_mU.release();
+    h->d_mR.release();
+    h->d_mB.release();
+    h->error = std::string("hipfact_solve_device_multi: workspace: ") + hipGetErrorString(e);
+    return e == hipErrorOutOfMemory ? HIPFACT_ENOMEM : HIPFACT_EDEVICE;
+  }
+  return HIPFACT_OK;
+}
+
+static inline DecideIn multi_decide_in(hipfact_handle* h, int j) {
+  return DecideIn{h->d_mctl.as<RefineCtl>() + j, static_cast<RefineCtl*>(h->h_mctl_dev) + j,
+                  h->d_mnorms.as<double>() + (size_t)j * 3 * g_resid_cap, resid_blocks(h->plan),
+                  h->refine_adaptive ? h->refine_tol : -1.0, minmax_ptr(h)};
+}
+
+// both sweeps over the factor for the block in d_mY
+static void multi_sweeps(hipfact_handle* h) {
+  const Plan& P = h->plan;
+  MultiIn A;
+  A.sn = h->d_sn.as<SnDesc>();
+  A.L = h->d_L.as<double>();
+  A.inv = h->d_inv.as<int>();
+  A.child_idx = h->d_child.as<int>();
+  A.rows = h->d_rows.as<int>();
+  A.Y = h->d_mY.as<double>();
+  A.ldy = P.m;
+  A.U = h->d_mU.as<double>();
+  // levels whose fronts have at most 256 rows run with four waves per front, the others with sixteen
+  auto threads = [&](const LevelInfo& li) {
+    int rmax = 0;
+    for (int q = li.begin; q < li.begin + li.count; ++q) rmax = std::max(rmax, P.sn_r[P.level_sn[q]]);
+    return rmax <= 256 ? 256 : MB;
+  };
+  for (int l = 0; l < P.nlevels; ++l) {
+    const LevelInfo& li = h->levels[l];
+    A.level_sn = h->d_level_sn.as<int>() + li.begin;
+    LAUNCH(PC_FWD, k_fwd_level_multi, dim3(li.count), dim3(threads(li)), 0, A);
+  }
+  for (int l = P.nlevels - 1; l >= 0; --l) {
+    const LevelInfo& li = h->levels[l];
+    A.level_sn = h->d_level_sn.as<int>() + li.begin;
+    LAUNCH(PC_BWD, k_bwd_level_multi, dim3(li.count), dim3(threads(li)), 0, A);
+  }
+}
+
+// One pass over a block: z_j = (acc: z_j +) K^-1 b_j for the columns `cols`, then their residuals and verdicts.
+// b[j] / z[j] / the residual of column j: vectors in the caller's numbering.
+static int multi_pass(hipfact_handle* h, const std::vector<int>& cols, const double* const* rhs, double* const* z,
+                      const double* const* b, bool acc, bool residual) {
+  Turn turn(h);
+  const Plan& P = h->plan;
+  const size_t N = (size_t)h->N_ext;
+  double* Y = h->d_mY.as<double>();
+  const SaddleMaps M = P.saddle ? saddle_maps(h) : SaddleMaps{};
+  if (P.m > 0) {
+    // columns that are not part of this pass (padding, frozen columns) are swept as zeros: one fill of the block, the
+    // right-hand-side kernels then write every entry of the live columns
+    if ((int)cols.size() < MR) HCHECK(h, hipMemsetAsync(Y, 0, (size_t)MR * P.m * sizeof(double), h->stream));
+    for (int j : cols) {
+      if (P.saddle)
+        launch_rhs_saddle(h, M, rhs[j], nullptr, Y + (size_t)j * P.m);
+      else
+        LAUNCH(PC_PERM, k_gather_skip, dim3(nblocks(P.m)), dim3(FB), 0, (long long)P.m, h->d_perm.as<int>(), rhs[j],
+               Y + (size_t)j * P.m, (const int*)nullptr);
+    }
+    multi_sweeps(h);
+  }
+  for (int j : cols) {
+    double* yj = Y + (size_t)j * P.m;
+    if (P.saddle)
+      launch_x_saddle(h, M, rhs[j], z[j], acc, nullptr, nullptr, yj);
+    else if (acc)
+      LAUNCH(PC_PERM, k_scatter_acc, dim3(nblocks(P.m)), dim3(FB), 0, (long long)P.m, h->d_perm.as<int>(), yj, z[j],
+             (const int*)nullptr, (int*)nullptr);
+    else
+      LAUNCH(PC_PERM, k_scatter, dim3(nblocks(P.m)), dim3(FB), 0, (long long)P.m, h->d_perm.as<int>(), yj, z[j], (int*)nullptr);
+  }
+  if (residual)
+    for (int j : cols) {
+      const DecideIn D = multi_decide_in(h, j);
+      residual_async(h, b[j], z[j], h->d_mR.as<double>() + (size_t)j * N, !acc, false, &D);
+    }
+  HCHECK(h, hipGetLastError());
+  h->multi_passes++;
+  return HIPFACT_OK;
+}
+
+// a block of nb <= MR columns; first: index of its first column in the call (for multi_failed_col and the messages)
+static int multi_block(hipfact_handle* h, int nb, int first, const double* d_rhs, long long ld_rhs, double* d_sol,
+                       long long ld_sol, bool in_place, double* omega) {
+  const size_t N = (size_t)h->N_ext;
+  const double* b[MR];
+  const double* rhs[MR];
+  double* z[MR];
+  if (in_place)  // a private copy of B: the residual needs it, and the back end reads b while it writes z
+    HCHECK(h, hipMemcpy2DAsync(h->d_mB.p, N * sizeof(double), d_rhs, (size_t)ld_rhs * sizeof(double), N * sizeof(double),
+                               (size_t)nb, hipMemcpyDeviceToDevice, h->stream));
+  for (int j = 0; j < nb; ++j) {
+    b[j] = in_place ? h->d_mB.as<double>() + (size_t)j * N : d_rhs + (size_t)j * ld_rhs;
+    rhs[j] = b[j];
+    z[j] = d_sol + (size_t)j * ld_sol;
+  }
+  const bool refine = h->refine_steps > 0;
+  const RefineCtl* hc = h->h_mctl.as<RefineCtl>();
+  for (int attempt = 0;; ++attempt) {
+    for (int j = 0; j < nb; ++j) rhs[j] = b[j];
+    std::vector<int> open(nb);
+    for (int j = 0; j < nb; ++j) open[j] = j;
+    int rc = multi_pass(h, open, rhs, z, b, false, refine);
+    if (rc) return rc;
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    if (attempt == 0) h->multi_blocks++;
+    if (!refine) {
+      if (omega)
+        for (int j = 0; j < nb; ++j) omega[j] = NAN;
+      return HIPFACT_OK;
+    }
+    for (int j = 0; j < nb; ++j) rhs[j] = h->d_mR.as<double>() + (size_t)j * N;  // correction passes solve for the residual
+    for (;;) {
+      // (adaptive: while a column is above its tolerance, has not stalled and has passes left; otherwise refine_steps
+      // unconditional passes, as the single solve's graph carries them)
+      std::vector<int> next;
+      const int cap = h->refine_adaptive ? h->refine_max : h->refine_steps;
+      for (int j : open)
+        if (!hc[j].done && hc[j].iters < cap) next.push_back(j);
+      if (next.empty()) break;
+      open.swap(next);
+      if ((rc = multi_pass(h, open, rhs, z, b, true, true))) return rc;
+      HCHECK(h, hipStreamSynchronize(h->stream));
+    }
+    bool stalled = false;
+    for (int j = 0; j < nb; ++j) {
+      const RefineCtl& c = hc[j];
+      if (omega) omega[j] = c.omega;
+      if (!h->refine_adaptive || c.status == 2 || h->multi_failed_col >= 0) continue;  // (a non-finite column is the caller's)
+      char buf[260];
+      if (c.omega > h->fail_omega) {
+        stalled = true;
+        snprintf(buf, sizeof buf, "working set is numerically singular: iterative refinement of column %d stalled at backward "
+                 "error %.2e after %d passes (pivot-ratio condition estimate %.2e)", first + j, c.omega, c.iters, c.kappa);
+      } else if (h->reg_delta > 0.0 && c.rnorm > h->fail_omega * c.bnorm) {
+        snprintf(buf, sizeof buf, "working set is rank deficient and column %d of the right-hand sides is not in the range of K: "
+                 "residual %.2e of its norm after %d passes on the statically pivoted factor", first + j, c.rnorm / c.bnorm, c.iters);
+      } else {
+        continue;
+      }
+      h->error = buf;
+      h->multi_failed_col = first + j;
+    }
+    if (h->multi_failed_col < 0) return HIPFACT_OK;
+    // dependent rows that rounding kept from an exact zero pivot show as a refinement that stalls (finish_solve):
+    // static pivoting as behind a zero pivot, then the block once more on the shifted factor
+    if (attempt == 0 && stalled && static_pivot_applies(h) && !h->no_solve_retry && h->pivot_ratio > 1e14 &&
+        static_pivot_retry(h, HIPFACT_ESINGULAR) == HIPFACT_OK) {
+      h->multi_failed_col = -1;
+      continue;
+    }
+    return HIPFACT_ESINGULAR;
+  }
+}
+
+// columns of a plan state with the low-rank dense-column correction (dense_mode 2): one by one through the single
+// solve.  Every column is a CHECKED solve (residual, verdict, correction passes: the refine_check_every cadence of the
+// single path is switched off for the call), and what the single path remembers between solves is put back afterwards:
+// "the last solve", the check cadence, the solve count that forms the top block, the inline-pass hint and the
+// counters.  The columns do use d_y, the epoch and the exchange slots, as every single solve does after another.
+static int multi_single_cols(hipfact_handle* h, int nrhs, const double* d_rhs, long long ld_rhs, double* d_sol,
+                             long long ld_sol, bool in_place, double* omega) {
+  const size_t N = (size_t)h->N_ext;
+  const double* const keep_b = h->last_b;
+  double* const keep_z = h->last_z;
+  const bool keep_solved = h->solved, keep_pre = h->sol_prefetched, keep_checked = h->last_solve_checked;
+  const RefineCtl keep_ctl = h->last_ctl;
+  const int keep_every = h->refine_check_every, keep_interval = h->check_interval_now, keep_since = h->solves_since_check;
+  const auto keep_this_factor = h->solves_this_factor;
+  const int keep_inline = h->refine_inline;
+  const bool keep_hint = h->wc_hint, keep_probe = h->inline_probe;
+  const auto keep_num_solve = h->num_solve, keep_num_passes = h->num_passes, keep_num_refined = h->num_refined,
+             keep_num_checked = h->num_checked;
+  h->refine_check_every = 1;
+  h->check_interval_now = 1;
+  int rc = HIPFACT_OK;
+  for (int j = 0; j < nrhs && rc == HIPFACT_OK; ++j) {
+    const double* bj = d_rhs + (size_t)j * ld_rhs;
+    if (in_place) {
+      if (hipMemcpyAsync(h->d_mB.p, bj, N * sizeof(double), hipMemcpyDeviceToDevice, h->stream) != hipSuccess) rc = HIPFACT_EDEVICE;
+      bj = h->d_mB.as<double>();
+    }
+    h->solves_this_factor = keep_this_factor - 1;  // (solve_async counts it back up: the top block is not formed earlier than without this call)
+    if (rc == HIPFACT_OK) rc = solve_async(h, bj, d_sol + (size_t)j * ld_sol);
+    if (rc == HIPFACT_OK) rc = finish_solve(h);
+    if (rc == HIPFACT_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = HIPFACT_EDEVICE;
+    if (omega) omega[j] = h->refine_steps > 0 ? h->last_ctl.omega : NAN;
+    if (rc == HIPFACT_ESINGULAR) h->multi_failed_col = j;
+    h->multi_single_cols++;
+  }
+  h->last_b = keep_b;
+  h->last_z = keep_z;
+  h->solved = keep_solved;
+  h->sol_prefetched = keep_pre;
+  h->last_solve_checked = keep_checked;
+  h->last_ctl = keep_ctl;
+  h->refine_check_every = keep_every;
+  h->check_interval_now = keep_interval;
+  h->solves_since_check = keep_since;
+  h->solves_this_factor = keep_this_factor;
+  if (!keep_probe) {  // (a factorisation whose first solve has not been judged yet keeps what these columns found)
+    h->refine_inline = keep_inline;
+    h->wc_hint = keep_hint;
+  }
+  h->num_solve = keep_num_solve;
+  h->num_passes = keep_num_passes;
+  h->num_refined = keep_num_refined;
+  h->num_checked = keep_num_checked;
+  return rc;
+}
+
+static int solve_multi_device(hipfact_handle* h, int nrhs, const double* d_rhs, long long ld_rhs, double* d_sol,
+                              long long ld_sol, double* omega) {
+  const bool in_place = d_sol == d_rhs;
+  int rc = multi_workspace(h);
+  if (rc) return rc;
+  h->multi_failed_col = -1;
+  h->multi_solves++;
+  h->multi_cols += nrhs;
+  if (h->nd > 0) return multi_single_cols(h, nrhs, d_rhs, ld_rhs, d_sol, ld_sol, in_place, omega);
+  for (int c0 = 0; c0 < nrhs; c0 += MR) {
+    const int nb = std::min(MR, nrhs - c0);
+    rc = multi_block(h, nb, c0, d_rhs + (size_t)c0 * ld_rhs, ld_rhs, d_sol + (size_t)c0 * ld_sol, ld_sol, in_place,
+                     omega ? omega + c0 : nullptr);
+    if (rc) return rc;
+  }
+  return HIPFACT_OK;
+}

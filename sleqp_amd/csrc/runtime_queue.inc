@@ -557,18 +557,19 @@ static void solve_m_async(hipfact_handle* h, const int* skip, const RhsIn* rhs =
 }
 
 // y = the right-hand side of M y = t in pivot order, from b in the caller's numbering (saddle mode)
-static void launch_rhs_saddle(hipfact_handle* h, const SaddleMaps& M, const double* b, const int* skip) {
+// (y null: the handle's own vector d_y; the blocked solve hands in a column of its block, runtime_multi.inc)
+static void launch_rhs_saddle(hipfact_handle* h, const SaddleMaps& M, const double* b, const int* skip, double* y = nullptr) {
   const Plan& P = h->plan;
   LAUNCH(PC_RHS, k_rhs_saddle, dim3(nblocks((long long)P.m * 16)), dim3(FB), 0, P.m, h->d_Ar_ptr.as<int>(),
-         h->d_Ar_col.as<int>(), h->d_Ar_val.as<double>(), h->d_perm.as<int>(), M, b, h->d_y.as<double>(), skip);
+         h->d_Ar_col.as<int>(), h->d_Ar_val.as<double>(), h->d_perm.as<int>(), M, b, y ? y : h->d_y.as<double>(), skip);
 }
 // z = (acc: z +) the solution in the caller's numbering, from y and the leaf columns of K (saddle mode)
 static void launch_x_saddle(hipfact_handle* h, const SaddleMaps& M, const double* b, double* z, bool acc, const int* skip,
-                            int* epoch) {
+                            int* epoch, const double* y = nullptr) {
   const Plan& P = h->plan;
   auto go = [&](auto ACC) {
     LAUNCH(PC_XUPD, k_x_saddle<decltype(ACC)::value>, dim3(nblocks((long long)P.n * 8)), dim3(FB), 0, P.n, P.m, h->d_Kp.as<int>(),
-           h->d_Ksc.as<double>(), h->d_Kc_y.as<int>(), h->d_perm.as<int>(), M, h->d_y.as<double>(), b, z, skip, epoch);
+           h->d_Ksc.as<double>(), h->d_Kc_y.as<int>(), h->d_perm.as<int>(), M, y ? y : h->d_y.as<double>(), b, z, skip, epoch);
   };
   acc ? go(std::true_type()) : go(std::false_type());
 }
@@ -651,24 +652,27 @@ static DecideIn decide_in(hipfact_handle* h) {
 }
 
 // res = b - K z; updates the refinement control block (first: the residual of the first pass).  defer: no verdict
-// launch behind it - the next tree launch (or flush_decide) delivers it.
+// launch behind it - the next tree launch (or flush_decide) delivers it.  own: the control block, its pinned copy and
+// the partial maxima of ONE column of the blocked solve (runtime_multi.inc) instead of the handle's
 static void residual_async(hipfact_handle* h, const double* b, const double* z, double* res, bool first,
-                           bool defer = false) {
+                           bool defer = false, const DecideIn* own = nullptr) {
   const Plan& P = h->plan;
-  RefineCtl* ctl = h->d_ctl.as<RefineCtl>();
+  const DecideIn D = own ? *own : decide_in(h);
+  RefineCtl* ctl = D.ctl;
+  double* norms = const_cast<double*>(D.partials);
   int* dflag = defer ? &ctl->pending : nullptr;
   if (P.saddle) {
     LAUNCH(PC_RESID, k_residual_saddle, dim3(resid_blocks(P)), dim3(FB), 0, P.n, P.m, h->d_Kp.as<int>(),
            h->d_Ki.as<int>(), h->d_Kval.as<double>(), h->d_Ar_ptr.as<int>(), h->d_Ar_col.as<int>(),
            (masked_rows(h) ? h->d_Ar_full : h->d_Ar_val).as<double>(), h->d_perm.as<int>(), saddle_maps(h), b, z, res, ctl,
-           h->d_norms.as<double>(),
+           norms,
            first ? 1 : 0, dflag);
   } else {
     LAUNCH(PC_RESID, k_residual_sym, dim3(resid_blocks(P)), dim3(FB), 0, P.N, h->d_Kp.as<int>(), h->d_Ki.as<int>(),
            h->d_Kval.as<double>(), h->d_Tp.as<int>(), h->d_Ti.as<int>(), h->d_Tsrc.as<int>(), b, z, res, ctl,
-           h->d_norms.as<double>(), first ? 1 : 0, dflag);
+           norms, first ? 1 : 0, dflag);
   }
-  if (!defer) LAUNCH(PC_RESID, k_refine_decide, dim3(1), dim3(FB), 0, decide_in(h), first ? 1 : 0, 0);
+  if (!defer) LAUNCH(PC_RESID, k_refine_decide, dim3(1), dim3(FB), 0, D, first ? 1 : 0, 0);
 }
 
 // the verdict of a solve whose graph left it to the next tree launch, for whoever needs it before that

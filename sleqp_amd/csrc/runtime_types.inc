@@ -229,6 +229,9 @@ struct PlanState {
   DevBuf d_rseg, d_cseg, d_lprod, d_segpart, d_segcnt;
   int n_rseg = 0, n_cseg = 0, n_lprod = 0;
   int n_lrows = 0;     // long rows (their right-hand side is formed by k_rhs_saddle, not inside the tree launch)
+  // blocked solve (runtime_multi.inc), MR columns each: the block Y of M Y = T, the update blocks, the residuals, a
+  // copy of B for the in-place case; allocated by the first multi solve of the state
+  DevBuf d_mY, d_mU, d_mR, d_mB;
 
   PlanState() = default;
   PlanState(PlanState&&) = default;
@@ -440,6 +443,13 @@ struct hipfact_handle : PlanState {
   DevBuf d_lsqr;                     // Gauss-Newton LSQR (krylov_lsqr.inc): right-hand sides, vectors, partials
   PinBuf h_lsqr;                     // ... what the host reads at its synchronisation, the right-hand side's staging
   long lsqr_runs = 0, lsqr_iters = 0;
+  // blocked solve (runtime_multi.inc): a control block and the partial maxima per column, the pinned copy the host
+  // reads once per pass, the staging of the host entry point; counters of hipfact_get_info
+  DevBuf d_mctl, d_mnorms, d_mhost;
+  PinBuf h_mctl;
+  void* h_mctl_dev = nullptr;
+  long multi_solves = 0, multi_cols = 0, multi_blocks = 0, multi_passes = 0, multi_single_cols = 0;
+  int multi_failed_col = -1;
 };
 
 struct hipfact_spmat {

@@ -103,6 +103,23 @@ class HipFact:
     def solve_device(self, d_rhs_ptr: int, d_sol_ptr: int):
         self._check(self._lib.hipfact_solve_device(self._h, C.c_void_p(d_rhs_ptr), C.c_void_p(d_sol_ptr)))
 
+    def solve_device_multi(self, d_rhs_ptr: int, ld_rhs: int, d_sol_ptr: int, ld_sol: int, nrhs: int) -> np.ndarray:
+        """hipfact_solve_device_multi: K Z = B for nrhs device columns (column j at ptr + 8 j ld), the factor read
+        once per block of 16 columns; blocks.  Returns the backward error of every column."""
+        omega = np.empty(max(int(nrhs), 0), dtype=np.float64)
+        self._check(self._lib.hipfact_solve_device_multi(self._h, int(nrhs), C.c_void_p(d_rhs_ptr), int(ld_rhs),
+                                                         C.c_void_p(d_sol_ptr), int(ld_sol), _ptr(omega)))
+        return omega
+
+    def solve_multi(self, B) -> np.ndarray:
+        """hipfact_solve_multi: Z with K Z = B for a host N x k array in either memory order."""
+        B = np.asarray(B, dtype=np.float64)
+        assert B.ndim == 2 and B.shape[0] == self.N, B.shape
+        rhs = np.asfortranarray(B)
+        sol = np.empty_like(rhs, order="F")
+        self._check(self._lib.hipfact_solve_multi(self._h, rhs.shape[1], _ptr(rhs), _ptr(sol)))
+        return sol
+
     def synchronize(self):
         self._check(self._lib.hipfact_synchronize(self._h))
 
