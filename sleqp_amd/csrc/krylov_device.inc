@@ -408,10 +408,7 @@ static int last_unchecked_solve_ok(hipfact_handle* h, const double* b, bool* ok)
   memcpy(&rcx, h->h_ctl.p, sizeof(rcx));
   h->solve_seq++;  // (the device counted a first residual)
   *ok = rcx.done && rcx.status == 0;
-  if (!*ok) {
-    h->wc_hint = false;
-    h->refine_inline = std::max(h->refine_inline, std::min(h->refine_steps, 1));
-  }
+  if (!*ok) judge_conditioning(h, false);
   return HIPFACT_OK;
 }
 

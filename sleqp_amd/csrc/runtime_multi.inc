@@ -40,12 +40,6 @@ static int multi_workspace(hipfact_handle* h) {
   return HIPFACT_OK;
 }
 
-static inline DecideIn multi_decide_in(hipfact_handle* h, int j) {
-  return DecideIn{h->d_mctl.as<RefineCtl>() + j, static_cast<RefineCtl*>(h->h_mctl_dev) + j,
-                  h->d_mnorms.as<double>() + (size_t)j * 3 * g_resid_cap, resid_blocks(h->plan),
-                  h->refine_adaptive ? h->refine_tol : -1.0, minmax_ptr(h)};
-}
-
 // both sweeps over the factor for the block in d_mY
 static void multi_sweeps(hipfact_handle* h) {
   const Plan& P = h->plan;
@@ -93,8 +87,7 @@ static int multi_pass(hipfact_handle* h, const std::vector<int>& cols, const dou
       if (P.saddle)
         launch_rhs_saddle(h, M, rhs[j], nullptr, Y + (size_t)j * P.m);
       else
-        LAUNCH(PC_PERM, k_gather_skip, dim3(nblocks(P.m)), dim3(FB), 0, (long long)P.m, h->d_perm.as<int>(), rhs[j],
-               Y + (size_t)j * P.m, (const int*)nullptr);
+        launch_rhs_perm(h, rhs[j], nullptr, Y + (size_t)j * P.m);
     }
     multi_sweeps(h);
   }
@@ -102,17 +95,11 @@ static int multi_pass(hipfact_handle* h, const std::vector<int>& cols, const dou
     double* yj = Y + (size_t)j * P.m;
     if (P.saddle)
       launch_x_saddle(h, M, rhs[j], z[j], acc, nullptr, nullptr, yj);
-    else if (acc)
-      LAUNCH(PC_PERM, k_scatter_acc, dim3(nblocks(P.m)), dim3(FB), 0, (long long)P.m, h->d_perm.as<int>(), yj, z[j],
-             (const int*)nullptr, (int*)nullptr);
-    else
-      LAUNCH(PC_PERM, k_scatter, dim3(nblocks(P.m)), dim3(FB), 0, (long long)P.m, h->d_perm.as<int>(), yj, z[j], (int*)nullptr);
+    else  // (no skip flag, no epoch: the block has neither)
+      launch_x_perm(h, z[j], acc, nullptr, nullptr, yj);
   }
   if (residual)
-    for (int j : cols) {
-      const DecideIn D = multi_decide_in(h, j);
-      residual_async(h, b[j], z[j], h->d_mR.as<double>() + (size_t)j * N, !acc, false, &D);
-    }
+    for (int j : cols) residual_async(h, b[j], z[j], h->d_mR.as<double>() + (size_t)j * N, !acc, false, j);
   HCHECK(h, hipGetLastError());
   h->multi_passes++;
   return HIPFACT_OK;
@@ -161,30 +148,20 @@ static int multi_block(hipfact_handle* h, int nb, int first, const double* d_rhs
       if ((rc = multi_pass(h, open, rhs, z, b, true, true))) return rc;
       HCHECK(h, hipStreamSynchronize(h->stream));
     }
+    // the verdict of every column (refine_verdict); the first failing one is reported
     bool stalled = false;
     for (int j = 0; j < nb; ++j) {
       const RefineCtl& c = hc[j];
       if (omega) omega[j] = c.omega;
-      if (!h->refine_adaptive || c.status == 2 || h->multi_failed_col >= 0) continue;  // (a non-finite column is the caller's)
-      char buf[260];
-      if (c.omega > h->fail_omega) {
-        stalled = true;
-        snprintf(buf, sizeof buf, "working set is numerically singular: iterative refinement of column %d stalled at backward "
-                 "error %.2e after %d passes (pivot-ratio condition estimate %.2e)", first + j, c.omega, c.iters, c.kappa);
-      } else if (h->reg_delta > 0.0 && c.rnorm > h->fail_omega * c.bnorm) {
-        snprintf(buf, sizeof buf, "working set is rank deficient and column %d of the right-hand sides is not in the range of K: "
-                 "residual %.2e of its norm after %d passes on the statically pivoted factor", first + j, c.rnorm / c.bnorm, c.iters);
-      } else {
-        continue;
-      }
-      h->error = buf;
+      const Verdict v = refine_verdict(h, c);
+      if (v == Verdict::accepted || h->multi_failed_col >= 0) continue;
+      stalled = v == Verdict::stalled;
+      set_verdict_error(h, v, c, first + j);
       h->multi_failed_col = first + j;
     }
     if (h->multi_failed_col < 0) return HIPFACT_OK;
-    // dependent rows that rounding kept from an exact zero pivot show as a refinement that stalls (finish_solve):
-    // static pivoting as behind a zero pivot, then the block once more on the shifted factor
-    if (attempt == 0 && stalled && static_pivot_applies(h) && !h->no_solve_retry && h->pivot_ratio > 1e14 &&
-        static_pivot_retry(h, HIPFACT_ESINGULAR) == HIPFACT_OK) {
+    // (stalled_retry_applies: the block once more on the shifted factor, once)
+    if (attempt == 0 && stalled && stalled_retry_applies(h) && static_pivot_retry(h, HIPFACT_ESINGULAR) == HIPFACT_OK) {
       h->multi_failed_col = -1;
       continue;
     }
@@ -195,21 +172,14 @@ static int multi_block(hipfact_handle* h, int nb, int first, const double* d_rhs
 // columns of a plan state with the low-rank dense-column correction (dense_mode 2): one by one through the single
 // solve.  Every column is a CHECKED solve (residual, verdict, correction passes: the refine_check_every cadence of the
 // single path is switched off for the call), and what the single path remembers between solves is put back afterwards:
-// "the last solve", the check cadence, the solve count that forms the top block, the inline-pass hint and the
-// counters.  The columns do use d_y, the epoch and the exchange slots, as every single solve does after another.
+// SingleSolveMemo and FactorMemo (runtime_types.inc), each as a whole - but for the judgement of a factorisation these
+// columns were the first to judge (FactorMemo::put_back_over).  The columns do use d_y, the epoch and the
+// exchange slots, as every single solve does after another.
 static int multi_single_cols(hipfact_handle* h, int nrhs, const double* d_rhs, long long ld_rhs, double* d_sol,
                              long long ld_sol, bool in_place, double* omega) {
   const size_t N = (size_t)h->N_ext;
-  const double* const keep_b = h->last_b;
-  double* const keep_z = h->last_z;
-  const bool keep_solved = h->solved, keep_pre = h->sol_prefetched, keep_checked = h->last_solve_checked;
-  const RefineCtl keep_ctl = h->last_ctl;
-  const int keep_every = h->refine_check_every, keep_interval = h->check_interval_now, keep_since = h->solves_since_check;
-  const auto keep_this_factor = h->solves_this_factor;
-  const int keep_inline = h->refine_inline;
-  const bool keep_hint = h->wc_hint, keep_probe = h->inline_probe;
-  const auto keep_num_solve = h->num_solve, keep_num_passes = h->num_passes, keep_num_refined = h->num_refined,
-             keep_num_checked = h->num_checked;
+  const SingleSolveMemo keep = *h;
+  const FactorMemo keep_factor = *h;
   h->refine_check_every = 1;
   h->check_interval_now = 1;
   int rc = HIPFACT_OK;
@@ -219,7 +189,7 @@ static int multi_single_cols(hipfact_handle* h, int nrhs, const double* d_rhs, l
       if (hipMemcpyAsync(h->d_mB.p, bj, N * sizeof(double), hipMemcpyDeviceToDevice, h->stream) != hipSuccess) rc = HIPFACT_EDEVICE;
       bj = h->d_mB.as<double>();
     }
-    h->solves_this_factor = keep_this_factor - 1;  // (solve_async counts it back up: the top block is not formed earlier than without this call)
+    h->solves_this_factor = keep_factor.solves_this_factor - 1;  // (solve_async counts it back up: the top block is not formed earlier than without this call)
     if (rc == HIPFACT_OK) rc = solve_async(h, bj, d_sol + (size_t)j * ld_sol);
     if (rc == HIPFACT_OK) rc = finish_solve(h);
     if (rc == HIPFACT_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = HIPFACT_EDEVICE;
@@ -227,24 +197,8 @@ static int multi_single_cols(hipfact_handle* h, int nrhs, const double* d_rhs, l
     if (rc == HIPFACT_ESINGULAR) h->multi_failed_col = j;
     h->multi_single_cols++;
   }
-  h->last_b = keep_b;
-  h->last_z = keep_z;
-  h->solved = keep_solved;
-  h->sol_prefetched = keep_pre;
-  h->last_solve_checked = keep_checked;
-  h->last_ctl = keep_ctl;
-  h->refine_check_every = keep_every;
-  h->check_interval_now = keep_interval;
-  h->solves_since_check = keep_since;
-  h->solves_this_factor = keep_this_factor;
-  if (!keep_probe) {  // (a factorisation whose first solve has not been judged yet keeps what these columns found)
-    h->refine_inline = keep_inline;
-    h->wc_hint = keep_hint;
-  }
-  h->num_solve = keep_num_solve;
-  h->num_passes = keep_num_passes;
-  h->num_refined = keep_num_refined;
-  h->num_checked = keep_num_checked;
+  static_cast<SingleSolveMemo&>(*h) = keep;
+  static_cast<FactorMemo&>(*h) = keep_factor.put_back_over(*h);
   return rc;
 }
 

@@ -72,7 +72,7 @@ static void turn_leave(hipfact_handle* h) {
 }
 
 // queue the numeric factorisation on the stream (values already in d_Kval, or still in h->vals_ride)
-static DecideIn decide_in(hipfact_handle* h);
+static DecideIn decide_in(hipfact_handle* h, int col = -1);
 // k_diag_inactive has something to write: a row of the structure outside the working set, or a late variable
 static inline bool diag_inactive_needed(const hipfact_handle* h) {
   const Plan& P = h->plan;
@@ -251,10 +251,16 @@ template <class F>
 static int run_cached(hipfact_handle* h, int kind, const void* b, void* z, F enqueue, int passes = 0);
 
 static void flush_decide(hipfact_handle* h);
-static DecideIn decide_in(hipfact_handle* h);
 static void drop_graphs(hipfact_handle* h);
 static int reset_dataflow_state(hipfact_handle* h);
 
+// The judgement "well conditioned": the first pass alone met a quarter of the tolerance.  What follows from it: no
+// correction pass in the solve graphs of this factorisation - or (well = false: the judgement withdrawn) a pass again.
+static inline bool first_pass_sufficed(const RefineCtl& c) { return c.done && c.status == 0 && c.iters == 0 && c.omega <= 0.25 * c.tol; }
+static inline void judge_conditioning(hipfact_handle* h, bool well) {
+  h->wc_hint = well;
+  h->refine_inline = well ? 0 : std::max(h->refine_inline, std::min(h->refine_steps, 1));
+}
 // src: the caller's values on the device (hipfact_refactor_device), copied into d_Kval in front of the factorisation
 static int factor_async(hipfact_handle* h, const double* src = nullptr) {
   const Plan& P = h->plan;
@@ -333,7 +339,7 @@ static int factor_async(hipfact_handle* h, const double* src = nullptr) {
     const int seq = __atomic_load_n(&hc->seq, __ATOMIC_ACQUIRE);
     if (seq > h->first_factor_seq && seq > h->hint_seq_seen) {  // (a verdict nobody has looked at yet)
       h->hint_seq_seen = seq;
-      h->wc_hint = hc->done && hc->status == 0 && hc->iters == 0 && hc->omega <= 0.25 * hc->tol;
+      h->wc_hint = first_pass_sufficed(*hc);
     }
   }
   h->refine_inline = (h->wc_hint && h->refine_adaptive) ? 0 : h->refine_steps;
@@ -574,6 +580,21 @@ static void launch_x_saddle(hipfact_handle* h, const SaddleMaps& M, const double
   acc ? go(std::true_type()) : go(std::false_type());
 }
 
+// the same two ends of a plan without the saddle structure: y = b in pivot order, z = (acc: z +) y in the caller's
+static void launch_rhs_perm(hipfact_handle* h, const double* b, const int* skip, double* y = nullptr) {
+  const Plan& P = h->plan;
+  LAUNCH(PC_PERM, k_gather_skip, dim3(nblocks(P.m)), dim3(FB), 0, (long long)P.m, h->d_perm.as<int>(), b,
+         y ? y : h->d_y.as<double>(), skip);
+}
+static void launch_x_perm(hipfact_handle* h, double* z, bool acc, const int* skip, int* epoch, const double* y = nullptr) {
+  const Plan& P = h->plan;
+  if (!y) y = h->d_y.as<double>();
+  if (acc)
+    LAUNCH(PC_PERM, k_scatter_acc, dim3(nblocks(P.m)), dim3(FB), 0, (long long)P.m, h->d_perm.as<int>(), y, z, skip, epoch);
+  else
+    LAUNCH(PC_PERM, k_scatter, dim3(nblocks(P.m)), dim3(FB), 0, (long long)P.m, h->d_perm.as<int>(), y, z, epoch);
+}
+
 // z = K^-1 b (acc: z += K^-1 b) without refinement; b, z device vectors in the caller's
 // numbering, b != z
 static void solve_once_async(hipfact_handle* h, const double* b, double* z, bool acc, const int* skip, bool raw = false) {
@@ -627,15 +648,9 @@ static void solve_once_async(hipfact_handle* h, const double* b, double* z, bool
     }
     if (!whole) launch_x_saddle(h, M, b, z, acc, skip, epoch);
   } else {
-    LAUNCH(PC_PERM, k_gather_skip, dim3(nblocks(P.m)), dim3(FB), 0, (long long)P.m, h->d_perm.as<int>(), b,
-           h->d_y.as<double>(), skip);
+    launch_rhs_perm(h, b, skip);
     solve_m_async(h, skip);
-    if (acc)
-      LAUNCH(PC_PERM, k_scatter_acc, dim3(nblocks(P.m)), dim3(FB), 0, (long long)P.m, h->d_perm.as<int>(),
-             h->d_y.as<double>(), z, skip, epoch);
-    else
-      LAUNCH(PC_PERM, k_scatter, dim3(nblocks(P.m)), dim3(FB), 0, (long long)P.m, h->d_perm.as<int>(),
-             h->d_y.as<double>(), z, epoch);
+    launch_x_perm(h, z, acc, skip, epoch);
   }
 }
 
@@ -645,19 +660,22 @@ static inline int resid_blocks(const Plan& P) {  // saddle: an even number >= 2 
   return P.saddle ? std::max(2, nblocks((long long)P.N * 8, g_resid_cap) & ~1) : nblocks(P.N, g_resid_cap);
 }
 
-static DecideIn decide_in(hipfact_handle* h) {
+// where a verdict is formed: control block, pinned copy, partial maxima; the handle's, or (col >= 0) a column's of the blocked solve
+static DecideIn decide_in(hipfact_handle* h, int col) {
+  const bool own = col >= 0;
+  const size_t j = own ? (size_t)col : 0;
   // non-adaptive mode (negative target): every in-graph pass runs
-  return DecideIn{h->d_ctl.as<RefineCtl>(), static_cast<RefineCtl*>(h->h_ctl_dev), h->d_norms.as<double>(),
-                  resid_blocks(h->plan), h->refine_adaptive ? h->refine_tol : -1.0, minmax_ptr(h)};
+  return DecideIn{(own ? h->d_mctl : h->d_ctl).as<RefineCtl>() + j, static_cast<RefineCtl*>(own ? h->h_mctl_dev : h->h_ctl_dev) + j,
+                  (own ? h->d_mnorms : h->d_norms).as<double>() + j * 3 * g_resid_cap, resid_blocks(h->plan),
+                  h->refine_adaptive ? h->refine_tol : -1.0, minmax_ptr(h)};
 }
 
 // res = b - K z; updates the refinement control block (first: the residual of the first pass).  defer: no verdict
-// launch behind it - the next tree launch (or flush_decide) delivers it.  own: the control block, its pinned copy and
-// the partial maxima of ONE column of the blocked solve (runtime_multi.inc) instead of the handle's
+// launch behind it - the next tree launch (or flush_decide) delivers it.  col: decide_in
 static void residual_async(hipfact_handle* h, const double* b, const double* z, double* res, bool first,
-                           bool defer = false, const DecideIn* own = nullptr) {
+                           bool defer = false, int col = -1) {
   const Plan& P = h->plan;
-  const DecideIn D = own ? *own : decide_in(h);
+  const DecideIn D = decide_in(h, col);
   RefineCtl* ctl = D.ctl;
   double* norms = const_cast<double*>(D.partials);
   int* dflag = defer ? &ctl->pending : nullptr;
@@ -776,6 +794,13 @@ static bool defers_decide(const hipfact_handle* h) {
   return h->decide_lazy && h->refine_steps > 0 && h->refine_adaptive && h->refine_inline == 0 && tree_delivers_verdict(h);
 }
 
+// Keys of the captured solve sequences (run_cached's `passes`, the launch notes): the correction passes in the graph (a
+// solve: -2 with the verdict left to the next tree launch, -1 without a residual), top_block_key added with the top block
+static inline int top_block_key(const hipfact_handle* h) { return h->tb_valid ? 1000 : 0; }
+static inline int solve_graph_key(const hipfact_handle* h, bool defer) {
+  return (h->refine_steps > 0 ? (defer ? -2 : h->refine_inline) : -1) + top_block_key(h);
+}
+
 // first pass z = K^-1 b, residual, and the in-graph correction passes
 static int solve_enqueue(hipfact_handle* h, const double* b, double* z) {
   const double* bb = b;
@@ -869,13 +894,7 @@ static int solve_async(hipfact_handle* h, const double* b, double* z) {
     // continued at the next synchronising entry point, which also puts the pass back.
     const RefineCtl* hc = h->h_ctl.as<RefineCtl>();
     if (__atomic_load_n(&hc->seq, __ATOMIC_ACQUIRE) == h->solve_seq) {
-      if (hc->done && hc->status == 0 && hc->iters == 0 && hc->omega <= 0.25 * hc->tol) {
-        h->refine_inline = 0;
-        h->wc_hint = true;
-      } else {
-        h->wc_hint = false;
-        h->refine_inline = std::max(h->refine_inline, std::min(h->refine_steps, 1));
-      }
+      judge_conditioning(h, first_pass_sufficed(*hc));
       h->inline_probe = false;
     }
   }
@@ -895,11 +914,9 @@ static int solve_async(hipfact_handle* h, const double* b, double* z) {
   h->last_solve_checked = !unchecked;
   // (an unchecked steady-state solve is two launches: queued directly - replaying a two-node graph measures 4-5 us
   // slower per solve than the launches themselves)
-  // (graphs with and without the top block are different launches: +1000 in the key)
-  h->note(unchecked ? 'U' : 'S', (h->refine_steps > 0 ? (defer ? -2 : h->refine_inline) : -1) + (h->tb_valid ? 1000 : 0));
-  int rc = unchecked ? solve_enqueue(h, b, z)
-                     : run_cached(h, 1, b, z, [&] { return solve_enqueue(h, b, z); },
-                                  (h->refine_steps > 0 ? (defer ? -2 : h->refine_inline) : -1) + (h->tb_valid ? 1000 : 0));
+  const int key = solve_graph_key(h, defer);
+  h->note(unchecked ? 'U' : 'S', key);
+  int rc = unchecked ? solve_enqueue(h, b, z) : run_cached(h, 1, b, z, [&] { return solve_enqueue(h, b, z); }, key);
   h->skip_resid_now = false;
   if (rc) return rc;
   if (!unchecked) h->decide_deferred = defer;  // (the tree launch of this solve has delivered an older one)
@@ -912,15 +929,48 @@ static int solve_async(hipfact_handle* h, const double* b, double* z) {
   return HIPFACT_OK;
 }
 
-// Called by entry points that synchronise anyway: looks at the control block of the last solve,
 static bool vtable_can_retry(const hipfact_handle* h);
 static int vtable_retry_exact(hipfact_handle* h);
-
-// continues a refinement that is still running, and reports a solve that stalled far above the
-// tolerance (numerically singular working set) or a timed-out dataflow launch.
-// (synced: the caller has just awaited the stream behind the solve and its verdict)
 static bool static_pivot_applies(const hipfact_handle* h);
 static int static_pivot_retry(hipfact_handle* h, int rc);
+
+// The verdict on a refinement that has ended, for the single solve (finish_solve) and for every column of the blocked
+// one (multi_block).  accepted includes a non-finite solve (status 2): that one is the caller's case.  The two failures
+// exclude each other (omega > fail_omega, omega <= fail_omega): the order they are asked in decides nothing.
+enum class Verdict { accepted, stalled, out_of_range };
+static Verdict refine_verdict(const hipfact_handle* h, const RefineCtl& c) {
+  if (!h->refine_adaptive || c.status == 2) return Verdict::accepted;
+  if (c.omega > h->fail_omega) return Verdict::stalled;
+  // A statically pivoted factor of a rank-deficient K: a right-hand side outside the range of K has no solution, and
+  // the refinement answers it with a huge z whose NORMWISE backward error ||r|| / (||z|| + ||b||) is small - z solves a
+  // system next to K, as a pivoted method's garbage does.  The residual is therefore judged against the right-hand
+  // side alone as well: consistent systems reach rounding level, inconsistent ones stay at the distance of b from
+  // the range.
+  if (h->reg_delta > 0.0 && c.rnorm > h->fail_omega * c.bnorm) return Verdict::out_of_range;
+  return Verdict::accepted;
+}
+// h->error for a verdict that is not `accepted`; col >= 0: of that column of a blocked solve
+static void set_verdict_error(hipfact_handle* h, Verdict v, const RefineCtl& c, int col = -1) {
+  char of_col[32] = "", subject[48] = "the right-hand side", buf[260];
+  if (col >= 0) {
+    snprintf(of_col, sizeof of_col, " of column %d", col);
+    snprintf(subject, sizeof subject, "column %d of the right-hand sides", col);
+  }
+  if (v == Verdict::stalled)
+    snprintf(buf, sizeof buf, "working set is numerically singular: iterative refinement%s stalled at backward error %.2e after %d "
+             "passes (pivot-ratio condition estimate %.2e)", of_col, c.omega, c.iters, c.kappa);
+  else
+    snprintf(buf, sizeof buf, "working set is rank deficient and %s is not in the range of K: residual %.2e of %s norm after %d "
+             "passes on the statically pivoted factor", subject, c.rnorm / c.bnorm, col >= 0 ? "its" : "the right-hand side's", c.iters);
+  h->error = buf;
+}
+// Dependent rows that rounding kept from an exact zero pivot (a pivot sixteen decades under the largest) show as a stalled
+// refinement: static pivoting as behind a zero pivot, then the same solve or block once more (inconsistent: fails again)
+static bool stalled_retry_applies(const hipfact_handle* h) { return static_pivot_applies(h) && !h->no_solve_retry && h->pivot_ratio > 1e14; }
+
+// Called by entry points that synchronise anyway: looks at the control block of the last solve, continues a refinement
+// that is still running, and reports a solve that stalled far above the tolerance (numerically singular working set) or
+// a timed-out dataflow launch.  (synced: the caller has just awaited the stream behind the solve and its verdict)
 static int finish_solve(hipfact_handle* h, bool* continued = nullptr, bool synced = false) {
   if (continued) *continued = false;
   if (!h->ctl_pending) return HIPFACT_OK;
@@ -934,8 +984,8 @@ static int finish_solve(hipfact_handle* h, bool* continued = nullptr, bool synce
     const int passes = std::min(std::max(h->refine_inline, 1), h->refine_max - c.iters);
     const double* b = h->last_b;
     double* z = h->last_z;
-    h->note('C', passes + (h->tb_valid ? 1000 : 0));
-    int rc = run_cached(h, 2, b, z, [&] { return correct_enqueue(h, b, z, passes); }, passes + (h->tb_valid ? 1000 : 0));
+    h->note('C', passes + top_block_key(h));
+    int rc = run_cached(h, 2, b, z, [&] { return correct_enqueue(h, b, z, passes); }, passes + top_block_key(h));
     if (rc) return rc;
     HCHECK(h, hipStreamSynchronize(h->stream));
     memcpy(&c, h->h_ctl.p, sizeof(c));
@@ -946,10 +996,7 @@ static int finish_solve(hipfact_handle* h, bool* continued = nullptr, bool synce
   if (more > 0) h->sol_prefetched = false;  // (the copy sent to the host behind the solve is the unrefined one)
   if (h->inline_probe && h->refine_adaptive && h->refine_steps > 0) {
     // (the verdict of the first solve of this factorisation, read here instead of at the next solve's peek)
-    if (c.done && c.status == 0 && c.iters == 0 && c.omega <= 0.25 * c.tol) {
-      h->refine_inline = 0;
-      h->wc_hint = true;
-    }
+    if (first_pass_sufficed(c)) judge_conditioning(h, true);
     h->inline_probe = false;
   }
   if (continued) *continued = more > 0;
@@ -970,42 +1017,19 @@ static int finish_solve(hipfact_handle* h, bool* continued = nullptr, bool synce
     h->refine_inline = std::min(std::max(h->refine_inline, c.iters), 4);
     h->wc_hint = false;
   }
-  if (h->refine_adaptive && c.status != 2 && c.omega > h->fail_omega && static_pivot_applies(h) && !h->no_solve_retry &&
-      h->pivot_ratio > 1e14 && h->last_b && h->last_z) {
-    // dependent rows that rounding kept from an exact zero pivot (a pivot sixteen decades under the largest: S is
-    // singular to working precision) show here, as a refinement that stalls: static pivoting as behind a zero pivot,
-    // then the same solve once more on the shifted factor (an inconsistent right-hand side stalls again and is reported)
+  const Verdict v = refine_verdict(h, c);
+  if (v == Verdict::stalled && stalled_retry_applies(h) && h->last_b && h->last_z) {
     const double* b2 = h->last_b;
     double* z2 = h->last_z;
     if (b2 == z2) return HIPFACT_ESINGULAR;  // (in place: the right-hand side is gone)
-    const int r2 = static_pivot_retry(h, HIPFACT_ESINGULAR);
-    if (r2 == HIPFACT_OK) {
-      int r3 = solve_async(h, b2, z2);
-      if (r3) return r3;
+    if (static_pivot_retry(h, HIPFACT_ESINGULAR) == HIPFACT_OK) {
+      if (int r3 = solve_async(h, b2, z2)) return r3;
       return finish_solve(h, continued);
     }
   }
-  if (h->refine_adaptive && c.status != 2 && h->reg_delta > 0.0 && c.omega <= h->fail_omega && c.rnorm > h->fail_omega * c.bnorm) {
-    // A statically pivoted factor of a rank-deficient K: a right-hand side outside the range of K has no solution, and
-    // the refinement answers it with a huge z whose NORMWISE backward error ||r|| / (||z|| + ||b||) is small - z solves a
-    // system next to K, as a pivoted method's garbage does.  The residual is therefore judged against the right-hand
-    // side alone as well: consistent systems reach rounding level, inconsistent ones stay at the distance of b from
-    // the range.
-    char buf[240];
-    snprintf(buf, sizeof buf, "working set is rank deficient and the right-hand side is not in the range of K: residual %.2e "
-             "of the right-hand side's norm after %d passes on the statically pivoted factor", c.rnorm / c.bnorm, c.iters);
-    h->error = buf;
-    return HIPFACT_ESINGULAR;
-  }
-  if (h->refine_adaptive && c.status != 2 && c.omega > h->fail_omega) {
-    char buf[200];
-    snprintf(buf, sizeof buf,
-             "working set is numerically singular: iterative refinement stalled at backward error %.2e after %d "
-             "passes (pivot-ratio condition estimate %.2e)", c.omega, c.iters, c.kappa);
-    h->error = buf;
-    return HIPFACT_ESINGULAR;
-  }
-  return HIPFACT_OK;
+  if (v == Verdict::accepted) return HIPFACT_OK;
+  set_verdict_error(h, v, c);
+  return HIPFACT_ESINGULAR;
 }
 
 // word-wise FNV-1a (the patterns are megabytes: this runs at memory speed)

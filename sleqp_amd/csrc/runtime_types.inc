@@ -158,14 +158,36 @@ struct GraphList {
   void push_back(const GraphEntry& g) { v.push_back(g); }
 };
 
+// What the single-solve path (solve_async, finish_solve) remembers about the CURRENT factorisation of a plan (it parks
+// with the plan).  Solves that are not to be remembered (multi_single_cols) put it back as a whole.  seq_at_factor,
+// hint_seq_seen, first_factor_seq place the factorisation in the handle's solve_seq, which such solves do advance: not here.
+struct FactorMemo {
+  bool solved = false;           // a single solve has been queued on this factorisation
+  long solves_this_factor = 0;   // (the count that forms the top block)
+  int refine_inline = 1;         // correction passes currently carried by the solve graphs
+  bool inline_probe = true;      // the first solve of this factorisation has not been looked at yet
+  bool wc_hint = false;          // the previous factorisation of this plan was judged well-conditioned (first pass enough)
+  // `*this` saved in front of such solves, `now` what they left.  Everything goes back, with ONE exception: a factorisation
+  // not yet judged when saved (inline_probe) keeps the judgement found since, and inline_probe itself is never put back.
+  FactorMemo put_back_over(const FactorMemo& now) const {
+    FactorMemo r = *this;
+    r.inline_probe = now.inline_probe;
+    if (inline_probe) {
+      r.refine_inline = now.refine_inline;
+      r.wc_hint = now.wc_hint;
+    }
+    return r;
+  }
+};
+
 // Everything that belongs to ONE symbolic plan: the plan, its device image, the numeric arenas
 // and the captured graphs (which hold pointers into exactly these buffers).  The handle IS the
 // active state (it derives from this struct, so h->d_L etc. address the active plan); states of
 // other sparsity patterns / working-set supersets wait in an LRU list and are swapped in whole,
 // so coming back to a pattern seen before costs neither an analysis nor an upload nor a capture.
-struct PlanState {
+struct PlanState : FactorMemo {
   Plan plan;
-  bool have_plan = false, factored = false, solved = false;
+  bool have_plan = false, factored = false;
   bool factor_checked = false;  // info words of the last factorisation have been read back
   bool prod_packed = false;     // product lists as one packed word per pair
   bool idx32 = false;           // product-list pointers and panel targets fit 32 bits
@@ -180,10 +202,7 @@ struct PlanState {
   int n_inactive = 0;         // rows of the structure outside the current working set (cmap == -1): k_diag_inactive writes their unit pivots
   int n_bounds = 0;           // active bounds of the current working set
   unsigned long long use_stamp = 0;  // LRU clock
-  int refine_inline = 1;      // correction passes currently carried by the solve graphs
   int seq_at_factor = 0;      // handle's solve_seq at the time of the last factorisation
-  bool inline_probe = true;   // the first solve of this factorisation has not been looked at yet
-  bool wc_hint = false;       // the previous factorisation of this plan was judged well-conditioned (first pass enough)
   int hint_seq_seen = -1;     // the last verdict a refactorisation has looked at (factor_hint_peek)
   int first_factor_seq = -1;  // handle's solve_seq at the first factorisation of this plan (verdicts behind it belong to its factorisations)
   GraphList graphs;
@@ -214,7 +233,6 @@ struct PlanState {
   // top block of the solve (device_types.h: TopBlockIn): the fronts of the last levels as two dense products
   int tb_nT = 0, tb_ntf = 0, tb_nfb = 0, tb_levels = 0, tb_nchunks = 0;  // nfb: items of the fronts below T
   bool tb_valid = false;       // X_T of the CURRENT factorisation has been formed
-  long solves_this_factor = 0;
   long solves_prev_factor = 1 << 20;  // solves the previous factorisation of this plan saw (a fresh plan: as if many)
   DevBuf d_tb_gathered;  // TopBlockIn::gathered2
   DevBuf d_tb_zd, d_tb_items, d_tb_xtf, d_tb_tpos, d_tb_tl, d_tb_gptr, d_tb_gsrc, d_tb_xhat, d_tb_xd, d_tb_fronts,
@@ -242,7 +260,26 @@ struct PlanState {
 #include "vtable_superset.inc"
 #undef VTABLE_SUPERSET_TYPES
 
-struct hipfact_handle : PlanState {
+// What the single-solve path remembers on the handle for the NEXT call to find: the last solve, the cadence of the
+// residual checks, the counters of hipfact_get_info.  multi_single_cols copies the struct out and back around its columns:
+// a member added here is put back there.  NOT here (the columns really advance them): ctl_pending, solve_seq, decide_deferred.
+struct SingleSolveMemo {
+  const double* last_b = nullptr;
+  double* last_z = nullptr;
+  RefineCtl last_ctl = {1, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0};
+  bool last_solve_checked = true;  // the last solve_async carried a residual (and possibly correction passes)
+  bool sol_prefetched = false;     // h_sol_pin holds the solution of the last solve (valid once ev_sol has fired)
+  // Once a factorisation has been judged well-conditioned (its solves meet the tolerance in the first pass with room
+  // to spare: no correction pass in their graph), the residual of K z = b is checked on every k-th solve only - the
+  // reference's MA57 path never checks (fact_ma57.c:18).  1: every solve (the blocked solve's setting for its call).
+  int refine_check_every = 8;
+  int check_interval_now = 0;      // (the interval in force; back to refine_check_every with every factorisation)
+  long solves_since_check = 0;
+  // solves / those whose residual was taken / that applied at least one correction pass / passes applied in total
+  long num_solve = 0, num_checked = 0, num_refined = 0, num_passes = 0;
+};
+
+struct hipfact_handle : PlanState, SingleSolveMemo {
   std::atomic<int> refcount{1};
   int device = 0;
   hipStream_t stream = nullptr;
@@ -306,29 +343,17 @@ struct hipfact_handle : PlanState {
   long static_pivot_runs = 0;
   std::string warning;  // of the last factorisation ("" = none): rank deficiency handled by static pivoting
   bool equilibrate = true;       // row equilibration of the constraint block (saddle mode)
-  long num_refined = 0;          // solves that applied at least one correction pass
-  long num_passes = 0;           // correction passes applied in total
   bool decide_lazy = true;       // verdict of a solve without correction passes delivered by the next tree launch
-  // Once a factorisation has been judged well-conditioned (its solves meet the tolerance in the first pass with room
-  // to spare: no correction pass in their graph), the residual of K z = b is checked on every k-th solve only - the
-  // reference's MA57 path never checks (fact_ma57.c:18).  1: every solve.
-  int refine_check_every = 8;
-  int refine_check_backoff = 2;  // the interval is multiplied by this after every periodic check (1 = fixed interval)
+  int refine_check_backoff = 2;  // the interval (refine_check_every, SingleSolveMemo) is multiplied by this after every periodic check (1 = fixed interval)
   int refine_check_max = 64;     // ... up to this many solves between two checks
-  int check_interval_now = 0;    // (the interval in force; back to refine_check_every with every factorisation)
-  long num_checked = 0;          // solves whose residual was taken
   double pivot_ratio = 1.0;      // largest / smallest positive pivot of the last factorisation (check_info)
   bool no_solve_retry = false;   // (a probe solve: no change of plan behind a stalled refinement)
   long dense_probes = 0;
   bool skip_resid_now = false;   // (the solve being queued is one of the unchecked ones)
-  long solves_since_check = 0;
   bool decide_deferred = false;  // ... and such a verdict is outstanding
   bool decide_rides = false;     // (during factor_enqueue) it is delivered by the first block of k_row_scale
   const double* vals_ride = nullptr;  // (during factor_enqueue) the caller's device values: k_row_scale reads them there and writes d_Kval
   bool ctl_pending = false;      // the control block of the last solve has not been looked at yet
-  const double* last_b = nullptr;
-  double* last_z = nullptr;
-  RefineCtl last_ctl = {1, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0};
   int solve_seq = 0;             // solves with a residual queued since the control block was last cleared
   bool use_graph = true;         // replay captured hipGraphs instead of re-enqueueing ~100 launches
   // The single-launch dataflow kernels rely on workgroups being dispatched in index order (observed per XCD on every
@@ -354,7 +379,6 @@ struct hipfact_handle : PlanState {
   long long pair_extra = 0;      // doubles behind the plan's update-matrix arena for the paired fronts (two slots)
   double schur_flops_max = 0.0;  // fp64 flops of the Schur updates of the level that has the most (one launch of k_front_schur when the level runs split)
   bool check_launches = false, launch_reported = false;  // HIPFACT_CHECK_LAUNCHES: report the first refused launch
-  bool last_solve_checked = true;  // the last solve_async carried a residual (and possibly correction passes)
   double* x_dot_out = nullptr;  // set around a projection of the device-controlled CG
   int x_dot_blocks = 0;
   int xupd_blocks = 256;      // workgroups of the x update inside the tree launch (xupd_fused)
@@ -378,7 +402,7 @@ struct hipfact_handle : PlanState {
   int panel_small_below = 0;  // levels with fewer 128-row panel blocks use 64-row blocks
   int pull_max_children = 4;  // 0: always the separate assembly kernel; otherwise pull for any number of children
   int top_max_fronts = 1024;
-  long cache_hits = 0, analyses = 0, num_factor = 0, num_solve = 0;
+  long cache_hits = 0, analyses = 0, num_factor = 0;
   int info_host[INFO_WORDS] = {0, 0, 0, 0};
   Prof prof;
   // shared by all plan states (fixed size, never reallocated: graphs of every state may point at them)
@@ -403,7 +427,6 @@ struct hipfact_handle : PlanState {
   int rhs_slot = 0;
   bool boundary_fast = true;     // option: off = the round-3 path (pageable borrows, three blocking points)
   bool validate_rhs = false;     // option: walk the index array of every sparse right-hand side on the host
-  bool sol_prefetched = false;   // h_sol_pin holds the solution of the last solve (valid once ev_sol has fired)
   // option boundary_profile: where the time of solve + solution goes (sums over the calls since it was switched on)
   bool bd_profile = false;
   hipEvent_t bd_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // rhs on device | solve done | download done

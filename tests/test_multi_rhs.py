@@ -340,12 +340,24 @@ def _against_oracle(fact, hip, N, kc, kr, kd, n, k=5, seed=3):
         assert scaled_residual(K, Z[:, j], B[:, j]) <= RESID_TOL, j
 
 
-@pytest.mark.parametrize("mode", [1, 2], ids=["late_elimination", "low_rank_correction"])
-def test_dense_jacobian_columns(fact, hip, mode):
+# every info word of the single path: what a multi solve through the single solve (dense_mode 2) must leave as it was
+SINGLE_PATH_INFO = ("num_solve", "num_checked", "num_passes", "num_refined", "refine_check_interval", "refine_check_every",
+                    "refine_inline", "last_omega", "last_iters", "last_status", "last_tol", "kappa_est")
+
+
+@functools.lru_cache(maxsize=None)
+def _dense_columns_case():
+    """K with four dense columns in the Jacobian (n = 1500, m = 700): computed once, shared, never modified."""
     n, m = 1500, 700
     J, _ = synth.with_dense_columns(synth.banded_jacobian(n, m, 10, 80, 17), 4, 5)
     vi, ci, _ = synth.working_set_all_rows(n, m, 0.0, 0)
     N, kc, kr, kd = oracle.fill_aug_jac(n, m, J.indptr, J.indices, J.data, vi, ci)
+    return n, N, kc, kr, kd
+
+
+@pytest.mark.parametrize("mode", [1, 2], ids=["late_elimination", "low_rank_correction"])
+def test_dense_jacobian_columns(fact, hip, mode):
+    n, N, kc, kr, kd = _dense_columns_case()
     fact.set_option("dense_mode", mode)
     _set(fact, N, kc, kr, kd)
     if mode == 1:
@@ -363,7 +375,7 @@ def test_dense_jacobian_columns(fact, hip, mode):
         fact.solve(b)
     z0 = fact.solution_raw(0, N)
     tol = fact.info("last_tol")
-    counters = {k: fact.info(k) for k in ("num_solve", "num_checked", "refine_check_interval")}
+    counters = {k: fact.info(k) for k in SINGLE_PATH_INFO}
     B = _columns(n, N, 5, 3)
     B[:, 4] = np.random.default_rng(5).standard_normal(N)  # (instead of the zero column, whose omega is 0)
     Z, omega, _, _ = _solve(fact, hip, B)
@@ -378,6 +390,32 @@ def test_dense_jacobian_columns(fact, hip, mode):
     assert counters == {k: fact.info(k) for k in counters}
     fact.solve(b)
     assert np.array_equal(_bits(fact.solution_raw(0, N)), _bits(z0))
+
+
+def test_multi_solve_is_the_first_solve_of_a_factorisation(fact, hip):
+    """dense_mode 2, and the columns are the first solves the factorisation sees: nothing has judged it yet, so the
+    judgement the columns reach (the correction passes the solve graphs carry) is NOT put back - the one branch of the
+    restore that keeps what the multi solve found.  The counters and "the last solve" are put back as always."""
+    n, N, kc, kr, kd = _dense_columns_case()
+    K = synth.kkt_full_matrix(N, kc, kr, kd)
+    fact.set_option("dense_mode", 2)
+    _set(fact, N, kc, kr, kd)
+    assert fact.info("dense_columns") == 4
+    B = _columns(n, N, 3, 3)
+    Z, omega, _, _ = _solve(fact, hip, B)
+    for j in range(3):
+        assert scaled_residual(K, Z[:, j], B[:, j]) <= RESID_TOL, j
+    assert fact.info("multi_single_cols") == 3 and fact.info("num_solve") == 0
+    print("refine_inline behind the multi solve:", fact.info("refine_inline"))
+    # 0: the columns judged the factorisation well conditioned, and that stands.  (The value the library of commit
+    # 52989ce, which added the blocked solve, shows here on the MI355X; put back, it would be the 1 = refine_steps that
+    # every fresh factorisation starts with.)
+    assert fact.info("refine_inline") == 0
+    b = np.random.default_rng(8).standard_normal(N)
+    fact.solve(b)
+    z = fact.solution_raw(0, N)
+    assert fact.info("num_solve") == 1
+    assert scaled_residual(K, z, b) <= RESID_TOL
 
 
 @pytest.mark.parametrize("variant", ["dense_rows", "active_bounds"])
@@ -458,9 +496,16 @@ def test_rank_deficient_working_set(fact, hip):
     with pytest.raises(HipfactError) as e:
         _solve(fact, hip, bad)
     assert e.value.code == ESINGULAR and fact.info("multi_failed_col") == 1
+    assert "column 1 of the right-hand sides is not in the range of K" in str(e.value)
+    assert "on the statically pivoted factor" in str(e.value)
     Z2, _, _, _ = _solve(fact, hip, B)  # the consistent block again
     assert fact.info("multi_failed_col") == -1
     assert np.array_equal(_bits(Z2), _bits(Z))
+    with pytest.raises(HipfactError) as e:  # the same column alone through the single solve: the same verdict, its words
+        fact.solve(bad[:, 1].copy())
+        fact.solution_raw(0, N)
+    assert e.value.code == ESINGULAR
+    assert "the right-hand side is not in the range of K" in str(e.value) and "column" not in str(e.value)
 
 
 # ---- 8. neighbours --------------------------------------------------------------------------------------------------------
