@@ -540,6 +540,19 @@ int hipfact_debug_copy(hipfact_handle* h, const char* name, void* out, size_t by
  * once (0 = sound). */
 int hipfact_debug_pool_selftest(int callers, int rounds);
 
+/* Placement of the front end's work by XCD, as pure host functions (no GPU needed; used by the tests).  A class is the
+ * set of workgroups with equal index modulo C; a handle takes C from HIPFACT_XCD_CLASSES (1-16, default 8) at creation.
+ * place_rows: the ranges [bounds[g], bounds[g + 1]) of the rows of A in pivot order (by Ar_ptr, m + 1 offsets;
+ * fill_bytes: what the row scaling clears) that class g of *classes_out <= classes classes owns, and the grid of the
+ * launch; `bounds` holds classes + 1 values, `blocks` 2 x classes: the first 16-row block class g takes in the
+ * kernel and how many (rows longer than the kernel's long-row threshold weigh nothing in the balance: they are segments).
+ * place_items: the item order of a per-level panel or Schur launch whose front f, in today's order, has counts[f]
+ * items: order[pos] = index of the item in today's front-by-front order, lost[pos] = 1 where position pos (class
+ * pos % classes) was filled from another class; a level with fewer fronts than classes keeps today's order. */
+int hipfact_debug_place_rows(int m, const int* Ar_ptr, long long fill_bytes, int classes, long long* bounds, int* classes_out,
+                             int* grid_out, int* blocks);
+int hipfact_debug_place_items(int nfronts, const int* counts, int classes, int* order, int* lost);
+
 /* ---- host-only symbolic plan (no GPU needed; used by the tests) ---------- */
 
 typedef struct hipfact_plan hipfact_plan;

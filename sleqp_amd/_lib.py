@@ -30,7 +30,8 @@ SYMBOLS = [
     "hipfact_solve_device", "hipfact_solve_device_multi", "hipfact_solve_multi", "hipfact_solution_device", "hipfact_synchronize", "hipfact_check", "hipfact_stream",
     "hipfact_assemble_kkt", "hipfact_reduced_matrix", "hipfact_spmat_create", "hipfact_spmat_update_values", "hipfact_spmat_free",
     "hipfact_spmat_mult_vec", "hipfact_spmat_mult_vec_trans", "hipfact_spmat_mult_vec_sym",
-    "hipfact_spmat_mult_device", "hipfact_steihaug_solve", "hipfact_tr_solve", "hipfact_tr_solve_ex", "hipfact_lsqr_solve", "hipfact_tridiag_tr", "hipfact_set_option", "hipfact_get_info", "hipfact_debug_copy", "hipfact_debug_pool_selftest", "hipfact_plan_create",
+    "hipfact_spmat_mult_device", "hipfact_steihaug_solve", "hipfact_tr_solve", "hipfact_tr_solve_ex", "hipfact_lsqr_solve", "hipfact_tridiag_tr", "hipfact_set_option", "hipfact_get_info", "hipfact_debug_copy", "hipfact_debug_pool_selftest",
+    "hipfact_debug_place_rows", "hipfact_debug_place_items", "hipfact_plan_create",
     "hipfact_plan_free", "hipfact_plan_error", "hipfact_plan_array", "hipfact_plan_scalar",
 ]
 
@@ -93,16 +94,18 @@ def load() -> C.CDLL:
     lib.hipfact_debug_copy.argtypes = [vp, C.c_char_p, vp, C.c_size_t]
     lib.hipfact_debug_pool_selftest.argtypes = [ci, ci]
     lib.hipfact_get_info.argtypes = [vp, C.c_char_p, C.POINTER(cd)]
+    if hasattr(lib, "hipfact_debug_place_items"):  # (an older build loaded through HIPFACT_LIBRARY has neither)
+        lib.hipfact_debug_place_rows.argtypes = [ci, vp, C.c_longlong, ci, vp, C.POINTER(ci), C.POINTER(ci), vp]
+        lib.hipfact_debug_place_items.argtypes = [ci, vp, ci, vp, vp]
     lib.hipfact_plan_create.argtypes = [ci, vp, vp, vp, C.POINTER(vp)]
     lib.hipfact_plan_free.argtypes = [C.POINTER(vp)]
     lib.hipfact_plan_error.argtypes = [vp]
     lib.hipfact_plan_error.restype = C.c_char_p
     lib.hipfact_plan_array.argtypes = [vp, C.c_char_p, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(ci)]
     lib.hipfact_plan_scalar.argtypes = [vp, C.c_char_p, C.POINTER(cd)]
-    for name in SYMBOLS:
-        fn = getattr(lib, name)
-        if fn.restype is C.c_int or fn.restype is None:
-            pass
+    for name in SYMBOLS:  # (the in-tree build has them all; an alternative build may be older than the header)
+        if not hasattr(lib, name) and not os.environ.get("HIPFACT_LIBRARY"):
+            raise ImportError(f"{LIB_PATH} lacks {name}: rebuild it (make -C sleqp_amd/csrc)")
     lib.hipfact_plan_free.restype = None
     _lib = lib
     return lib

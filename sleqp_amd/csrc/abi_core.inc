@@ -60,6 +60,7 @@ int hipfact_create(hipfact_handle** out, int device) {
   if (const char* s = getenv("HIPFACT_TOP_BLOCK_AFTER")) h->top_block_after = std::max(0, atoi(s));
   if (const char* s = getenv("HIPFACT_BOUNDARY_FAST")) h->boundary_fast = atoi(s) != 0;
   if (const char* s = getenv("HIPFACT_SOL_SPLIT")) h->sol_split = atoi(s) != 0;
+  if (const char* s = getenv("HIPFACT_XCD_CLASSES")) h->xcd_classes = std::max(1, std::min(XCD_CLASSES_MAX, atoi(s)));
   turn_join(h);
   *out = h;
   return HIPFACT_OK;

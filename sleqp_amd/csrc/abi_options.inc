@@ -299,6 +299,36 @@ int hipfact_debug_copy(hipfact_handle* h, const char* name, void* out, size_t by
   return HIPFACT_OK;
 }
 
+// placement by XCD (xcd_place.h) as pure host functions: what a handle with `classes` classes would launch
+int hipfact_debug_place_rows(int m, const int* Ar_ptr, long long fill_bytes, int classes, long long* bounds, int* classes_out,
+                             int* grid_out, int* blocks) {
+  if (m < 0 || (m > 0 && !Ar_ptr) || fill_bytes < 0 || classes < 1 || classes > XCD_CLASSES_MAX || !bounds || !classes_out ||
+      !grid_out || !blocks)
+    return HIPFACT_EINVAL;
+  ClassBounds cb;
+  *grid_out = place_rows(m, Ar_ptr, (size_t)fill_bytes, classes, cb);
+  *classes_out = cb.C;
+  for (int g = 0; g <= cb.C; ++g) bounds[g] = cb.b[g];
+  for (int g = 0; g < cb.C; ++g) class_row_blocks(cb, g, FB / RL, blocks[2 * g], blocks[2 * g + 1]);
+  return HIPFACT_OK;
+}
+int hipfact_debug_place_items(int nfronts, const int* counts, int classes, int* order, int* lost) {
+  if (nfronts < 0 || (nfronts > 0 && !counts) || classes < 1 || classes > XCD_CLASSES_MAX) return HIPFACT_EINVAL;
+  long long total = 0;
+  for (int f = 0; f < nfronts; ++f) {
+    if (counts[f] < 0) return HIPFACT_EINVAL;
+    total += counts[f];
+  }
+  if (total >= (1LL << 31) || (total > 0 && (!order || !lost))) return HIPFACT_EINVAL;
+  std::vector<int> o, l;
+  deal_items(std::vector<int>(counts, counts + nfronts), classes, o, &l);
+  for (size_t i = 0; i < o.size(); ++i) {
+    order[i] = o[i];
+    lost[i] = l[i];
+  }
+  return HIPFACT_OK;
+}
+
 int hipfact_get_info(const hipfact_handle* h, const char* name, double* value) {
   if (!h || !name || !value) return HIPFACT_EINVAL;
   const Plan& P = h->plan;
@@ -392,8 +422,10 @@ int hipfact_get_info(const hipfact_handle* h, const char* name, double* value) {
   INFO("device", h->device) INFO("nnzM", P.Mi.size()) INFO("nnzA", P.Ar_src.size())
   INFO("rows_total", P.sn_rows.size()) INFO("ent_fused", h->ent_fused) INFO("ent_split", h->ent_split)
   INFO("rows_fused", h->rows_fused) INFO("rows_split", h->rows_split)
-  INFO("long_row_segments", h->n_rseg) INFO("row_scale_blocks", row_scale_in_sequence(h) ? row_scale_grid(P) : 0)
+  INFO("long_row_segments", h->n_rseg) INFO("row_scale_blocks", row_scale_in_sequence(h) ? h->rs_grid : 0)
   INFO("arena_fill_bytes", arena_fill_bytes(P))
+  INFO("xcd_classes", h->xcd_classes) INFO("dealt_multi_item_fronts", h->dealt_multi) INFO("long_prod_segments", h->n_lprod)
+  INFO("active_bounds", h->maps_on ? h->n_bounds : 0)
   // (hipfact_refactor_device takes the caller's values as the structure's own, entry by entry)
   INFO("values_in_place",
        h->have_plan && (!h->from_jacobian || (virtual_current(h) && h->vj->identity))) INFO("inactive_rows", h->maps_on ? h->n_inactive : 0)

@@ -151,6 +151,24 @@ struct LongProd {
   long long begin, end;  // pairs [begin, end)
   int idx, nseg, uid, poff;
 };
+// Placement by XCD (xcd_place.h): the blocks with blockIdx.x % C == g form class g, which owns [b[g], b[g + 1]) of the
+// launch's entries or rows.  Passed by value.
+constexpr int XCD_CLASSES_MAX = 16;
+struct ClassBounds {
+  long long b[XCD_CLASSES_MAX + 1];
+  int C, pad;
+};
+#ifdef __HIP__
+#define HIPFACT_HD __host__ __device__
+#else
+#define HIPFACT_HD
+#endif
+// the blocks of `rpb` rows that class g of k_row_scale takes: [rb0, rb0 + nrb).  Inner bounds are multiples of rpb or
+// equal to the number of rows, so an empty class behind the last, partial block gets nothing of it.
+HIPFACT_HD inline void class_row_blocks(const ClassBounds& cb, int g, int rpb, int& rb0, int& nrb) {
+  rb0 = (int)((cb.b[g] + rpb - 1) / rpb);
+  nrb = (int)((cb.b[g + 1] + rpb - 1) / rpb) - rb0;
+}
 // ---- the top of the solve tree as ONE dense block (runtime_plan.inc: top block) ----------------------------------
 // The last levels of the tree hold a handful of fronts each and cost the solve ~2.7 us per level and direction in
 // pure hop latency.  For the fronts T of those levels (closed under "parent", nT columns in all) the forward sweep is

@@ -42,6 +42,7 @@
 // the kernels are translation units of their own (kernels_factor.hip, kernels_solve.hip); this one sees their declarations
 #include "kernel_types.h"
 #include "kernels_decl.h"
+#include "xcd_place.h"
 
 #include "runtime_types.inc"
 #include "runtime_plan.inc"

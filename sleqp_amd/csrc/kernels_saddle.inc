@@ -61,6 +61,11 @@
 // masked columns stay out of Ar_val (the right-hand side of the constraint rows: x_d is an unknown of M) and out of
 // the products of S, but their scaled values are what the entries of M between a row and a late variable are
 // multiplied from (Ksc / Kprod keep them) and what the x update x_d = b_d - A_d^T y reads; they count in the row norm.
+// Placement by XCD (xcd_place.h): the blocks of class g = blockIdx.x % C take the 16-row blocks of the rows
+// [RB.b[g], RB.b[g + 1]) in pivot order (equal numbers of entries per class), one block after the other.  Neighbouring
+// rows share columns of K: a class then gathers from its own part of Kval and fills the lines of Ksc it scatters into on
+// its own, where neighbouring blocks (C = 1) spread both over all L2s.  The value copy and the fill store whole lines and
+// stay strided over the whole grid.
 __global__ __launch_bounds__(FB) void k_row_scale(int m, const int* __restrict__ Ar_ptr,
                                                   const int* __restrict__ Ar_col, const int* __restrict__ Ar_src,
                                                   const double* __restrict__ Kval, const int* __restrict__ vmap,
@@ -71,7 +76,8 @@ __global__ __launch_bounds__(FB) void k_row_scale(int m, const int* __restrict__
                                                   double* __restrict__ Kcopy, long long nnzK,
                                                   double2* __restrict__ zero,
                                                   long long nzero, int* __restrict__ info, int nrseg,
-                                                  const LongSeg* __restrict__ rseg, DecideIn D, int decide) {
+                                                  const LongSeg* __restrict__ rseg, DecideIn D, int decide,
+                                                  ClassBounds RB) {
   const int nbw = gridDim.x, bid = blockIdx.x;
   if (bid == 0) {
     // The deferred verdict of the previous factorisation's last solve (a residual kernel has left its partial maxima,
@@ -86,9 +92,13 @@ __global__ __launch_bounds__(FB) void k_row_scale(int m, const int* __restrict__
     for (long long i = bid * (long long)FB + threadIdx.x; i < nnzK; i += (long long)nbw * FB) Kcopy[i] = Kval[i];
   const int sub = threadIdx.x % RL;
   const int rpb = FB / RL;
-  const int iters = (m + nbw * rpb - 1) / (nbw * rpb);
+  const int cls = bid % RB.C, cbid = bid / RB.C, cnb = (nbw - cls + RB.C - 1) / RB.C;  // this block among the cnb of its class
+  int rb0, nrb;  // the class's row blocks
+  class_row_blocks(RB, cls, rpb, rb0, nrb);
+  const int iters = (nrb + cnb - 1) / cnb;
   for (int it = 0; it < iters; ++it) {  // uniform trip count (the shuffles need whole groups)
-    const int k = (it * nbw + bid) * rpb + threadIdx.x / RL;
+    const int crb = it * cnb + cbid;
+    const int k = crb < nrb ? (rb0 + crb) * rpb + threadIdx.x / RL : m;
     double s = 0.0;
     int p0 = 0, p1 = 0;
     constexpr int KEEP = 4;  // rows of up to 64 entries are read once

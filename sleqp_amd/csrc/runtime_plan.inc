@@ -71,6 +71,8 @@ static size_t solve_panel_lds(int wmax) {
 
 static int dense_upload(hipfact_handle* h, size_t vec_bytes);
 
+static void place_front_end(hipfact_handle* h);  // (runtime_queue.inc)
+
 static int upload_plan(hipfact_handle* h) {
   const Plan& P = h->plan;
   const int ns = P.nsuper;
@@ -232,6 +234,7 @@ static int upload_plan(hipfact_handle* h) {
         if ((rc = upload(h, h->d_prod_b, P.prod_b))) return rc;
       }
     }
+    place_front_end(h);
     if ((rc = upload(h, h->d_Ar_ptr, P.Ar_ptr))) return rc;
     if ((rc = upload(h, h->d_Ar_col, P.Ar_col))) return rc;
     if ((rc = upload(h, h->d_Ar_src, P.Ar_src))) return rc;
@@ -258,6 +261,7 @@ static int upload_plan(hipfact_handle* h) {
   }
   // per-level launch metadata
   h->levels.assign(P.nlevels, LevelInfo());
+  h->dealt_multi = 0;
   size_t max_lds = 0;
   std::vector<int> items;
   std::vector<FrontItem> fitems;
@@ -363,14 +367,28 @@ static int upload_plan(hipfact_handle* h) {
         }
         li.panel_threads = (blocks128 < h->panel_small_below) ? 256 : 512;
       }
+      // Placement by XCD (xcd_place.h): the items of a launch, built in the plain order (front by front), go out so
+      // that the items of a front run side by side on one XCD - the inverse of the pivot block a front's panel
+      // items all read, the strips of L21 its Schur tiles share
+      std::vector<FrontItem> plain;
+      std::vector<int> per_front, dealt;
+      auto emit_by_class = [&]() {
+        if (deal_items(per_front, h->xcd_classes, dealt))
+          for (int c : per_front) h->dealt_multi += c > 1;
+        for (int i : dealt) fitems.push_back(plain[(size_t)i]);
+        plain.clear();
+        per_front.clear();
+      };
       const int prow = li.panel_threads / 4;
       for (int s : order) {
         const int u = P.sn_r[s] - (P.sn_c0[s + 1] - P.sn_c0[s]);
+        per_front.push_back((u + prow - 1) / prow);
         for (int b = 0; b < (u + prow - 1) / prow; ++b) {
-          fitems.push_back(item(s, b));
+          plain.push_back(item(s, b));
           ++li.nC;
         }
       }
+      emit_by_class();
       li.itD = (long long)fitems.size();
       // A level with ONE front of thousands of update rows (dense chain): its Schur workgroups share one item and
       // find their tile from the block index (part = -1) - a Schur complement of order 5e4 would otherwise carry
@@ -418,12 +436,14 @@ static int upload_plan(hipfact_handle* h) {
         if (li.compactD) break;
         const int u = P.sn_r[s] - (P.sn_c0[s + 1] - P.sn_c0[s]);
         const int nt = (u + 63) / 64;
+        per_front.push_back(nt * (nt + 1) / 2);
         for (int I = 0; I < nt; ++I)
           for (int J = 0; J <= I; ++J) {
-            fitems.push_back(item(s, (I << 16) | J));
+            plain.push_back(item(s, (I << 16) | J));
             ++li.nD;
           }
       }
+      emit_by_class();
     }
   }
   h->ent_fused = h->ent_split = h->rows_fused = h->rows_split = 0;

@@ -104,10 +104,20 @@ static inline size_t arena_fill_bytes(const Plan& P) {
 // grid of k_row_scale: 16 rows per workgroup, and not fewer workgroups than the arena alone would get (every workgroup
 // stores its share of the fill: a plan with few rows and a dense S would otherwise fill ~m^2 / 2 doubles on m / 16
 // workgroups; workgroups beyond the rows only fill, the row loop's trip count is uniform)
-static inline int row_scale_grid(const Plan& P) {
-  const long long nz16 = (long long)((arena_fill_bytes(P) + 15) / 16);
+static inline int row_scale_grid(long long m, size_t fill_bytes) {
+  const long long nz16 = (long long)((fill_bytes + 15) / 16);
   const int for_fill = (int)std::min<long long>(2048, std::max<long long>(1, nz16 / (FB * 8)));
-  return std::max(nblocks((long long)P.m * 16), for_fill);
+  return std::max(nblocks(m * 16), for_fill);
+}
+// Placement by XCD of the rows of k_row_scale (xcd_place.h), when the plan is uploaded: the class ranges and the grid
+// that goes with them - one 16-row block per workgroup for the largest class, and still no more workgroups than the fill
+// has 16-byte units (every workgroup owns a share of it).
+static int place_rows(int m, const int* Ar_ptr, size_t fill_bytes, int classes, ClassBounds& cb) {
+  return place_ranges((long long)m, FB / RL, Ar_ptr, LONG_ROW, classes, row_scale_grid(m, fill_bytes), (long long)((fill_bytes + 15) / 16), cb);
+}
+static void place_front_end(hipfact_handle* h) {
+  const Plan& P = h->plan;
+  h->rs_grid = place_rows(P.m, P.Ar_ptr.data(), arena_fill_bytes(P), h->xcd_classes, h->rs_place);
 }
 // the Schur items of a level whose pivot blocks and panels are done (CH: a chain level)
 template <bool CH>
@@ -152,14 +162,14 @@ static int factor_enqueue(hipfact_handle* h) {
                h->d_Ar_col.as<int>(), h->d_Ar_src.as<int>(), kin, vmap,
                masked ? h->d_dmask.as<int>() : nullptr, P.n_late > 0 ? 1 : 0, h->equilibrate ? 1 : 0,
                h->d_dscale.as<double>(), h->d_segpart.as<double>(), h->d_segcnt.as<unsigned int>());
-      LAUNCH(PC_GATHER, k_row_scale, dim3(row_scale_grid(P)), dim3(FB), 0, P.m,
+      LAUNCH(PC_GATHER, k_row_scale, dim3(h->rs_grid), dim3(FB), 0, P.m,
              h->d_Ar_ptr.as<int>(), h->d_Ar_col.as<int>(), h->d_Ar_src.as<int>(), kin, vmap,
              masked ? h->d_dmask.as<int>() : nullptr, h->d_perm.as<int>(), P.n_late > 0 ? P.my : -1,
              h->equilibrate ? 1 : 0, h->d_dscale.as<double>(),
              h->d_Ar_val.as<double>(), masked ? h->d_Ar_full.as<double>() : nullptr, h->d_Ksc.as<double>(), kprod,
              h->vals_ride ? h->d_Kval.as<double>() : nullptr, (long long)P.nnzK,
              reinterpret_cast<double2*>(h->d_L.p), nz16, h->d_info.as<int>(), h->n_rseg,
-             h->d_rseg.as<LongSeg>(), decide_in(h), h->decide_rides ? 1 : 0);
+             h->d_rseg.as<LongSeg>(), decide_in(h), h->decide_rides ? 1 : 0, h->rs_place);
     }
   }
   if (nM > 0) {

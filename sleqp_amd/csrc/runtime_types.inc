@@ -246,6 +246,11 @@ struct PlanState : FactorMemo {
   // partial-sum slots and the arrival counters they share (the kernels run one after the other on the stream)
   DevBuf d_rseg, d_cseg, d_lprod, d_segpart, d_segcnt;
   int n_rseg = 0, n_cseg = 0, n_lprod = 0;
+  // placement by XCD (xcd_place.h): the class ranges of k_row_scale (rows in pivot order) and the grid that goes with
+  // them; set when the plan is uploaded
+  ClassBounds rs_place = {};
+  int rs_grid = 1;
+  int dealt_multi = 0;  // fronts of several panel / Schur items in per-level launches whose order the dealing changed (info)
   int n_lrows = 0;     // long rows (their right-hand side is formed by k_rhs_saddle, not inside the tree launch)
   // blocked solve (runtime_multi.inc), MR columns each: the block Y of M Y = T, the update blocks, the residuals, a
   // copy of B for the in-place case; allocated by the first multi solve of the state
@@ -383,6 +388,7 @@ struct hipfact_handle : PlanState, SingleSolveMemo {
   int x_dot_blocks = 0;
   int xupd_blocks = 256;      // workgroups of the x update inside the tree launch (xupd_fused)
   bool solve_sorted = true;   // solve items of a level: biggest fronts first
+  int xcd_classes = 8;        // HIPFACT_XCD_CLASSES (1-16): classes the rows of k_row_scale and the items of the per-level panel / Schur launches are dealt to (1: plain order)
   int factor_top_max = 160;   // levels with at most this many fronts join the single-launch top-of-tree factorisation (0: off)
   int factor_top_levels = 1 << 20;  // at most this many levels in the single-launch top-of-tree factorisation (tests)
   int factor_top_max_u = 1024;  // ... and only levels whose fronts have at most this many update rows
