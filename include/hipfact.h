@@ -400,7 +400,7 @@ int hipfact_tridiag_tr(int k, const double* delta, const double* gamma, double g
  * says otherwise (the parity tests sweep them); analysis options take effect at the next set_matrix / assemble, which
  * re-analyses.  The table is generated from the source: */
 /* BEGIN OPTION TABLE (generated by scripts/gen_option_table.py from sleqp_amd/csrc/abi_options.inc)
- * 50 options; unknown names return HIPFACT_EINVAL.
+ * 47 options; unknown names return HIPFACT_EINVAL.
  *   "refine_steps"
  *       correction passes carried by every solve graph (default 1; 0: plain solve, no residual); they
  *       return at once when the device-side control block reports convergence
@@ -423,15 +423,8 @@ int hipfact_tridiag_tr(int k, const double* delta, const double* gamma, double g
  *       takes effect at the next factorisation
  *   "use_graph"
  *       0: enqueue the launch sequences instead of replaying captured hipGraphs
- *   "top_max_fronts"
- *       0 disables the single-launch top-of-tree solve
  *   "factor_top_max"
  *       0: one launch per phase and level everywhere
- *   "wide_min_rows"
- *       fronts with at least this many update rows are solved by several workgroups in the per-level
- *       solve kernels (default 256; 0: off)
- *   "top_prefetch"
- *       0: the two-launch solve kernels fetch their panels behind the dependency wait (tests)
  *   "pull_max_children"
  *       0: extend-add always through the separate assembly kernel
  *   "debug_fake_timeout"
@@ -480,7 +473,7 @@ int hipfact_tridiag_tr(int k, const double* delta, const double* gamma, double g
  *       solves of one factorisation from which forming the dense top block of the solve tree pays
  *       (default 48)
  *   "solve_fused"
- *       0: the two-launch / per-level solve kernels on the factor panels
+ *       0: the per-level solve kernels on the factor panels
  *   "top_block_after"
  *       the top levels of the solve tree as one dense block from this solve of a factorisation on (0:
  *       never)

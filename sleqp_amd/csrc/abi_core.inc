@@ -40,8 +40,6 @@ int hipfact_create(hipfact_handle** out, int device) {
   if (const char* s = getenv("HIPFACT_REFINE")) h->refine_steps = atoi(s);
   if (const char* s = getenv("HIPFACT_DATAFLOW_RETRY")) h->df_retry_every = std::max(0, atoi(s));
   if (const char* s = getenv("HIPFACT_PULL_MAX")) h->pull_max_children = atoi(s);
-  if (const char* s = getenv("HIPFACT_TOP_PREFETCH")) h->top_prefetch = atoi(s);
-  if (const char* s = getenv("HIPFACT_WIDE_MIN")) h->wide_min_rows = atoi(s);
   if (const char* s = getenv("HIPFACT_FACTOR_TOP")) h->factor_top_max = atoi(s);
   if (const char* s = getenv("HIPFACT_SOLVE_SORTED")) h->solve_sorted = atoi(s) != 0;
   if (const char* s = getenv("HIPFACT_CHAIN_PAIRS")) h->chain_pairs = atoi(s) != 0;
@@ -55,7 +53,6 @@ int hipfact_create(hipfact_handle** out, int device) {
   if (const char* s = getenv("HIPFACT_SOLVE_SLICES")) h->solve_slices = atoi(s) != 0;
   if (const char* s = getenv("HIPFACT_CHAIN_FUSE")) h->chain_fuse = atoi(s) != 0;
   if (const char* s = getenv("HIPFACT_DECIDE_LAZY")) h->decide_lazy = atoi(s) != 0;
-  if (const char* s = getenv("HIPFACT_TOP_MAX")) h->top_max_fronts = atoi(s);
   if (const char* s = getenv("HIPFACT_GRAPH")) h->use_graph = atoi(s) != 0;
   if (const char* s = getenv("HIPFACT_TOP_BLOCK_AFTER")) h->top_block_after = std::max(0, atoi(s));
   if (const char* s = getenv("HIPFACT_BOUNDARY_FAST")) h->boundary_fast = atoi(s) != 0;

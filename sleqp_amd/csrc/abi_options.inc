@@ -47,23 +47,8 @@ int hipfact_set_option(hipfact_handle* h, const char* name, double value) {
     if (!h->use_graph) drop_graphs(h);
     return HIPFACT_OK;
   }
-  if (!strcmp(name, "top_max_fronts")) {  // 0 disables the single-launch top-of-tree solve
-    h->top_max_fronts = (int)value;
-    invalidate_plans(h);
-    return HIPFACT_OK;
-  }
   if (!strcmp(name, "factor_top_max")) {  // 0: one launch per phase and level everywhere
     h->factor_top_max = (int)value;
-    invalidate_plans(h);
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "wide_min_rows")) {  // fronts with at least this many update rows are solved by several workgroups in the per-level solve kernels (default 256; 0: off)
-    h->wide_min_rows = (int)value;
-    invalidate_plans(h);
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "top_prefetch")) {  // 0: the two-launch solve kernels fetch their panels behind the dependency wait (tests)
-    h->top_prefetch = value != 0.0;
     invalidate_plans(h);
     return HIPFACT_OK;
   }
@@ -172,7 +157,7 @@ int hipfact_set_option(hipfact_handle* h, const char* name, double value) {
     h->top_block_breakeven = (int)value;
     return HIPFACT_OK;
   }
-  if (!strcmp(name, "solve_fused")) {  // 0: the two-launch / per-level solve kernels on the factor panels
+  if (!strcmp(name, "solve_fused")) {  // 0: the per-level solve kernels on the factor panels
     h->solve_fused = value != 0.0;
     invalidate_plans(h);
     return HIPFACT_OK;
@@ -413,7 +398,8 @@ int hipfact_get_info(const hipfact_handle* h, const char* name, double* value) {
   INFO("num_passes", h->num_passes) INFO("last_omega", h->last_ctl.omega) INFO("last_iters", h->last_ctl.iters)
   INFO("last_status", h->last_ctl.status) INFO("last_tol", h->last_ctl.tol) INFO("kappa_est", h->last_ctl.kappa)
   INFO("refine_inline", h->refine_inline) INFO("refine_tol", h->refine_tol) INFO("equilibrate", h->equilibrate)
-  INFO("factor_top_level", h->ftop_level) INFO("factor_top_count", h->ftop_count) INFO("top_level", h->top_level) INFO("top_count", h->top_count) INFO("solve_timeouts", h->h_info.p ? h->h_info.as<int>()[INFO_TIMEOUT] : 0)
+  INFO("factor_top_level", h->ftop_level) INFO("factor_top_count", h->ftop_count) INFO("solve_timeouts", h->h_info.p ? h->h_info.as<int>()[INFO_TIMEOUT] : 0)
+  INFO("top_level", 1 << 30)  // the retired two-launch solve route, reported as "off": the benchmark still asks
   INFO("use_graph", h->use_graph) INFO("num_graphs", h->graphs.size()) INFO("max_r", P.max_r) INFO("max_w", P.max_w) INFO("refine_steps", h->refine_steps)
   INFO("schur_flops_max_level", h->schur_flops_max)
   INFO("chain_pairs", h->n_pairs)

@@ -81,26 +81,6 @@ struct TopFItem {
   int wait_head[MAXCH];   // pivot: head workgroups of each child (0: wait for the whole child, wait_cnt)
 };
 
-// one front of the single-launch top-of-tree solve kernels (one uniform load per workgroup)
-struct TopItem {
-  long long Loff, uoff, rowoff;
-  int s, c0, w, r, parent;
-  int nchild;              // -1: more than MAXCH children (generic path through the SnDesc walk)
-  int prefetch;            // bit 0 / 1: the forward / backward step prefetches (buffers fit the LDS)
-  int pad;
-  long long c_uoff[MAXCH];   // children's update vectors
-  long long c_reloff[MAXCH]; // children's relative indices
-  int c_uc[MAXCH];
-  int c_id[MAXCH];
-  int c_wait[MAXCH];         // child is part of the same launch: wait until its flag reaches this count (0: no wait)
-  // wide fronts (thousands of update rows): one "head" workgroup (pivot block) and several "slice"
-  // workgroups (256 update rows each) instead of one workgroup that streams the whole panel
-  int kind;                  // 0 ordinary front, 1 head, 2 slice
-  int a0, a1;                // slice: update rows [a0, a1)
-  int nsl;                   // number of slices of the front
-  long long poff;            // backward: the front's partial sums (nsl x w) in the scratch buffer
-  int c_invoff[MAXCH];       // children's inverse relative indices
-};
 // One front of the fused solve launch (k_solve_tree): everything a workgroup needs in ONE uniform
 // load.  The front's factor is stored twice in "solve panel" form, S = [X; -W] with X = inv(L11)
 // (unit lower) and W = L21 X, so that each sweep is a single product with no dependency between the
@@ -214,10 +194,6 @@ struct TopBlockIn {
   int ltop;  // first level of T (only the children of T's fronts feed the block: they are the ones that wait)
 };
 constexpr int SOLVE_PREFETCH = 32;  // panel entries per thread requested before the dependency wait
-
-constexpr int WIDE_SLICE_ROWS = 256;
-constexpr int TOP_REL_CAP = 2048;   // ints of children's relative indices staged in LDS
-constexpr int TOP_L21_CAP = 16384;  // doubles of L21 (forward) / inv(L11) (backward) staged in LDS
 
 // info words written by the factorisation kernels
 // (INFO_TIMEOUT_WG: 2^30 - the lowest workgroup index of a solve launch whose wait timed out, 0 if none)

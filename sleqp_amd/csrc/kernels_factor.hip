@@ -13,8 +13,8 @@
 // The numeric factorisation and the solves are bound by the critical path of the elimination
 // tree, so the code is organised around dependent memory round trips and issue slots rather
 // than bandwidth: self-contained work items, pull-mode extend-add, prefetch before every
-// dependency wait, and single-launch dataflow kernels (k_factor_top, k_solve_tree; k_fwd_top /
-// k_bwd_top as the fallback) in which workgroups synchronise through counters and posted data
+// dependency wait, and single-launch dataflow kernels (k_factor_top, k_solve_tree; the per-level
+// kernels as the fallback) in which workgroups synchronise through counters and posted data
 // (DESIGN.md sections 2 and 4).
 //
 // One translation unit, split by role (included below in this order):
@@ -22,13 +22,8 @@
 //   kernels_front_pivot.inc   pivot block of a front: blocked LDL^T as free-running waves, posted tiles
 //   kernels_front_update.inc  panel solve, Schur tiles, the per-level kernels
 //   kernels_front_fused.inc   panel solve + Schur tile of a front as one role of the dataflow launch
-//   kernels_solve_level.inc   level-scheduled / one-launch-per-direction solves (fallback)
+//   kernels_solve_panels.inc  k_build_solve_panels: the solve panels of the tree launch, built behind the factorisation
 //   kernels_factor_top.inc    k_factor_top: the upper levels of the factorisation as one dataflow launch
-//   kernels_solve_wide.inc    wide fronts of the fallback solves
-//   kernels_solve_tree.inc    k_solve_tree (the whole solve in one launch), solve panels
-//   kernels_saddle.inc        row scaling, right-hand side, x update, residual, refinement verdict
-//   kernels_vector.inc        Krylov vector kernels, CSR SpMV, fill_aug_jac on the device
-// (dense_cols.inc and krylov_device.inc carry their own kernels next to the host code that launches them.)
 #include <hip/hip_runtime.h>
 
 #include "device_types.h"

@@ -14,17 +14,16 @@
 // The numeric factorisation and the solves are bound by the critical path of the elimination
 // tree, so the code is organised around dependent memory round trips and issue slots rather
 // than bandwidth: self-contained work items, pull-mode extend-add, prefetch before every
-// dependency wait, and single-launch dataflow kernels (k_factor_top, k_solve_tree; k_fwd_top /
-// k_bwd_top as the fallback) in which workgroups synchronise through counters and posted data
+// dependency wait, and single-launch dataflow kernels (k_factor_top, k_solve_tree; the per-level
+// kernels as the fallback) in which workgroups synchronise through counters and posted data
 // (DESIGN.md sections 2 and 4).
 //
 // One translation unit, split by role (included below in this order):
 //   kernels_mvals.inc         product lists -> entries of S = A A^T in the front panels
 //   kernels_front_pivot.inc   pivot block of a front: blocked LDL^T as free-running waves, posted tiles
 //   kernels_front_update.inc  panel solve, Schur tiles, the per-level kernels
-//   kernels_solve_level.inc   level-scheduled / one-launch-per-direction solves (fallback)
+//   kernels_solve_level.inc   level-scheduled solves (fallback)
 //   kernels_factor_top.inc    k_factor_top: the upper levels of the factorisation as one dataflow launch
-//   kernels_solve_wide.inc    wide fronts of the fallback solves
 //   kernels_solve_multi.inc   blocked level-scheduled sweeps: 16 right-hand sides per pass over the factor panels
 //   kernels_solve_tree.inc    k_solve_tree (the whole solve in one launch), solve panels
 //   kernels_saddle.inc        row scaling, right-hand side, x update, residual, refinement verdict
@@ -40,7 +39,6 @@
 namespace hipfact {
 #include "kernels_common.inc"
 #include "kernels_solve_level.inc"
-#include "kernels_solve_wide.inc"
 #include "kernels_solve_multi.inc"
 #include "kernels_solve_tree.inc"
 #include "kernels_saddle.inc"

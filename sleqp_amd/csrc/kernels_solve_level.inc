@@ -1,4 +1,4 @@
-// kernels_solve_level.inc - level-scheduled solves and the one-launch-per-direction sweeps (fallback path of the solve)
+// kernels_solve_level.inc - level-scheduled solves (solve_fused = 0, and every solve after a dataflow timeout)
 // (part of the translation unit kernels_solve.hip; included from there, in this order)
 
 // ---------------------------------------------------------------------------
@@ -109,127 +109,6 @@ __device__ __forceinline__ void dev_fwd_front(const SnDesc& S, const SnDesc* __r
   }
 }
 
-
-__device__ __forceinline__ void top_wait(int* __restrict__ flags, int who, int* __restrict__ info, int target = 1);
-
-
-// Forward step of one front inside the single-launch top-of-tree kernel.  Everything that does
-// not depend on the children is requested BEFORE the wait for their flags: own right-hand side,
-// the children's relative indices (LDS), this thread's fragments of inv(L11) (registers) and L21
-// (LDS).  After the wait only the children's update vectors are one memory round trip away.
-// Same arithmetic, in the same order, as dev_fwd_front.
-__device__ __forceinline__ void dev_fwd_front_top(const TopItem& T, const double* __restrict__ L,
-                                                  const int* __restrict__ inv, double* __restrict__ y,
-                                                  double* __restrict__ uvec, double* lds, int* __restrict__ info) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int w = T.w, r = T.r, u = r - w;
-  const double* __restrict__ P = L + T.Loff;
-  double* f = lds;            // r
-  double* xs = f + r;         // w
-  double* ps = xs + w;        // 8 x w partial sums of the triangular product
-  double* part = ps + 8 * w;  // <= 1024 partial sums of the rectangular product
-  double* Lb = part + 1024 + TOP_REL_CAP / 2;       // u x w, column-major
-  // front row tid (r <= SB): own right-hand side and, per child, which of its update rows lands here
-  double f0 = (tid < w) ? y[T.c0 + tid] : 0.0;
-  int iv[MAXCH];
-#pragma unroll
-  for (int ch = 0; ch < MAXCH; ++ch) iv[ch] = (ch < T.nchild && tid < r) ? inv[T.c_invoff[ch] + tid] : -1;
-  // row k of inv(L11), eighth p of the column range [0, k): at most 16 entries
-  const int xk = tid & 127, xp = tid >> 7;
-  const int xlo = (int)(((long long)xk * xp) >> 3), xhi = (int)(((long long)xk * (xp + 1)) >> 3);
-  double xr[16];
-#pragma unroll
-  for (int j = 0; j < 16; ++j) xr[j] = (xk < w && xlo + j < xhi) ? P[xk + (long long)(xlo + j) * r] : 0.0;
-  for (int k0 = 4 * wave; k0 < w; k0 += 64)
-    for (int a = lane; a < u; a += 64) {
-      double v[4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) v[c] = (k0 + c < w) ? P[w + a + (long long)(k0 + c) * r] : 0.0;
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-        if (k0 + c < w) Lb[a + (k0 + c) * u] = v[c];
-    }
-  // ---- the children's contributions, polled element by element, added in child order
-#pragma unroll
-  for (int ch = 0; ch < MAXCH; ++ch)
-    if (iv[ch] >= 0) f0 += poll_f64(uvec + T.c_uoff[ch] + iv[ch], info);
-  if (tid < r) f[tid] = f0;
-  __syncthreads();
-  if (xk < w) {
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-    const int n = xhi - xlo, n4 = n & ~3;
-#pragma unroll
-    for (int j = 0; j < 16; j += 4)
-      if (j < n4) {
-        s0 += xr[j] * f[xlo + j];
-        s1 += xr[j + 1] * f[xlo + j + 1];
-        s2 += xr[j + 2] * f[xlo + j + 2];
-        s3 += xr[j + 3] * f[xlo + j + 3];
-      }
-#pragma unroll
-    for (int j = 0; j < 16; ++j)
-      if (j >= n4 && j < n) s0 += xr[j] * f[xlo + j];
-    ps[xp * w + xk] = (s0 + s1) + (s2 + s3);
-  }
-  __syncthreads();
-  for (int k = tid; k < w; k += SB) {
-    double s = f[k];
-#pragma unroll
-    for (int p = 0; p < 8; ++p) s += ps[p * w + k];
-    xs[k] = s;
-    y[T.c0 + k] = s;
-  }
-  __syncthreads();
-  if (u > 0) {
-    const int nchunk = (u + 63) >> 6;
-    const int nslice = nchunk >= 16 ? 1 : 16 / nchunk;  // u * w <= TOP_L21_CAP: nchunk < 16 unless w < 17
-    double* __restrict__ us = uvec + T.uoff;
-    if (nslice == 1) {
-      for (int ch = wave; ch < nchunk; ch += 16) {
-        const int a = (ch << 6) + lane;
-        if (a < u) {
-          const double* Lr = Lb + a;
-          double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-          int k = 0;
-          for (; k + 3 < w; k += 4) {
-            s0 += Lr[k * u] * xs[k];
-            s1 += Lr[(k + 1) * u] * xs[k + 1];
-            s2 += Lr[(k + 2) * u] * xs[k + 2];
-            s3 += Lr[(k + 3) * u] * xs[k + 3];
-          }
-          for (; k < w; ++k) s0 += Lr[k * u] * xs[k];
-          post_f64(us + a, f[w + a] - ((s0 + s1) + (s2 + s3)));
-        }
-      }
-    } else {
-      const int ch = wave % nchunk, sl = wave / nchunk;
-      if (sl < nslice) {
-        const int a = (ch << 6) + lane;
-        const int lo = (int)(((long long)w * sl) / nslice), hi = (int)(((long long)w * (sl + 1)) / nslice);
-        double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-        if (a < u) {
-          const double* Lr = Lb + a;
-          int k = lo;
-          for (; k + 3 < hi; k += 4) {
-            s0 += Lr[k * u] * xs[k];
-            s1 += Lr[(k + 1) * u] * xs[k + 1];
-            s2 += Lr[(k + 2) * u] * xs[k + 2];
-            s3 += Lr[(k + 3) * u] * xs[k + 3];
-          }
-          for (; k < hi; ++k) s0 += Lr[k * u] * xs[k];
-        }
-        part[sl * (nchunk << 6) + (ch << 6) + lane] = (s0 + s1) + (s2 + s3);
-      }
-      __syncthreads();
-      for (int a = tid; a < u; a += SB) {
-        double s = 0.0;
-        for (int sl2 = 0; sl2 < nslice; ++sl2) s += part[sl2 * (nchunk << 6) + a];
-        post_f64(us + a, f[w + a] - s);
-      }
-    }
-  }
-}
-
 __global__ __launch_bounds__(SB) void k_fwd_level(const SnDesc* __restrict__ sn, const int* __restrict__ level_sn,
                                                   const double* __restrict__ L, const int* __restrict__ rel,
                                                   const int* __restrict__ child_idx, double* __restrict__ y,
@@ -241,13 +120,9 @@ __global__ __launch_bounds__(SB) void k_fwd_level(const SnDesc* __restrict__ sn,
 }
 
 
-// backward step of one front (lds: u + w doubles).  In the single-launch top-of-tree
-// kernel (flags != nullptr) the wait for the parent happens AFTER the panel
-// fragments have been requested, so their latency overlaps the dependency wait.
+// backward step of one front (lds: u + w doubles)
 __device__ __forceinline__ void dev_bwd_front(const SnDesc& S, const double* __restrict__ L,
-                                              const int* __restrict__ rows, double* __restrict__ y, double* lds,
-                                              int* __restrict__ flags = nullptr, int* __restrict__ info = nullptr,
-                                              double* __restrict__ ysol = nullptr) {
+                                              const int* __restrict__ rows, double* __restrict__ y, double* lds) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int w = S.w, r = S.r, u = r - w;
   const double* __restrict__ P = L + S.Loff;
@@ -269,7 +144,6 @@ __device__ __forceinline__ void dev_bwd_front(const SnDesc& S, const double* __r
         lv[p][c][q] = (pre && k < w && a < u) ? col[w + a] : 0.0;
       }
     }
-  if (flags && S.parent >= 0) top_wait(flags, S.parent, info);  // the parent is done only after all its ancestors
   for (int a = tid; a < u; a += SB) g[a] = y[rw[a]];
   __syncthreads();
   // v_k = z_k / d_k - L21(:,k)^T g
@@ -346,10 +220,7 @@ __device__ __forceinline__ void dev_bwd_front(const SnDesc& S, const double* __r
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         const int k = 4 * (wave + 16 * p) + c;
-        if (k < w) {
-          y[S.c0 + k] = v[k] + s[c];
-          if (ysol) post_f64(ysol + S.c0 + k, v[k] + s[c]);
-        }
+        if (k < w) y[S.c0 + k] = v[k] + s[c];
       }
     }
   }
@@ -362,18 +233,13 @@ __device__ __forceinline__ void dev_bwd_front(const SnDesc& S, const double* __r
 // instructions per wave, and with 16 waves per CU that is microseconds on the critical path).
 //   v = z / d - L21^T g      wave (kb, sp): 16 pivot columns x one slice of the update rows
 //   x = v + strict_lower(inv(L11))^T v
-// Slices are added in a fixed order through LDS.  TOP: part of the single-launch top-of-tree
-// kernel; everything that does not depend on the ancestors (L21 fragments in registers,
-// inv(L11), z / d and the row list in LDS) is requested BEFORE the wait for the parent.
-// lds (doubles): 4 ceil(u/4) | wp + 4 | wp | 256 | ceil(u/2) | TOP: w w
-template <bool TOP>
-__device__ __forceinline__ void dev_bwd_small(long long Loff, long long rowoff, int c0, int w, int r, int parent,
-                                              const double* __restrict__ L, const int* __restrict__ rows,
-                                              double* __restrict__ y, double* lds, double* __restrict__ ysol,
-                                              int* __restrict__ info) {
+// Slices are added in a fixed order through LDS.
+// lds (doubles): 4 ceil(u/4) | wp + 4 | wp | 256 | ceil(u/2)
+__device__ __forceinline__ void dev_bwd_small(const SnDesc& S, const double* __restrict__ L,
+                                              const int* __restrict__ rows, double* __restrict__ y, double* lds) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 15, lk = lane >> 4;
-  const int u = r - w;
+  const int c0 = S.c0, w = S.w, r = S.r, u = r - w;
   const int nbk = (w + 15) >> 4, wp = nbk << 4;
   const int nsplit = 16 / nbk;  // >= 2
   const int kb = wave % nbk, sp = wave / nbk;
@@ -381,41 +247,24 @@ __device__ __forceinline__ void dev_bwd_small(long long Loff, long long rowoff, 
   const int nac = (u + 3) >> 2;  // chunks of 4 update rows, <= 64
   const int c_lo = nac * sp / nsplit, c_hi = nac * (sp + 1) / nsplit;
   const int k = 16 * kb + li;
-  const double* __restrict__ P = L + Loff;
-  const int* __restrict__ rw = rows + rowoff + w;
+  const double* __restrict__ P = L + S.Loff;
+  const int* __restrict__ rw = rows + S.rowoff + w;
   double* g = lds;                // 4 nac
   double* v = g + 4 * nac;        // wp + 4 (zero beyond w)
   double* ypre = v + wp + 4;      // z_k / d_k
   double* part = ypre + wp;       // nsplit x wp <= 256 partial sums
   int* rwb = reinterpret_cast<int*>(part + 256);
-  double* Xb = part + 256 + ((u + 1) >> 1);  // TOP: w x w, zero on and above the diagonal
-  int myrow = -1;  // TOP: update row tid (u <= 256 < SB) is polled by this thread
   for (int a = tid; a < 4 * nac; a += SB) {
-    if (a < u) {
-      if (TOP)
-        myrow = rw[a];
-      else
-        rwb[a] = rw[a];
-    } else {
+    if (a < u)
+      rwb[a] = rw[a];
+    else
       g[a] = 0.0;
-    }
   }
   for (int t = tid; t < wp + 4; t += SB) {
     if (t < w)
       ypre[t] = y[c0 + t] / P[t + (long long)t * r];
     else
       v[t] = 0.0;
-  }
-  if (TOP) {
-    for (int k0 = 4 * wave; k0 < w; k0 += 64)
-      for (int t = lane; t < w; t += 64) {
-        double x[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) x[c] = (k0 + c < w && t > k0 + c) ? P[t + (long long)(k0 + c) * r] : 0.0;
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-          if (k0 + c < w) Xb[t + (k0 + c) * w] = x[c];
-      }
   }
   // (requested last: the staging loops above then run without these 64 registers live)
   double lv[32];
@@ -424,13 +273,8 @@ __device__ __forceinline__ void dev_bwd_small(long long Loff, long long rowoff, 
     const int a = 4 * (c_lo + j) + lk;
     lv[j] = (active && c_lo + j < c_hi && k < w && a < u) ? P[w + a + (long long)k * r] : 0.0;
   }
-  if (TOP) {
-    // the ancestors' solution entries, polled one by one (no flag, no fence: see poll_f64)
-    if (myrow >= 0) g[tid] = poll_f64(ysol + myrow, info);
-  } else {
-    __syncthreads();
-    for (int a = tid; a < u; a += SB) g[a] = y[rwb[a]];
-  }
+  __syncthreads();
+  for (int a = tid; a < u; a += SB) g[a] = y[rwb[a]];
   __syncthreads();
   if (active) {
     d4_t acc = {0.0, 0.0, 0.0, 0.0};
@@ -447,12 +291,10 @@ __device__ __forceinline__ void dev_bwd_small(long long Loff, long long rowoff, 
   const int cnt = ntc - 4 * kb;
   const int t_lo = 4 * kb + cnt * sp / nsplit, t_hi = 4 * kb + cnt * (sp + 1) / nsplit;
   double xf[16];
-  if (!TOP) {
 #pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const int t = 4 * (t_lo + j) + lk;
-      xf[j] = (active && t_lo + j < t_hi && k < w && t < w && t > k) ? P[t + (long long)k * r] : 0.0;
-    }
+  for (int j = 0; j < 16; ++j) {
+    const int t = 4 * (t_lo + j) + lk;
+    xf[j] = (active && t_lo + j < t_hi && k < w && t < w && t > k) ? P[t + (long long)k * r] : 0.0;
   }
   __syncthreads();
   for (int t = tid; t < w; t += SB) {
@@ -467,8 +309,7 @@ __device__ __forceinline__ void dev_bwd_small(long long Loff, long long rowoff, 
     for (int j = 0; j < 16; ++j)
       if (t_lo + j < t_hi) {
         const int t = 4 * (t_lo + j) + lk;
-        const double xa = TOP ? ((k < w && t < w) ? Xb[t + k * w] : 0.0) : xf[j];
-        acc = MFMA_F64(xa, v[t], acc);
+        acc = MFMA_F64(xf[j], v[t], acc);
       }
     if (li == 0) {
 #pragma unroll
@@ -480,7 +321,6 @@ __device__ __forceinline__ void dev_bwd_small(long long Loff, long long rowoff, 
     double s = 0.0;
     for (int q = 0; q < nsplit; ++q) s += part[q * wp + t];
     y[c0 + t] = v[t] + s;
-    if (TOP) post_f64(ysol + c0 + t, v[t] + s);
   }
 }
 
@@ -491,55 +331,7 @@ __global__ __launch_bounds__(SB) void k_bwd_level(const SnDesc* __restrict__ sn,
   if (skip && *skip) return;
   const SnDesc S = sn[level_sn[blockIdx.x]];
   if (S.r - S.w <= 256)
-    dev_bwd_small<false>(S.Loff, S.rowoff, S.c0, S.w, S.r, S.parent, L, rows, y, lds, nullptr, nullptr);
+    dev_bwd_small(S, L, rows, y, lds);
   else
     dev_bwd_front(S, L, rows, y, lds);
-}
-
-// ---------------------------------------------------------------------------
-// The elimination tree of the solve in ONE launch per direction: every front gets its own
-// workgroup, indexed so that a front never waits for one dispatched after it (workgroups are
-// dispatched in index order, so progress needs no co-residency).  Ordinary fronts exchange their
-// vectors element by element (poll_f64 / post_f64: the data is its own flag).  Wide and generic
-// fronts use one done-flag per front:
-//   producer: all waves drain their stores, block barrier, one lane issues an
-//             agent-scope release and then a relaxed agent-scope flag store;
-//   consumer: one lane polls the flag (relaxed, agent scope, bounded spin), then
-//             an agent-scope acquire, block barrier, plain loads.
-// The flags of one sweep are cleared by the kernel of the other.  A spin that runs out
-// sets INFO_TIMEOUT instead of hanging the GPU.
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ void top_wait(int* __restrict__ flags, int who, int* __restrict__ info, int target) {
-  if (threadIdx.x == 0) {
-    int spins = 0;
-    while (__hip_atomic_load(&flags[who], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-      __builtin_amdgcn_s_sleep(2);
-      if (++spins > (1 << 22)) {
-        atomicAdd(&info[INFO_TIMEOUT], 1);
-        break;
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
-  __syncthreads();
-}
-
-__device__ __forceinline__ void top_publish_add(int* __restrict__ flags, int who) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __hip_atomic_fetch_add(&flags[who], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-__device__ __forceinline__ void top_publish(int* __restrict__ flags, int who) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __hip_atomic_store(&flags[who], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
 }

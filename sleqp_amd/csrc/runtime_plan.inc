@@ -822,105 +822,6 @@ static int upload_plan(hipfact_handle* h) {
     }
   }
   {
-    // levels merged into the single-launch top-of-tree solve: as many of the last levels as fit
-    // the co-residency cap, and only if that saves at least two launches
-    int lvl = P.nlevels, total = 0;
-    while (lvl > 0 && total + h->levels[lvl - 1].count <= h->top_max_fronts) total += h->levels[--lvl].count;
-    h->top_level = 1 << 30;
-    h->top_count = 0;
-    if (P.nlevels - lvl >= 3 && h->top_max_fronts > 0) {
-      h->top_level = lvl;
-      h->top_count = total;
-      std::vector<int> top;
-      std::vector<TopItem> titems;
-      h->top_lds_fwd = h->top_lds_bwd = 0;
-      // wide fronts: a head and slices of WIDE_SLICE_ROWS update rows; the flag of such a front
-      // counts its slices in the forward pass
-      std::vector<int> ftarget(ns, 1);
-      auto wide_slices = [&](int s) {
-        const long long u = sn[s].r - sn[s].w;
-        const int nch = sn[s].child_end - sn[s].child_begin;
-        return (h->wide_min_rows > 0 && u >= h->wide_min_rows && nch <= MAXCH)
-                   ? (int)((u + WIDE_SLICE_ROWS - 1) / WIDE_SLICE_ROWS)
-                   : 0;
-      };
-      for (int l = lvl; l < P.nlevels; ++l)
-        for (int q = P.level_ptr[l]; q < P.level_ptr[l + 1]; ++q) {
-          const int nsl = wide_slices(P.level_sn[q]);
-          if (nsl > 0) ftarget[P.level_sn[q]] = nsl;
-        }
-      long long wpart_size = 0;
-      for (int l = lvl; l < P.nlevels; ++l) {
-        for (int q = P.level_ptr[l]; q < P.level_ptr[l + 1]; ++q) {
-          const int s = P.level_sn[q];
-          top.push_back(s);
-          TopItem T;
-          memset(&T, 0, sizeof(T));
-          T.Loff = sn[s].Loff;
-          T.uoff = sn[s].uoff;
-          T.rowoff = sn[s].rowoff;
-          T.s = s;
-          T.c0 = sn[s].c0;
-          T.w = sn[s].w;
-          T.r = sn[s].r;
-          T.parent = sn[s].parent;
-          const int nch = sn[s].child_end - sn[s].child_begin;
-          const long long u = T.r - T.w;
-          T.nchild = nch <= MAXCH ? nch : -1;
-          for (int k = 0; k < nch && nch <= MAXCH; ++k) {
-            const int ch = P.child_idx[sn[s].child_begin + k];
-            T.c_uoff[k] = sn[ch].uoff;
-            T.c_reloff[k] = sn[ch].reloff;
-            T.c_uc[k] = sn[ch].r - sn[ch].w;
-            T.c_id[k] = ch;
-            T.c_invoff[k] = sn[ch].pad1;
-            T.c_wait[k] = P.sn_level[ch] >= lvl ? ftarget[ch] : 0;
-          }
-          size_t lf = h->levels[l].lds_fwd, lb = h->levels[l].lds_bwd;
-          if (h->top_prefetch && T.nchild >= 0 && T.r <= 1024 && u * T.w <= TOP_L21_CAP) {  // one front row per thread
-            T.prefetch |= 1;
-            lf = ((size_t)T.r + 9 * (size_t)T.w + 1024 + TOP_REL_CAP / 2 + (size_t)(u * T.w) + 2) * sizeof(double);
-          }
-          if (u <= 256) {  // same arithmetic as the level kernels' small-front path
-            T.prefetch |= 2;
-            const size_t wp16 = (size_t)((T.w + 15) & ~15);
-            lb = ((size_t)u + 4 + 2 * wp16 + 4 + 256 + (size_t)((u + 1) / 2) + (size_t)T.w * T.w + 2) * sizeof(double);
-          }
-          const int nsl = wide_slices(s);
-          if (nsl > 0) {
-            T.prefetch = 0;
-            T.kind = 1;
-            T.nsl = nsl;
-            T.poff = wpart_size;
-            wpart_size += (long long)nsl * T.w;
-            lf = lb = ((size_t)10 * T.w + WIDE_SLICE_ROWS + 1024 + 2 + (size_t)nsl * T.w) * sizeof(double);
-            titems.push_back(T);
-            for (int q2 = 0; q2 < nsl; ++q2) {
-              TopItem S2 = T;
-              S2.kind = 2;
-              S2.a0 = q2 * WIDE_SLICE_ROWS;
-              S2.a1 = (int)std::min<long long>(u, (long long)(q2 + 1) * WIDE_SLICE_ROWS);
-              titems.push_back(S2);
-            }
-          } else {
-            titems.push_back(T);
-          }
-          h->top_lds_fwd = std::max(h->top_lds_fwd, lf);
-          h->top_lds_bwd = std::max(h->top_lds_bwd, lb);
-        }
-      }
-      h->top_count = (int)titems.size();
-      if ((rc = upload(h, h->d_ftarget, ftarget))) return rc;
-      HCHECK(h, h->d_wpart.ensure(std::max<size_t>((size_t)wpart_size * sizeof(double), 16)));
-      // (polled by the heads of the sliced fronts: sentinel between solves)
-      HCHECK(h, hipMemsetAsync(h->d_wpart.p, 0xFF, std::max<size_t>((size_t)wpart_size * sizeof(double), 16), h->stream));
-      if ((rc = upload(h, h->d_top_sn, top))) return rc;
-      if ((rc = upload(h, h->d_titems, titems))) return rc;
-    }
-    HCHECK(h, h->d_flags.ensure(std::max<size_t>((size_t)4 * ns * sizeof(int), 16)));
-    HCHECK(h, hipMemsetAsync(h->d_flags.p, 0, (size_t)4 * ns * sizeof(int), h->stream));
-  }
-  {
     // fused solve launch: every front (or row slice of a big front) as a SolveItem, children before parents
     h->fused_solve = false;
     h->n_sitems = 0;
@@ -1148,15 +1049,11 @@ static int upload_plan(hipfact_handle* h) {
     }
   }
   // Capacity limits of the LDS-resident working sets (documented in INTEGRATION.md).  Only what can actually
-  // run is checked: the per-level solve kernels below the single-launch top (whose wide fronts are sliced and
-  // need no front-sized buffer), the top kernels' own requirements, and the scatter assembly.
+  // run is checked: the per-level solve kernels where the caller chose them, and the scatter assembly.
   {
     size_t solve_lds = 0, asm_lds = 0;
-    if (!h->fused_solve) {
-      const int ltop = std::min(h->top_level, P.nlevels);
-      for (int l = 0; l < ltop; ++l) solve_lds = std::max(solve_lds, h->levels[l].lds_solve_max);
-      if (ltop < P.nlevels) solve_lds = std::max({solve_lds, h->top_lds_fwd, h->top_lds_bwd});
-    }
+    if (!h->fused_solve)
+      for (int l = 0; l < P.nlevels; ++l) solve_lds = std::max(solve_lds, h->levels[l].lds_solve_max);
     // (the scatter assembly only runs on levels that do not pull their extend-add; its buffer holds the relative
     //  indices of the largest child - a pulled front with a 47 000-row child needs no such buffer)
     for (int l = 0; l < P.nlevels; ++l)
@@ -1180,9 +1077,7 @@ static int upload_plan(hipfact_handle* h) {
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   for (const void* fn : {reinterpret_cast<const void*>(k_front_pivot<false>), reinterpret_cast<const void*>(k_front_pivot<true>),
                          reinterpret_cast<const void*>(k_front_panel<false>), reinterpret_cast<const void*>(k_front_panel<true>),
-                         reinterpret_cast<const void*>(k_front_schur<false>), reinterpret_cast<const void*>(k_front_schur<true>), reinterpret_cast<const void*>(k_front_schur_pair), reinterpret_cast<const void*>(k_factor_top),
-                         reinterpret_cast<const void*>(k_fwd_top),
-                         reinterpret_cast<const void*>(k_bwd_top)})
+                         reinterpret_cast<const void*>(k_front_schur<false>), reinterpret_cast<const void*>(k_front_schur<true>), reinterpret_cast<const void*>(k_front_schur_pair), reinterpret_cast<const void*>(k_factor_top)})
     HCHECK(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   HCHECK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_factor_level),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));

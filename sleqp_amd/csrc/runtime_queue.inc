@@ -369,11 +369,9 @@ static int reset_dataflow_state(hipfact_handle* h) {
   if (h->d_uvec.p) HCHECK(h, hipMemsetAsync(h->d_uvec.p, 0xFF, std::max<size_t>((size_t)P.u_size * sizeof(double), 16), st));
   if (h->d_ysol.p) HCHECK(h, hipMemsetAsync(h->d_ysol.p, 0xFF, std::max<size_t>((size_t)2 * P.m * sizeof(double), 16), st));
   if (h->d_xhat.p) HCHECK(h, hipMemsetAsync(h->d_xhat.p, 0xFF, std::max<size_t>((size_t)P.m * sizeof(double), 16), st));
-  if (h->d_wpart.p) HCHECK(h, hipMemsetAsync(h->d_wpart.p, 0xFF, h->d_wpart.bytes, st));
   if (h->d_spart.p) HCHECK(h, hipMemsetAsync(h->d_spart.p, 0xFF, h->d_spart.bytes, st));
   if (h->d_tb_xhat.p) HCHECK(h, hipMemsetAsync(h->d_tb_xhat.p, 0xFF, h->d_tb_xhat.bytes, st));
   if (h->d_tb_gathered.p) HCHECK(h, hipMemsetAsync(h->d_tb_gathered.p, 0, 16, st));
-  if (h->d_flags.p) HCHECK(h, hipMemsetAsync(h->d_flags.p, 0, (size_t)4 * P.nsuper * sizeof(int), st));
   if (h->d_epoch.p) HCHECK(h, hipMemsetAsync(h->d_epoch.p, 0, 16, st));  // (parity and the count of its readers)
   HCHECK(h, hipMemsetAsync(h->d_info.p, 0, INFO_BYTES, st));
   HCHECK(h, hipMemsetAsync(h->d_ctl.p, 0, sizeof(RefineCtl), st));
@@ -545,27 +543,13 @@ static void solve_m_async(hipfact_handle* h, const int* skip, const RhsIn* rhs =
            decide_in(h), h->d_spart.as<double>(), X);
     return;
   }
-  const int ltop = h->no_dataflow ? P.nlevels : std::min(h->top_level, P.nlevels);
-  for (int l = 0; l < ltop; ++l) {
+  for (int l = 0; l < P.nlevels; ++l) {
     const LevelInfo& li = h->levels[l];
     LAUNCH(PC_FWD, k_fwd_level, dim3(li.count), dim3(SB), li.lds_fwd, h->d_sn.as<SnDesc>(),
            h->d_level_sn.as<int>() + li.begin, h->d_L.as<double>(), h->d_rel.as<int>(), h->d_child.as<int>(),
            h->d_y.as<double>(), h->d_uvec.as<double>(), skip);
   }
-  if (ltop < P.nlevels) {
-    // two flag sets, one per sweep; each kernel clears the other one's (zero after upload_plan)
-    int* ffl = h->d_flags.as<int>();
-    int* bfl = ffl + 2 * P.nsuper;
-    LAUNCH(PC_FWD, k_fwd_top, dim3(h->top_count), dim3(SB), h->top_lds_fwd, h->d_sn.as<SnDesc>(),
-           h->d_titems.as<TopItem>(), ltop, h->d_L.as<double>(), h->d_rel.as<int>(), h->d_child.as<int>(),
-           h->d_inv.as<int>(), h->d_ftarget.as<int>(), h->d_y.as<double>(), h->d_uvec.as<double>(),
-           ffl, ffl + P.nsuper, h->d_info.as<int>(), bfl, 2 * P.nsuper, h->d_ysol.as<double>(), skip);
-    LAUNCH(PC_BWD, k_bwd_top, dim3(h->top_count), dim3(SB), h->top_lds_bwd, h->d_sn.as<SnDesc>(),
-           h->d_titems.as<TopItem>(), h->d_L.as<double>(), h->d_rows.as<int>(), h->d_y.as<double>(),
-           h->d_wpart.as<double>(), bfl, bfl + P.nsuper, h->d_info.as<int>(), ffl, 2 * P.nsuper,
-           h->d_ysol.as<double>(), h->d_uvec.as<double>(), skip);
-  }
-  for (int l = ltop - 1; l >= 0; --l) {
+  for (int l = P.nlevels - 1; l >= 0; --l) {
     const LevelInfo& li = h->levels[l];
     LAUNCH(PC_BWD, k_bwd_level, dim3(li.count), dim3(SB), li.lds_bwd, h->d_sn.as<SnDesc>(),
            h->d_level_sn.as<int>() + li.begin, h->d_L.as<double>(), h->d_rows.as<int>(), h->d_y.as<double>(), skip);

@@ -212,12 +212,9 @@ struct PlanState : FactorMemo {
   size_t mini_x_bytes = 0;   // ... and how many bytes: back to the sentinel with every factorisation
   double ent_fused = 0, ent_split = 0, rows_fused = 0, rows_split = 0;  // L entries / row indices per kernel family
   std::vector<LevelInfo> levels;
-  // top of the tree solved in one launch per direction (levels >= top_level)
-  int top_level = 1 << 30, top_count = 0;
-  size_t top_lds_fwd = 0, top_lds_bwd = 0;
   // plan on device
   DevBuf d_sn, d_level_sn, d_rows, d_rel, d_child, d_Mtarget, d_prod_ptr, d_prod_a, d_prod_b, d_src;
-  DevBuf d_items, d_fitems, d_top_sn, d_titems, d_flags, d_inv, d_tfitems, d_ftarget, d_wpart, d_pullx;
+  DevBuf d_items, d_fitems, d_inv, d_tfitems, d_pullx;
   DevBuf d_perm, d_Ar_ptr, d_Ar_col, d_Ar_src, d_Ar_val, d_Kp, d_Ki, d_Kc_y, d_Tp, d_Ti, d_Tsrc;
   // numeric
   DevBuf d_xarena;  // posted pivot blocks of the single-launch factorisation (polled by its panel workgroups)
@@ -403,11 +400,8 @@ struct hipfact_handle : PlanState, SingleSolveMemo {
   int factor_top_fused32 = 12;  // ... with 32-row strips (one computing wave per SIMD, half the rows to gather) on levels of at most this many fronts
   int factor_top_fused_u = 256;  // ... if every front of the level has at most this many update rows (64-row strips, T (T + 1) / 2 items)
   int factor_top_post = 64;   // levels with at most this many fronts post the pivot block to polling panel workgroups
-  int wide_min_rows = 256;    // fronts with at least this many update rows are solved by several workgroups (0: off; one workgroup streams a panel at ~50 GB/s)
-  int top_prefetch = 1;       // top-of-tree solve kernels prefetch their panels before the dependency wait
   int panel_small_below = 0;  // levels with fewer 128-row panel blocks use 64-row blocks
   int pull_max_children = 4;  // 0: always the separate assembly kernel; otherwise pull for any number of children
-  int top_max_fronts = 1024;
   long cache_hits = 0, analyses = 0, num_factor = 0;
   int info_host[INFO_WORDS] = {0, 0, 0, 0};
   Prof prof;

@@ -1172,10 +1172,10 @@ def test_single_launch_top_of_tree_factorisation_agrees(fact):
     assert scaled_residual(K, outs[0], b) <= 1e-9
 
 
-def test_wide_fronts_solved_by_several_workgroups(fact):
-    """Fronts with many update rows are split into a head and row slices in the single-launch
-    solves (dense Schur complements, BASELINE configs[2] family): against the one-workgroup
-    path and the residual."""
+def test_tall_fronts_as_row_slices_of_the_tree_launch_agree_with_the_per_level_solve(fact):
+    """Fronts with many update rows (dense Schur complements, BASELINE configs[2] family) are one workgroup each
+    in the per-level solve kernels and several row-sliced items in the tree launch: the latter against the
+    former and the residual."""
     from sleqp_amd.sparse import SleqpMat
 
     n, m = 3000, 1500
@@ -1185,18 +1185,15 @@ def test_wide_fronts_solved_by_several_workgroups(fact):
     K = synth.kkt_full_matrix(N, kc, kr, kd)
     b = np.random.default_rng(4).standard_normal(N)
     fact.set_option("refine_steps", 0)
-    fact.set_option("solve_fused", 0)  # the head / slice workgroups belong to the two-launch kernels
-    outs = []
-    for wide in (0, 300):
-        fact.set_option("wide_min_rows", wide)
-        fact.set_matrix(SleqpMat(N, N, kc, kr, kd))
-        assert fact.info("max_r") >= 700  # the Schur complement of this family is (nearly) dense
-        for _ in range(2):
-            fact.solve(b)
-        outs.append(fact.solution_raw(0, N))
-        assert fact.info("solve_timeouts") == 0
-        assert scaled_residual(K, outs[-1], b) <= 1e-10
-    assert rel_err(outs[1], outs[0]) <= 1e-10
+    fact.set_option("solve_fused", 0)  # the reference: the per-level kernels, one workgroup per front
+    fact.set_matrix(SleqpMat(N, N, kc, kr, kd))
+    assert fact.info("fused_solve") == 0
+    assert fact.info("max_r") >= 700  # the Schur complement of this family is (nearly) dense
+    for _ in range(2):
+        fact.solve(b)
+    outs = [fact.solution_raw(0, N)]
+    assert fact.info("solve_timeouts") == 0
+    assert scaled_residual(K, outs[0], b) <= 1e-10
     # in the fused launch a front of more than 1024 rows is several items (row slices with their own copies of
     # their rows of the solve panel; the backward items of the slices post partial sums that slice 0 adds up):
     # repeated solves and a refactorisation in between (the polled slots must all be back at the sentinel)
@@ -1214,9 +1211,9 @@ def test_wide_fronts_solved_by_several_workgroups(fact):
         assert scaled_residual(K, fact.solution_raw(0, N), b2) <= 1e-10
 
 
-def test_top_of_tree_solve_variants_agree_bitwise(fact):
-    """Level-by-level solve launches, the single-launch top-of-tree kernels, and their
-    panel-prefetching variant run the same arithmetic in the same order: identical bits."""
+def test_per_level_solve_is_deterministic_and_the_tree_launch_agrees_to_rounding(fact):
+    """The level-by-level solve launches give identical bits on successive factorisations of the same
+    matrix; the tree launch, on another form of the factor, agrees with them to rounding."""
     from sleqp_amd.sparse import SleqpMat
 
     J, vi, ci, _ = _problem(20000, 10000, "b", 0.0, 12)
@@ -1225,14 +1222,12 @@ def test_top_of_tree_solve_variants_agree_bitwise(fact):
     fact.set_option("refine_steps", 0)
     fact.set_option("solve_fused", 0)
     outs = []
-    for top_max, prefetch in ((0, 0), (256, 0), (1024, 1)):
-        fact.set_option("top_max_fronts", top_max)
-        fact.set_option("top_prefetch", prefetch)
+    for _ in range(2):
         fact.set_matrix(SleqpMat(N, N, kc, kr, kd))
+        assert fact.info("fused_solve") == 0
         fact.solve(b)
         outs.append(fact.solution_raw(0, N))
-        assert (fact.info("top_level") < fact.info("nlevels")) == (top_max > 0)
-    assert np.array_equal(outs[0], outs[1]) and np.array_equal(outs[0], outs[2])
+    assert np.array_equal(outs[0], outs[1])
     K = synth.kkt_full_matrix(N, kc, kr, kd)
     assert scaled_residual(K, outs[0], b) <= 1e-9
     # the fused forward + backward launch works on another form of the factor ([X; -L21 X] instead of
@@ -1571,10 +1566,9 @@ def test_residual_checked_on_every_kth_solve_only(fact):
 
 def test_dense_chain_levels_as_small_dataflow_launches(fact):
     """Single-front levels of a dense chain below the top-of-tree launch run their pivot and panel items as ONE
-    small dataflow launch (panel workgroups following the posted pivot block) instead of two launches; the sliced
-    fronts of the two-launch solves exchange posted data instead of flags.  Agreement with the per-level kernels to
-    rounding (substitution against the posted L11 / product with inv(L11)), bitwise reproducible over repeated
-    factorisations (the posted slots are refilled with the sentinel each time)."""
+    small dataflow launch (panel workgroups following the posted pivot block) instead of two launches.  Agreement with
+    the per-level kernels to rounding (substitution against the posted L11 / product with inv(L11)), bitwise
+    reproducible over repeated factorisations (the posted slots are refilled with the sentinel each time)."""
     fact.set_option("top_block_breakeven", 0)  # (bits are compared ACROSS factorisations: the top block forms at the same solve in each)
     from sleqp_amd.sparse import SleqpMat
 
@@ -1725,16 +1719,13 @@ def test_top_block_forms_when_it_pays(fact):
 
 
 def test_solve_sequence_with_changing_right_hand_sides(fact):
-    """The single-launch solve sweeps exchange vectors element by element through slots that the
-    opposite sweep puts back to a sentinel.  A slot that was not put back would hand a value of
-    the PREVIOUS solve to the next one: a sequence of different right-hand sides (mixed front
-    kinds: prefetching, generic and wide fronts, levels below the launch) against the
-    level-by-level path (bit for bit, except that wide fronts sum their slices in another order),
-    with a refactorisation in between."""
+    """The tree launch exchanges vectors element by element through slots that the opposite sweep
+    puts back to a sentinel.  A slot that was not put back would hand a value of the PREVIOUS solve
+    to the next one: a sequence of different right-hand sides (a multi-level tree and a dense
+    chain of tall fronts) against the level-by-level path, with a refactorisation in between."""
     from sleqp_amd.sparse import SleqpMat
 
-    cases = [("b", 20000, 10000, {}), ("u", 3000, 1500, {"wide_min_rows": 300}), ("b", 20000, 10000, {"top_max_fronts": 200})]
-    for kind, n, m, opts in cases:
+    for kind, n, m in [("b", 20000, 10000), ("u", 3000, 1500)]:
         J, vi, ci, _ = _problem(n, m, kind, 0.0, 5)
         N, kc, kr, kd = oracle.fill_aug_jac(n, m, J.indptr, J.indices, J.data, vi, ci)
         K = synth.kkt_full_matrix(N, kc, kr, kd)
@@ -1743,23 +1734,16 @@ def test_solve_sequence_with_changing_right_hand_sides(fact):
         rhs.insert(2, np.zeros(N))
         fact.set_option("refine_steps", 0)
         fact.set_option("solve_fused", 0)
-        outs = {}
-        for top_max in (0, opts.get("top_max_fronts", 1024)):
-            fact.set_option("top_max_fronts", top_max)
-            fact.set_option("wide_min_rows", opts.get("wide_min_rows", 1024))
-            fact.set_matrix(SleqpMat(N, N, kc, kr, kd))
-            res = []
-            for i, b in enumerate(rhs):
-                if i == 3:
-                    fact.set_matrix(SleqpMat(N, N, kc, kr, kd))  # numeric refactorisation in the middle
-                fact.solve(b)
-                res.append(fact.solution_raw(0, N))
-                assert fact.info("solve_timeouts") == 0
-                assert scaled_residual(K, res[-1], b) <= 1e-9
-            outs[top_max] = res
-        a, c = outs.values()
-        for x, y in zip(a, c):
-            assert np.array_equal(x, y) if "wide_min_rows" not in opts else rel_err(x, y) <= 1e-10
+        fact.set_matrix(SleqpMat(N, N, kc, kr, kd))
+        assert fact.info("fused_solve") == 0
+        a = []
+        for i, b in enumerate(rhs):
+            if i == 3:
+                fact.set_matrix(SleqpMat(N, N, kc, kr, kd))  # numeric refactorisation in the middle
+            fact.solve(b)
+            a.append(fact.solution_raw(0, N))
+            assert fact.info("solve_timeouts") == 0
+            assert scaled_residual(K, a[-1], b) <= 1e-9
         # the same sequence through the fused launch (three kinds of sentinel slots: update vectors, x^, ysol)
         fact.set_option("solve_fused", 1)
         fact.set_matrix(SleqpMat(N, N, kc, kr, kd))
@@ -1771,8 +1755,6 @@ def test_solve_sequence_with_changing_right_hand_sides(fact):
             z = fact.solution_raw(0, N)
             assert fact.info("solve_timeouts") == 0
             assert rel_err(z, a[i]) <= 1e-10 and scaled_residual(K, z, b) <= 1e-9
-    fact.set_option("top_max_fronts", 1024)
-    fact.set_option("wide_min_rows", 1024)
 
 
 def test_non_finite_right_hand_side_does_not_stall_the_sweeps(fact):
