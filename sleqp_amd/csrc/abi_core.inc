@@ -615,9 +615,11 @@ int hipfact_condition(hipfact_handle* h, double* condition) {
     *condition = 1.0;
     return HIPFACT_OK;
   }
-  // min / max |d| were left behind the info words by the factorisation
+  // min / max |d| over EVERY pivot were left behind the info words by the factorisation (words 2 and 3; words 0 and 1,
+  // what the refinement tolerance is taken from, cover the positive pivots only: they leave out the pivots of late
+  // variables and the negative ones of a quasi-definite K)
   unsigned long long* hm = reinterpret_cast<unsigned long long*>(h->h_info.as<char>() + INFO_WORDS * sizeof(int));
-  HCHECK(h, hipMemcpyAsync(hm, minmax_ptr(h), 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+  HCHECK(h, hipMemcpyAsync(hm, minmax_ptr(h) + 2, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
   HCHECK(h, hipStreamSynchronize(h->stream));
   const unsigned long long nlo = ~hm[0];
   double lo, hi;

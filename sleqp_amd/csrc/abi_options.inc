@@ -263,6 +263,8 @@ int hipfact_debug_copy(hipfact_handle* h, const char* name, void* out, size_t by
   if (!strcmp(name, "sn_rows")) return host_copy(P.sn_rows);
   if (!strcmp(name, "sn_Loff")) return host_copy(P.sn_Loff);
   if (!strcmp(name, "late_cols")) return host_copy(P.late_cols);
+  if (!strcmp(name, "sn_level")) return host_copy(P.sn_level);
+  if (!strcmp(name, "dense_cols")) return host_copy(P.dense_cols);
   const DevBuf* b = nullptr;
   if (!strcmp(name, "L")) b = &h->d_L;
   else if (!strcmp(name, "U")) b = &h->d_U;
@@ -275,6 +277,7 @@ int hipfact_debug_copy(hipfact_handle* h, const char* name, void* out, size_t by
   else if (!strcmp(name, "uvec")) b = &h->d_uvec;
   else if (!strcmp(name, "dscale")) b = &h->d_dscale;
   else if (!strcmp(name, "Kval")) b = &h->d_Kval;
+  else if (!strcmp(name, "mY")) b = &h->d_mY;  // the last block of the blocked solve: m x MR, pivot order
   if (!b || !b->p || bytes > b->bytes) {
     h->error = "hipfact_debug_copy: unknown buffer or size";
     return HIPFACT_EINVAL;
@@ -404,6 +407,10 @@ int hipfact_get_info(const hipfact_handle* h, const char* name, double* value) {
   INFO("schur_flops_max_level", h->schur_flops_max)
   INFO("chain_pairs", h->n_pairs)
   INFO("xupd_fused", h->xupd_fused ? 1 : 0)
+  // what tells the solve routes apart (tests): what the last queued solve launched (solve_once_async), and what the
+  // plan did with the solve items - the fronts cut into row slices, the levels whose items are not in plan order
+  INFO("rhs_in_tree", h->last_rhs_in_tree) INFO("xupd_in_tree", h->last_xupd_in_tree) INFO("xupd_blocks_launched", h->last_xupd_blocks)
+  INFO("solve_sliced_fronts", h->n_sliced) INFO("solve_resorted_levels", h->n_resorted) INFO("tree_solve", tree_solve(h))
   INFO("refine_check_every", h->refine_check_every) INFO("refine_check_interval", h->check_interval_now) INFO("num_checked", h->num_checked)
   INFO("device", h->device) INFO("nnzM", P.Mi.size()) INFO("nnzA", P.Ar_src.size())
   INFO("rows_total", P.sn_rows.size()) INFO("ent_fused", h->ent_fused) INFO("ent_split", h->ent_split)

@@ -198,7 +198,8 @@ constexpr int SOLVE_PREFETCH = 32;  // panel entries per thread requested before
 // info words written by the factorisation kernels
 // (INFO_TIMEOUT_WG: 2^30 - the lowest workgroup index of a solve launch whose wait timed out, 0 if none)
 enum { INFO_ZERO_PIVOT = 0, INFO_NEG_PIVOT = 1, INFO_TIMEOUT = 2, INFO_TIMEOUT_WG = 3, INFO_WORDS = 4 };
-// ... followed by two 64-bit words: pivot minimum (bit-inverted) and maximum (k_pivot_minmax)
-constexpr int INFO_BYTES = INFO_WORDS * 4 + 16;
+// ... followed by four 64-bit words: minimum (bit-inverted) and maximum of the positive pivots (the refinement
+// tolerance), then of |d| over every pivot (hipfact_condition)
+constexpr int INFO_BYTES = INFO_WORDS * 4 + 32;
 
 }  // namespace hipfact

@@ -793,23 +793,30 @@ __device__ __forceinline__ void dev_pivot_block(const FrontCtx& c, int* __restri
   if (wave == nw - 1 && !(phases & 32)) {
     // (positive pivots only: the negative ones belong to late variables - M = [A_s A_s^T  A_d; A_d^T  -I] -, whose
     // magnitude 1 + a_d^T S_s^-1 a_d says how dense the column is, not how well conditioned the constraint rows are)
-    double lo = 1.7e308, hi = 0.0;
+    // (words 2 and 3: the same over EVERY pivot, |d| of the negative ones included - hipfact_condition)
+    double lo = 1.7e308, hi = 0.0, alo = 1.7e308, ahi = 0.0;
     for (int k = lane; k < w; k += 64) {
       const double d = dd[k];
       if (d > 0.0) {
         lo = fmin(lo, d);
         hi = fmax(hi, d);
       }
+      alo = fmin(alo, fabs(d));
+      ahi = fmax(ahi, fabs(d));
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
       lo = fmin(lo, __shfl_down(lo, o, 64));
       hi = fmax(hi, __shfl_down(hi, o, 64));
+      alo = fmin(alo, __shfl_down(alo, o, 64));
+      ahi = fmax(ahi, __shfl_down(ahi, o, 64));
     }
     if (lane == 0) {
       unsigned long long* mm = reinterpret_cast<unsigned long long*>(info + INFO_WORDS);
       atomicMax(&mm[0], ~(unsigned long long)__double_as_longlong(lo));
       atomicMax(&mm[1], (unsigned long long)__double_as_longlong(hi));
+      atomicMax(&mm[2], ~(unsigned long long)__double_as_longlong(alo));
+      atomicMax(&mm[3], (unsigned long long)__double_as_longlong(ahi));
     }
   }
   if (ROWINV) __syncthreads();

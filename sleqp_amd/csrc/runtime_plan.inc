@@ -476,6 +476,10 @@ static int upload_plan(hipfact_handle* h) {
       std::stable_sort(solve_order.begin() + P.level_ptr[l], solve_order.begin() + P.level_ptr[l + 1], [&](int a, int b) {
         return (long long)sn[a].r * sn[a].w > (long long)sn[b].r * sn[b].w;
       });
+  h->n_resorted = 0;
+  for (int l = 0; l < P.nlevels; ++l)
+    h->n_resorted += !std::equal(solve_order.begin() + P.level_ptr[l], solve_order.begin() + P.level_ptr[l + 1],
+                                 P.level_sn.begin() + P.level_ptr[l]);
   for (int q = 0; q < ns; ++q) {
     const int s2 = solve_order[q];
     const int w2 = std::max(1, sn[s2].w), u2 = sn[s2].r - sn[s2].w;
@@ -825,6 +829,7 @@ static int upload_plan(hipfact_handle* h) {
     // fused solve launch: every front (or row slice of a big front) as a SolveItem, children before parents
     h->fused_solve = false;
     h->n_sitems = 0;
+    h->n_sliced = 0;
     bool ok = h->solve_fused && ns > 0;
     for (int s2 = 0; s2 < ns && ok; ++s2) ok = sn[s2].w >= 1 && (h->solve_slices || sn[s2].r <= 1024);
     if (ok) {
@@ -921,6 +926,7 @@ static int upload_plan(hipfact_handle* h) {
                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         h->fused_solve = true;
         h->n_sitems = nit;
+        for (int q = 0; q < nit; ++q) h->n_sliced += it_sl[q] == 0 && it_nsl[q] > 1;
         h->sp_bytes = (double)(spf + spb) * sizeof(double);
         // ---- top block: the last levels (few fronts each: pure hop latency in the solves) as two dense products
         h->tb_nT = h->tb_ntf = h->tb_nfb = h->tb_levels = h->tb_nchunks = 0;

@@ -609,6 +609,7 @@ static void solve_once_async(hipfact_handle* h, const double* b, double* z, bool
   const bool tree = tree_solve(h);
   // fused solve launch: the kernel behind it advances the epoch of its double-buffered exchange slots
   int* epoch = (tree && P.m > 0) ? h->d_epoch.as<int>() : nullptr;
+  h->last_rhs_in_tree = h->last_xupd_in_tree = h->last_xupd_blocks = 0;
   if (P.saddle) {
     const SaddleMaps M = saddle_maps(h);
     // The shape of the launches: the forward items of the tree launch form their own rows of the right-hand side,
@@ -638,6 +639,9 @@ static void solve_once_async(hipfact_handle* h, const double* b, double* z, bool
           h->x_dot_blocks = X.nblocks;
         }
       }
+      h->last_rhs_in_tree = rhs_in_tree;
+      h->last_xupd_in_tree = whole;
+      h->last_xupd_blocks = X.nblocks;
       solve_m_async(h, skip, (rhs_in_tree || whole) ? &R : nullptr, whole ? &X : nullptr);
     }
     if (!whole) launch_x_saddle(h, M, b, z, acc, skip, epoch);

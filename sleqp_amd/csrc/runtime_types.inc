@@ -227,6 +227,11 @@ struct PlanState : FactorMemo {
   double sp_bytes = 0;
   DevBuf d_SPf, d_SPb, d_sitems, d_xhat, d_sxuoff, d_sxinvoff, d_epoch, d_spart;
   int n_sitems = 0;  // items of the fused solve launch: one per front, row slices for fronts of more than 1024 rows
+  int n_sliced = 0;  // fronts of the fused solve launch that are cut into row slices (info key solve_sliced_fronts)
+  int n_resorted = 0;  // levels whose solve items are not in plan order (solve_sorted; info key solve_resorted_levels)
+  // what the last queued single solve launched (info keys rhs_in_tree, xupd_in_tree, xupd_blocks_launched): the
+  // right-hand side / the x update inside the tree launch, and the workgroups the x update got there
+  int last_rhs_in_tree = 0, last_xupd_in_tree = 0, last_xupd_blocks = 0;
   // top block of the solve (device_types.h: TopBlockIn): the fronts of the last levels as two dense products
   int tb_nT = 0, tb_ntf = 0, tb_nfb = 0, tb_levels = 0, tb_nchunks = 0;  // nfb: items of the fronts below T
   bool tb_valid = false;       // X_T of the CURRENT factorisation has been formed

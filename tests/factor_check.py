@@ -19,7 +19,7 @@ import numpy as np
 import scipy.sparse as sp
 
 PLAN_ARRAYS = {"perm": np.int32, "sn_c0": np.int32, "sn_r": np.int32, "sn_rowptr": np.int64, "sn_rows": np.int32,
-               "sn_Loff": np.int64, "late_cols": np.int32}
+               "sn_Loff": np.int64, "late_cols": np.int32, "sn_level": np.int32}
 
 
 class Structure:
@@ -41,7 +41,7 @@ def device_plan_arrays(fact) -> Structure:
     ns = int(fact.info("nsuper"))
     m = int(fact.info("m"))
     n_rows = int(fact.info("rows_total"))
-    sizes = {"perm": m, "sn_c0": ns + 1, "sn_r": ns, "sn_rowptr": ns + 1, "sn_rows": n_rows, "sn_Loff": ns,
+    sizes = {"perm": m, "sn_c0": ns + 1, "sn_r": ns, "sn_rowptr": ns + 1, "sn_rows": n_rows, "sn_Loff": ns, "sn_level": ns,
              "late_cols": int(fact.info("late_columns"))}
     out = {k: _debug_copy(fact, k, np.empty(sizes[k], dtype=dt)) for k, dt in PLAN_ARRAYS.items()}
     return Structure(**out)
@@ -379,6 +379,9 @@ def crafted_cases():
         "arrow_spd": (nat, lambda: block_arrow(ARROW_EDGES, ARROW_BORDER, 0)),
         "arrow_quasidef": (nat, lambda: block_arrow(ARROW_EDGES, ARROW_BORDER, 1, quasi=True)),
         "arrow_wide_update": (dict(nat, HIPFACT_RELAX="0,0,0"), lambda: block_arrow(WIDE_EDGES, WIDE_BORDER, 2)),
+        # arrow_spd without its isolated node: one root, so the plan forms the top block of the solve (every root has to
+        # lie in the block; the isolated node of the other arrows is a root at level 0)
+        "arrow_one_root": (nat, lambda: block_arrow(ARROW_EDGES[1:], ARROW_BORDER, 0)),
     }
 
 
