@@ -174,8 +174,18 @@ int hipfact_solution_device(hipfact_handle* h, const double** d_sol);
  * From which nrhs the call pays (measured on the MI355X, EXPERIMENTS.md, "Blocked solve"): a block costs the same
  * whatever it holds, so use full blocks; on the headline workload (banded, 150 000 unknowns) the break-even against
  * back-to-back hipfact_solve_device calls is nrhs = 16 (0.88 x their time per column for one full block, 0.90 / 0.91 x
- * at nrhs = 32 / 64: the margin is about 10 % and shrinks a little over several blocks).  On plans whose top is a chain
- * of tall fronts (thousands of rows) there is NO break-even yet (1.85 x): issue single solves there. */
+ * at nrhs = 32 / 64: the margin is about 10 % and shrinks a little over several blocks; with the row slices below, which
+ * cut 14 of its fronts in two, 75.4 / 77.6 us per column at nrhs = 16 / 64 against 76.3 / 78.4 without).  On plans whose top is a chain of tall fronts (thousands of rows) every such front is cut
+ * into row slices of about "multi_slice_rows" rows (default 128), a workgroup each: on the dense-chain workload
+ * (15 000 unknowns, 41 levels) a full block then costs 169 us per column at nrhs = 16 and 64, 0.43 x the 388 us of a
+ * single solve and 0.24 x the 716 us of the unsliced sweeps ("multi_slice_rows" = 0; 256 rows: 204 us, 512 rows: 279 us).
+ * A block of the chain costs 2.7 ms whatever it holds, seven single solves' worth: use full blocks there too.
+ * Option "multi_slice_rows" (hipfact_set_option; the blocked solve's own, kept out of the table below): 0, or a multiple
+ * of 16 in [16, 4096], anything else is HIPFACT_EINVAL.  A front with u update rows becomes max(1, u / multi_slice_rows)
+ * slices (hipfact_debug_multi_slices); 0: one workgroup per front, the bytes of the unsliced sweeps.  It takes effect at
+ * the next blocked call and costs no analysis.  No workgroup waits for another: the slice that arrives last at the
+ * front's counter finishes the front, with sums in slice order - the bits do not depend on the arrival order.
+ * Info: "multi_sliced_fronts" fronts the item lists of the last blocked call cut, "multi_slice_items" their slices. */
 int hipfact_solve_device_multi(hipfact_handle* h, int nrhs, const double* d_rhs, long long ld_rhs,
                                double* d_sol, long long ld_sol, double* omega);
 
@@ -546,6 +556,13 @@ int hipfact_debug_pool_selftest(int callers, int rounds);
 int hipfact_debug_place_rows(int m, const int* Ar_ptr, long long fill_bytes, int classes, long long* bounds, int* classes_out,
                              int* grid_out, int* blocks);
 int hipfact_debug_place_items(int nfronts, const int* counts, int classes, int* order, int* lost);
+
+/* The row slices of the blocked solve, as a pure host function (no GPU needed; used by the tests): a front with `u`
+ * update rows has nt = ceil(u / 16) tiles of 16 rows and is cut into nslice = max(1, u / slice_rows) items (integer
+ * division; slice_rows = 0: one item), slice k owning the tiles [nt k / nslice, nt (k + 1) / nslice).  Returns nslice
+ * and, when tile_bounds is not NULL and nslice <= cap, writes the nslice + 1 tile bounds; HIPFACT_EINVAL for u < 0 or
+ * a slice_rows the option "multi_slice_rows" would refuse.  The item lists of the sweeps are built from the same rule. */
+int hipfact_debug_multi_slices(int u, int slice_rows, int* tile_bounds /* cap + 1 values */, int cap);
 
 /* ---- host-only symbolic plan (no GPU needed; used by the tests) ---------- */
 

@@ -3,6 +3,11 @@
 // ---------------------------------------------------------------------------
 int hipfact_set_option(hipfact_handle* h, const char* name, double value) {
   if (!h || !name) return HIPFACT_EINVAL;
+  {  // the blocked solve keeps its own option with its code (runtime_multi.inc) and documents it with its entry point
+    bool known = false;
+    const int rc = multi_set_option(h, name, value, known);
+    if (known) return rc;
+  }
   if (!strcmp(name, "refine_steps")) {  // correction passes carried by every solve graph (default 1; 0: plain solve, no residual); they return at once when the device-side control block reports convergence
     h->refine_steps = std::max(0, (int)value);
     h->refine_inline = h->refine_steps;
@@ -317,6 +322,15 @@ int hipfact_debug_place_items(int nfronts, const int* counts, int classes, int* 
   return HIPFACT_OK;
 }
 
+// the row slices of the blocked solve (multi_slices.h) as a pure host function: what a front with u update rows becomes
+int hipfact_debug_multi_slices(int u, int slice_rows, int* tile_bounds, int cap) {
+  if (u < 0 || !multi_slice_rows_valid(slice_rows)) return HIPFACT_EINVAL;
+  const int ns = multi_nslice(u, slice_rows);
+  if (tile_bounds && ns <= cap)
+    for (int k = 0; k <= ns; ++k) tile_bounds[k] = multi_slice_tile(u, ns, k);
+  return ns;
+}
+
 int hipfact_get_info(const hipfact_handle* h, const char* name, double* value) {
   if (!h || !name || !value) return HIPFACT_EINVAL;
   const Plan& P = h->plan;
@@ -397,6 +411,7 @@ int hipfact_get_info(const hipfact_handle* h, const char* name, double* value) {
   INFO("boundary_fast", h->boundary_fast) INFO("bd_count", h->bd_count) INFO("bd_stage_us", h->bd_stage_us) INFO("bd_queue_us", h->bd_queue_us) INFO("bd_rhs_us", h->bd_rhs_us) INFO("bd_device_us", h->bd_device_us) INFO("bd_d2h_us", h->bd_d2h_us) INFO("bd_wait_us", h->bd_wait_us) INFO("bd_copyout_us", h->bd_copyout_us)
   INFO("multi_solves", h->multi_solves) INFO("multi_cols", h->multi_cols) INFO("multi_blocks", h->multi_blocks)
   INFO("multi_passes", h->multi_passes) INFO("multi_single_cols", h->multi_single_cols) INFO("multi_failed_col", h->multi_failed_col)
+  INFO("multi_sliced_fronts", h->mitems_for < 0 ? 0 : h->n_mcut) INFO("multi_slice_items", h->mitems_for < 0 ? 0 : h->n_mslices) INFO("multi_slice_rows", h->multi_slice_rows)
   INFO("num_solve", h->num_solve) INFO("num_refined", h->num_refined) INFO("refine_adaptive", h->refine_adaptive)
   INFO("num_passes", h->num_passes) INFO("last_omega", h->last_ctl.omega) INFO("last_iters", h->last_ctl.iters)
   INFO("last_status", h->last_ctl.status) INFO("last_tol", h->last_ctl.tol) INFO("kappa_est", h->last_ctl.kappa)

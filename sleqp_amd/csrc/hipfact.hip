@@ -43,6 +43,7 @@
 #include "kernel_types.h"
 #include "kernels_decl.h"
 #include "xcd_place.h"
+#include "multi_slices.h"
 
 #include "runtime_types.inc"
 #include "runtime_plan.inc"

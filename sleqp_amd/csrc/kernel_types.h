@@ -47,10 +47,21 @@ struct DecideIn {
   double target;
   const unsigned long long* minmax;
 };
-// what a level launch of the blocked sweeps needs (kernels_solve_multi.inc); level_sn points at the level's fronts
+// An item of a level launch of the blocked sweeps: a whole front (nslice == 1: the tiles [0, nt) of its update rows)
+// or row slice `slice` of a tall one (multi_slices.h), with the tiles [t0, t1) of 16 update rows.  The slices of a
+// front share two arrival counters (cnt: forward, cnt + 1: backward; zero in front of every pass) and hand their
+// partial sums of L21^T G to the slice that arrives last, each in a slab of wp x MR doubles (slab: offset of this
+// slice's; the front's slabs follow one another in slice order, so slice 0's offset is slab - slice wp MR).
+struct MultiItem {
+  int sn, slice, nslice, t0, t1, cnt;
+  long long slab;
+};
+// what a level launch of the blocked sweeps needs (kernels_solve_multi.inc); items points at the level's items
 struct MultiIn {
   const SnDesc* __restrict__ sn;
-  const int* __restrict__ level_sn;
+  const MultiItem* __restrict__ items;
+  double* slabs;        // (handed from workgroup to workgroup inside a launch: no __restrict__, no const)
+  unsigned int* cnt;
   const double* __restrict__ L;
   const int* __restrict__ inv;        // inverse relative indices of every front as a child (SnDesc::pad1)
   const int* __restrict__ child_idx;

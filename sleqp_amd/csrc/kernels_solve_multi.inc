@@ -7,8 +7,11 @@
 // U hold MR doubles per update row (row a of front S at MR (S.uoff + a)), so that the 16 lanes of an MFMA column
 // group store and load 128 contiguous bytes.
 //
-// One launch per level and direction, one workgroup per front, NO waiting between workgroups: the level boundary is
-// the launch boundary.  The arithmetic is that of dev_fwd_front / dev_bwd_front (kernels_solve_level.inc) on the
+// One launch per level and direction, one workgroup per ITEM (kernel_types.h: MultiItem), NO waiting between
+// workgroups: the level boundary is the launch boundary.  An item is a whole front, or a row slice of a tall one
+// (multi_slices.h): a level of a dense chain holds ONE front of thousands of rows, and a single workgroup streaming its
+// panel leaves the other 255 compute units idle.  The slices of a front work side by side and meet at an arrival
+// counter; nobody polls it - the slice that finds itself last does what is left (see the two kernels).  The arithmetic is that of dev_fwd_front / dev_bwd_front (kernels_solve_level.inc) on the
 // column-major r x w panels of d_L,
 //     forward    F = Y[c0 : c0 + w, :] + the children's update blocks (child by child in plan order, pulled through
 //                the inverse relative indices: no atomics);  X1 = F_top + strict_lower(P11) F_top;
@@ -19,7 +22,8 @@
 // and B[k = lk][j = li] and gets D[i = lk + 4 q][j = li], q < 4 (scripts/probe/mfma_f64_layout.hip): column j of D
 // depends on column j of B alone, so a right-hand side never sees its neighbours - not their values, not a NaN or an
 // Inf among them - and no path below depends on how many columns of the block are in use.  Every sum has a fixed
-// order given by the front's shape and the workgroup size of its level.
+// order given by the front's shape, its slices and the workgroup size of its level: it does not depend on which slice
+// arrives last.
 // The w x MR head of a front lives in LDS (w <= 128: 16 KB); the update rows, of which there may be thousands, are
 // tiled through global memory: forward tiles of 16 rows go straight into the front's update block, the backward
 // sweep gathers G = Y[rows below] into that same block first (the parent consumed its forward content a launch
@@ -52,10 +56,11 @@ __global__ __launch_bounds__(MB) void k_fwd_level_multi(MultiIn A) {
   __shared__ double F[128 * MR];  // the head: right-hand side + children
   __shared__ double X[128 * MR];  // X1
   __shared__ long long ch_uoff[MCH];
-  __shared__ int ch_inv[MCH];
+  __shared__ int ch_inv[MCH + 1];  // [MCH]: this slice arrived last
   const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wave = tid >> 6, nw = nthr >> 6;
   const int li = lane & 15, lk = lane >> 4;
-  const SnDesc S = A.sn[A.level_sn[blockIdx.x]];
+  const MultiItem it = A.items[blockIdx.x];
+  const SnDesc S = A.sn[it.sn];
   const int w = S.w, r = S.r, u = r - w;
   const int nbk = (w + 15) >> 4, wp = nbk << 4;
   const double* __restrict__ P = A.L + S.Loff;
@@ -72,6 +77,14 @@ __global__ __launch_bounds__(MB) void k_fwd_level_multi(MultiIn A) {
     F[idx] = f;
   }
   __syncthreads();
+  // A sliced front: every slice forms the head and X1 for itself (w <= 128: little work, and the same bits in every
+  // slice), but the head of Y, which they have all just read as the right-hand side, is overwritten with X1 by ONE of
+  // them, and only once every slice holds its copy in LDS: by the one that arrives last at the front's forward
+  // counter.  (Nothing is handed over with the counter - the loads behind F have returned - so the add is relaxed.)
+  if (it.nslice > 1 && tid == 0) {
+    const unsigned int seen = __hip_atomic_fetch_add(A.cnt + it.cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    ch_inv[MCH] = seen + 1u == (unsigned int)it.nslice;
+  }
   // X1 = F_top + strict_lower(P11) F_top: a wave per block of 16 pivot rows, columns in ascending chunks of 4
   for (int kb = wave; kb < nbk; kb += nw) {
     const int row = 16 * kb + li;
@@ -90,11 +103,12 @@ __global__ __launch_bounds__(MB) void k_fwd_level_multi(MultiIn A) {
     }
   }
   __syncthreads();
-  for (int idx = tid; idx < w * MR; idx += nthr) A.Y[S.c0 + (idx >> 4) + (idx & 15) * A.ldy] = X[idx];
-  // U = F_below - L21 X1: a wave per tile of 16 update rows
-  const int ntile = (u + 15) >> 4;
+  if (it.nslice == 1 || ch_inv[MCH])
+    for (int idx = tid; idx < w * MR; idx += nthr) A.Y[S.c0 + (idx >> 4) + (idx & 15) * A.ldy] = X[idx];
+  // U = F_below - L21 X1: a wave per tile of 16 update rows, the item's own tiles (a tile has the same bits whichever
+  // item and wave computes it)
   double* __restrict__ Uo = A.U + S.uoff * MR;
-  for (int tl = wave; tl < ntile; tl += nw) {
+  for (int tl = it.t0 + wave; tl < it.t1; tl += nw) {
     const int a = 16 * tl + li;
     const double* __restrict__ Pr = P + w + a;
     d4_t acc = {0.0, 0.0, 0.0, 0.0};
@@ -116,26 +130,31 @@ __global__ __launch_bounds__(MB) void k_bwd_level_multi(MultiIn A) {
   __shared__ double part[256 * MR];  // nsplit x wp partial sums of L21^T G (nsplit wp <= 16 x waves <= 256)
   const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wave = tid >> 6, nw = nthr >> 6;
   const int li = lane & 15, lk = lane >> 4;
-  const SnDesc S = A.sn[A.level_sn[blockIdx.x]];
+  const MultiItem it = A.items[blockIdx.x];
+  const bool sliced = it.nslice > 1;
+  const SnDesc S = A.sn[it.sn];
   const int w = S.w, r = S.r, u = r - w;
   const int nbk = (w + 15) >> 4, wp = nbk << 4;
   const double* __restrict__ P = A.L + S.Loff;
   const int* __restrict__ rw = A.rows + S.rowoff + w;
   double* __restrict__ G = A.U + S.uoff * MR;
-  for (long long idx = tid; idx < (long long)u * MR; idx += nthr) G[idx] = A.Y[rw[idx >> 4] + (idx & 15) * A.ldy];
-  for (int idx = tid; idx < wp * MR; idx += nthr) {
-    const int t = idx >> 4;
-    V[idx] = (t < w) ? A.Y[S.c0 + t + (idx & 15) * A.ldy] / P[t + (long long)t * r] : 0.0;
-  }
+  // the item's own update rows (a whole front: all of them)
+  const long long g_hi = (long long)(16 * it.t1 < u ? 16 * it.t1 : u) * MR;
+  for (long long idx = (long long)16 * it.t0 * MR + tid; idx < g_hi; idx += nthr) G[idx] = A.Y[rw[idx >> 4] + (idx & 15) * A.ldy];
+  if (!sliced)  // (the head of a sliced front belongs to the slice that arrives last: below)
+    for (int idx = tid; idx < wp * MR; idx += nthr) {
+      const int t = idx >> 4;
+      V[idx] = (t < w) ? A.Y[S.c0 + t + (idx & 15) * A.ldy] / P[t + (long long)t * r] : 0.0;
+    }
   __syncthreads();
-  // L21^T G: unit (kb, sp) = 16 pivot columns x one slice of the 16-row chunks.  The four k-lanes of an MFMA take
+  // L21^T G: unit (kb, sp) = 16 pivot columns x one split of the item's 16-row chunks.  The four k-lanes of an MFMA take
   // the rows a0 + 4 lk + e (e = 0..3 over four MFMAs): a lane then reads four consecutive panel entries, the wave
   // whole 128-byte runs of 16 panel columns.
   const int nsplit = (nw / nbk > 0) ? nw / nbk : 1;
-  const int nac = (u + 15) >> 4;
+  const int nac = it.t1 - it.t0;
   for (int un = wave; un < nbk * nsplit; un += nw) {
     const int kb = un % nbk, sp = un / nbk;
-    const int c_lo = (int)((long long)nac * sp / nsplit), c_hi = (int)((long long)nac * (sp + 1) / nsplit);
+    const int c_lo = it.t0 + (int)((long long)nac * sp / nsplit), c_hi = it.t0 + (int)((long long)nac * (sp + 1) / nsplit);
     const int k = 16 * kb + li;
     const double* __restrict__ Pc = P + w + (long long)k * r;
     d4_t acc = {0.0, 0.0, 0.0, 0.0};
@@ -155,10 +174,52 @@ __global__ __launch_bounds__(MB) void k_bwd_level_multi(MultiIn A) {
     for (int q = 0; q < 4; ++q) part[(sp * wp + 16 * kb + lk + 4 * q) * MR + li] = acc[q];
   }
   __syncthreads();
-  for (int idx = tid; idx < w * MR; idx += nthr) {
-    double s = 0.0;
-    for (int q = 0; q < nsplit; ++q) s += part[q * wp * MR + idx];
-    V[idx] -= s;
+  if (!sliced) {
+    for (int idx = tid; idx < w * MR; idx += nthr) {
+      double s = 0.0;
+      for (int q = 0; q < nsplit; ++q) s += part[q * wp * MR + idx];
+      V[idx] -= s;
+    }
+  } else {
+    // A sliced front: the slice's share of L21^T G (its splits added in split order) goes to its slab, and the slice
+    // that arrives last at the front's backward counter adds the slabs IN SLICE ORDER - its own among them, read back
+    // like the others - and finishes the front: whichever slice that is, the head gets the same bits.  The hand-off
+    // is the in-launch split reduction: plain slab stores, drained by every wave, a barrier, then ONE agent-scope
+    // release and a relaxed agent-scope add; the last arriver takes ONE agent-scope acquire, and a barrier stands
+    // between it and the workgroup's plain loads of the slabs.  Nobody waits for anybody.
+    double* slab = A.slabs + it.slab;
+    for (int idx = tid; idx < w * MR; idx += nthr) {
+      double s = 0.0;
+      for (int q = 0; q < nsplit; ++q) s += part[q * wp * MR + idx];
+      slab[idx] = s;
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      const unsigned int seen = __hip_atomic_fetch_add(A.cnt + it.cnt + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const bool last = seen + 1u == (unsigned int)it.nslice;
+      if (last) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      }
+      part[0] = last ? 1.0 : 0.0;  // (every thread has read its partial sums: the barrier above)
+    }
+    __syncthreads();
+    if (part[0] == 0.0) return;
+    const double* slabs = A.slabs + (it.slab - (long long)it.slice * wp * MR);  // slab of slice 0
+    for (int idx = tid; idx < wp * MR; idx += nthr) {
+      const int t = idx >> 4;
+      double v = 0.0;
+      if (t < w) {
+        v = A.Y[S.c0 + t + (idx & 15) * A.ldy] / P[t + (long long)t * r];
+        double s = 0.0;
+        for (int q = 0; q < it.nslice; ++q) s += slabs[(long long)q * wp * MR + idx];
+        v -= s;
+      }
+      V[idx] = v;
+    }
   }
   __syncthreads();
   // X = V + strict_lower(P11)^T V: a wave per block of 16 pivot columns, rows below in ascending chunks of 16

@@ -12,6 +12,67 @@
 // The path has a workspace of its own (the block Y, the update blocks, residuals, a copy of B for the in-place case,
 // control blocks): it touches neither d_y nor d_uvec nor the epoch, the exchange slots, the flags or the top block of
 // the single solve, and it does not become "the last solve".
+// A level launch of the sweeps runs a list of ITEMS (kernel_types.h: MultiItem): a front, or - from twice
+// multi_slice_rows update rows on - its row slices (multi_slices.h), which meet at two arrival counters of the front
+// and at slabs of partial sums.  The lists belong to the workspace: they follow the plan and the option, nothing else
+// does (no analysis, no plan, no graph depends on them).
+
+// The option of the blocked solve (hipfact_set_option asks here first; documented with hipfact_solve_device_multi in
+// include/hipfact.h).  "multi_slice_rows": a front of at least twice this many update rows is cut into row slices of
+// about this height, a workgroup each (default 128; 0: one workgroup per front; otherwise a multiple of 16 up to
+// 4096, anything else is HIPFACT_EINVAL).  It takes effect at the next blocked call: the item lists are rebuilt, nothing
+// is analysed again, no plan and no graph is dropped.
+static int multi_set_option(hipfact_handle* h, const char* name, double value, bool& known) {
+  known = !strcmp(name, "multi_slice_rows");
+  if (!known) return HIPFACT_OK;
+  if (!(value >= 0.0 && value <= (double)MULTI_SLICE_ROWS_MAX) || value != (double)(int)value || !multi_slice_rows_valid((int)value)) {
+    h->error = "multi_slice_rows: 0 or a multiple of 16 in [16, 4096]";
+    return HIPFACT_EINVAL;
+  }
+  h->multi_slice_rows = (int)value;
+  return HIPFACT_OK;
+}
+
+// the item lists of the active plan for the slice height in force, the slabs and the counters
+static hipError_t multi_items(hipfact_handle* h) {
+  const Plan& P = h->plan;
+  const int S = h->multi_slice_rows;
+  std::vector<MultiItem> items;
+  items.reserve((size_t)P.nsuper);
+  h->mitems_for = -1;
+  h->mitem_ptr.assign((size_t)P.nlevels + 1, 0);
+  h->n_mcut = h->n_mslices = 0;
+  long long slab_max = 0;
+  for (int l = 0; l < P.nlevels; ++l) {
+    long long slab = 0;  // (one level is in flight at a time: the levels share the slabs)
+    for (int q = P.level_ptr[l]; q < P.level_ptr[l + 1]; ++q) {
+      const int s = P.level_sn[q];
+      const int w = P.sn_c0[s + 1] - P.sn_c0[s], u = P.sn_r[s] - w;
+      const long long wp = (w + 15) & ~15;
+      const int ns = multi_nslice(u, S);
+      for (int k = 0; k < ns; ++k)
+        items.push_back(MultiItem{s, k, ns, multi_slice_tile(u, ns, k), multi_slice_tile(u, ns, k + 1),
+                                  ns > 1 ? 2 * h->n_mcut : 0, ns > 1 ? slab + k * wp * MR : 0});
+      if (ns > 1) {
+        h->n_mcut++;
+        h->n_mslices += ns;
+        slab += ns * wp * MR;
+      }
+    }
+    slab_max = std::max(slab_max, slab);
+    h->mitem_ptr[(size_t)l + 1] = (int)items.size();
+  }
+  h->mcnt_bytes = ((size_t)2 * h->n_mcut * sizeof(unsigned int) + 15) & ~(size_t)15;
+  hipError_t e = h->d_mitems.ensure(std::max<size_t>(items.size() * sizeof(MultiItem), 16));
+  if (e == hipSuccess) e = h->d_mslab.ensure(std::max<size_t>((size_t)slab_max * sizeof(double), 16));
+  if (e == hipSuccess) e = h->d_mcnt.ensure(std::max<size_t>(h->mcnt_bytes, 16));
+  if (e == hipSuccess && !items.empty())
+    e = hipMemcpyAsync(h->d_mitems.p, items.data(), items.size() * sizeof(MultiItem), hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(h->d_mcnt.p, 0, h->d_mcnt.bytes, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);  // (`items` goes out of scope)
+  if (e == hipSuccess) h->mitems_for = S;
+  return e;
+}
 
 // workspace of the active plan state, MR columns; the handle stays usable for single solves when this fails
 static int multi_workspace(hipfact_handle* h) {
@@ -28,12 +89,17 @@ static int multi_workspace(hipfact_handle* h) {
     e = h->h_mctl.ensure(MR * sizeof(RefineCtl));
     if (e == hipSuccess) e = hipHostGetDevicePointer(&h->h_mctl_dev, h->h_mctl.p, 0);
   }
+  if (e == hipSuccess && h->mitems_for != h->multi_slice_rows) e = multi_items(h);
   if (e != hipSuccess) {
     (void)hipGetLastError();
     h->d_mY.release();
     h->d_mU.release();
     h->d_mR.release();
     h->d_mB.release();
+    h->d_mitems.release();
+    h->d_mslab.release();
+    h->d_mcnt.release();
+    h->mitems_for = -1;
     h->error = std::string("hipfact_solve_device_multi: workspace: ") + hipGetErrorString(e);
     return e == hipErrorOutOfMemory ? HIPFACT_ENOMEM : HIPFACT_EDEVICE;
   }
@@ -49,10 +115,13 @@ static void multi_sweeps(hipfact_handle* h) {
   A.inv = h->d_inv.as<int>();
   A.child_idx = h->d_child.as<int>();
   A.rows = h->d_rows.as<int>();
+  A.slabs = h->d_mslab.as<double>();
+  A.cnt = h->d_mcnt.as<unsigned int>();
   A.Y = h->d_mY.as<double>();
   A.ldy = P.m;
   A.U = h->d_mU.as<double>();
-  // levels whose fronts have at most 256 rows run with four waves per front, the others with sixteen
+  // levels whose fronts have at most 256 rows run with four waves per item, the others with sixteen (the slices of a
+  // front ride in their level's launch, with its workgroup size)
   auto threads = [&](const LevelInfo& li) {
     int rmax = 0;
     for (int q = li.begin; q < li.begin + li.count; ++q) rmax = std::max(rmax, P.sn_r[P.level_sn[q]]);
@@ -60,13 +129,13 @@ static void multi_sweeps(hipfact_handle* h) {
   };
   for (int l = 0; l < P.nlevels; ++l) {
     const LevelInfo& li = h->levels[l];
-    A.level_sn = h->d_level_sn.as<int>() + li.begin;
-    LAUNCH(PC_FWD, k_fwd_level_multi, dim3(li.count), dim3(threads(li)), 0, A);
+    A.items = h->d_mitems.as<MultiItem>() + h->mitem_ptr[l];
+    LAUNCH(PC_FWD, k_fwd_level_multi, dim3(h->mitem_ptr[l + 1] - h->mitem_ptr[l]), dim3(threads(li)), 0, A);
   }
   for (int l = P.nlevels - 1; l >= 0; --l) {
     const LevelInfo& li = h->levels[l];
-    A.level_sn = h->d_level_sn.as<int>() + li.begin;
-    LAUNCH(PC_BWD, k_bwd_level_multi, dim3(li.count), dim3(threads(li)), 0, A);
+    A.items = h->d_mitems.as<MultiItem>() + h->mitem_ptr[l];
+    LAUNCH(PC_BWD, k_bwd_level_multi, dim3(h->mitem_ptr[l + 1] - h->mitem_ptr[l]), dim3(threads(li)), 0, A);
   }
 }
 
@@ -89,6 +158,8 @@ static int multi_pass(hipfact_handle* h, const std::vector<int>& cols, const dou
       else
         launch_rhs_perm(h, rhs[j], nullptr, Y + (size_t)j * P.m);
     }
+    // the arrival counters of the sliced fronts start every pass at zero, whatever became of the pass before
+    if (h->n_mcut > 0) HCHECK(h, hipMemsetAsync(h->d_mcnt.p, 0, h->mcnt_bytes, h->stream));
     multi_sweeps(h);
   }
   for (int j : cols) {

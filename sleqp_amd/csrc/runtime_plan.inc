@@ -262,6 +262,7 @@ static int upload_plan(hipfact_handle* h) {
   // per-level launch metadata
   h->levels.assign(P.nlevels, LevelInfo());
   h->dealt_multi = 0;
+  h->mitems_for = -1;  // (the blocked solve's item lists: rebuilt by its next call)
   size_t max_lds = 0;
   std::vector<int> items;
   std::vector<FrontItem> fitems;

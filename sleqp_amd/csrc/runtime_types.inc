@@ -257,6 +257,14 @@ struct PlanState : FactorMemo {
   // blocked solve (runtime_multi.inc), MR columns each: the block Y of M Y = T, the update blocks, the residuals, a
   // copy of B for the in-place case; allocated by the first multi solve of the state
   DevBuf d_mY, d_mU, d_mR, d_mB;
+  // ... and the item lists of its sweeps (kernel_types.h: MultiItem; level l launches the items [mitem_ptr[l],
+  // mitem_ptr[l + 1])), the slabs of partial sums of the level with the most, two arrival counters per sliced front.
+  // Built with the workspace for the slice height mitems_for (-1: not built since the plan was uploaded).
+  DevBuf d_mitems, d_mslab, d_mcnt;
+  std::vector<int> mitem_ptr;
+  int mitems_for = -1;
+  int n_mcut = 0, n_mslices = 0;  // fronts the lists cut, and their slice items (info keys multi_sliced_fronts, multi_slice_items)
+  size_t mcnt_bytes = 0;          // the counters, padded to a multiple of 16 bytes: what is cleared in front of every pass
 
   PlanState() = default;
   PlanState(PlanState&&) = default;
@@ -478,6 +486,7 @@ struct hipfact_handle : PlanState, SingleSolveMemo {
   void* h_mctl_dev = nullptr;
   long multi_solves = 0, multi_cols = 0, multi_blocks = 0, multi_passes = 0, multi_single_cols = 0;
   int multi_failed_col = -1;
+  int multi_slice_rows = 128;  // fronts of at least twice this many update rows are cut into row slices of about this height (0: never; multi_slices.h)
 };
 
 struct hipfact_spmat {
