@@ -192,6 +192,54 @@ int hipfact_solve_device_multi(hipfact_handle* h, int nrhs, const double* d_rhs,
 /* The same for host arrays, both N x nrhs column-major with leading dimension N (sol may be rhs). */
 int hipfact_solve_multi(hipfact_handle* h, int nrhs, const double* rhs, double* sol);
 
+/* ---- extra-precise solve: iterative refinement on residuals taken in twice the working precision ---------------
+ * Every solve above is refined on an fp64 residual: its BACKWARD error reaches rounding level ("last_omega"), its
+ * forward error stays at about cond(K) 2^-53 - and the saddle path factors S^ = A^ A^^T, whose condition is that of
+ * A_W squared.  This call forms b - K z as double-double pairs (one rounding per entry, at the end) and iterates
+ *   z = K^-1 b;  for k = 1, 2, ...:  r = b - K z;  dz = K^-1 r;  z += dz
+ * so that z converges to the correctly rounded solution for every K on which the factor still contracts
+ * (||dz_k|| <= ||dz_{k-1}|| / 2), and reports an estimate of the error that is left (what LAPACK's xSYRFSX and MA57D
+ * offer).  Norms are taken per BLOCK: the variables [0, n) and the multipliers [n, N) of a saddle-point K (one block in
+ * generic mode), dn_k = ||dz_k||_inf, zn_k = ||z||_inf before the update.  The rule, pass k = 1, 2, ...:
+ *   a non-finite norm: status NONFINITE, stop, correction k not applied;
+ *   k >= 2: ratio = max over the blocks with dn_{k-1} > 0 of dn_k / dn_{k-1}, rho = max(rho, ratio); ratio > 1/2:
+ *           status STALLED, stop, correction k NOT applied;
+ *   otherwise correction k is applied; then dn_k <= 2^-53 zn_k in every block (0 <= 0 counts): status CONVERGED, stop;
+ *   k == refine_max: status PASS_LIMIT, stop.
+ *   ferr = max over the blocks of max(2^-53, (dn / zn) / (1 - min(rho, 1/2))) from the last pair of norms seen
+ *   (dn = 0: 0, whatever zn is; status NONFINITE or no pass at all: +inf).
+ * The call BLOCKS, with the contract of hipfact_solve_device_multi: on entry it does what hipfact_check does; it needs
+ * a factorisation (HIPFACT_ESTATE); d_sol may equal d_rhs (the call works on a copy of b), any other overlap and NULL
+ * arrays are HIPFACT_EINVAL; it does not become "the last solve" - hipfact_solution* still return the earlier single
+ * solve, and a single solve issued afterwards gives the bits it would have given without this call.  Every K^-1 above is
+ * one plain single solve (graphs, top block, dense-column correction, per-level fallback behind a timed-out wait
+ * included); a pass costs one such solve, one residual and one host synchronisation.
+ * Return code: one more double-double residual of the returned z is judged as every solve's first residual is;
+ * info->omega is that backward error, and the code is the single solve's verdict: HIPFACT_ESINGULAR above fail_omega or
+ * outside the range of a statically pivoted K (d_sol and *info are still written), HIPFACT_OK otherwise - a non-finite
+ * right-hand side is HIPFACT_OK with status NONFINITE and a non-finite z, as everywhere else.  Read `status`:
+ * STALLED / PASS_LIMIT with HIPFACT_OK is a solution of fp64 quality whose error estimate is `ferr`.
+ * Info: "extra_solves" calls that ran the loop, "extra_passes" corrections they applied, "extra_last_status". */
+enum { HIPFACT_EXTRA_CONVERGED = 0, HIPFACT_EXTRA_STALLED = 1, HIPFACT_EXTRA_NONFINITE = 2, HIPFACT_EXTRA_PASS_LIMIT = 3 };
+typedef struct hipfact_extra_info {
+  int passes;     /* corrections applied */
+  int status;     /* HIPFACT_EXTRA_* */
+  double ferr;    /* estimate of max over the blocks of ||z - z*||_inf / ||z||_inf */
+  double dz_rel;  /* max over the blocks of the last ||dz||_inf / ||z||_inf */
+  double rho;     /* largest ratio ||dz_k|| / ||dz_{k-1}|| seen (0 with fewer than two passes) */
+  double omega;   /* backward error of the returned z from a final double-double residual, as "last_omega" defines it */
+} hipfact_extra_info;
+int hipfact_solve_device_extra(hipfact_handle* h, const double* d_rhs, double* d_sol, hipfact_extra_info* info /* nullable */);
+/* The same for host arrays of N doubles (sol may be rhs); staged through a device buffer of the handle. */
+int hipfact_solve_extra(hipfact_handle* h, const double* rhs, double* sol, hipfact_extra_info* info /* nullable */);
+
+/* d_res = d_b - K d_z against the values of the current factorisation, queued on the handle's stream like
+ * hipfact_solve_device (no synchronisation).  extended = 0: the fp64 residual every checked solve takes; extended != 0:
+ * every entry accumulated as a double-double pair and rounded once (error at most 2^-53 |r_i| plus about
+ * (entries of the row) x 2^-105 sum |K_ij| |z_j|).  Vectors of N doubles in the caller's numbering; d_res must not overlap
+ * d_b or d_z (HIPFACT_EINVAL); HIPFACT_ESTATE before a factorisation.  Deterministic: the same bits on every call. */
+int hipfact_residual_device(hipfact_handle* h, const double* d_b, const double* d_z, double* d_res, int extended);
+
 /* Blocks until the queued work has finished and reports what the asynchronous
  * entry points above could not: a singular / rank-deficient factorisation
  * (HIPFACT_ESINGULAR), a solve whose iterative refinement stalled far above its
@@ -563,6 +611,19 @@ int hipfact_debug_place_items(int nfronts, const int* counts, int classes, int* 
  * and, when tile_bounds is not NULL and nslice <= cap, writes the nslice + 1 tile bounds; HIPFACT_EINVAL for u < 0 or
  * a slice_rows the option "multi_slice_rows" would refuse.  The item lists of the sweeps are built from the same rule. */
 int hipfact_debug_multi_slices(int u, int slice_rows, int* tile_bounds /* cap + 1 values */, int cap);
+
+/* The stopping rule of hipfact_solve_device_extra as a pure host function (no GPU needed; used by the tests), applied
+ * to a recorded sequence of norms: dn / zn hold npasses x nblocks values, pass by pass (nblocks 1 or 2, pass_cap >= 1,
+ * else HIPFACT_EINVAL).  Returns the number of passes it looked at (it stops where the solve would); *status is
+ * HIPFACT_EXTRA_*, or -1 when the sequence ended before the rule did; *applied corrections applied, *ferr, *rho as in
+ * hipfact_extra_info.  Every output pointer may be NULL. */
+int hipfact_debug_extra_rule(int nblocks, int npasses, const double* dn, const double* zn, int pass_cap, int* applied,
+                             int* status, double* ferr, double* rho);
+/* The double-double accumulate of the residual kernels on the host (the same header, no GPU needed; used by the
+ * tests): round(b - sum k[i] z[i]), term i accumulated in pair i % lanes, the pairs added through the kernels' fixed
+ * tree (lanes a power of two in [1, 256]: 8 / 16 are the lane groups of a column / a row, 256 a long row's workgroup
+ * up to the order inside its waves).  NaN for arguments out of range. */
+double hipfact_debug_dd_residual(int nterms, const double* k, const double* z, double b, int lanes);
 
 /* ---- host-only symbolic plan (no GPU needed; used by the tests) ---------- */
 

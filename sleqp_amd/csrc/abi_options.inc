@@ -412,6 +412,7 @@ int hipfact_get_info(const hipfact_handle* h, const char* name, double* value) {
   INFO("multi_solves", h->multi_solves) INFO("multi_cols", h->multi_cols) INFO("multi_blocks", h->multi_blocks)
   INFO("multi_passes", h->multi_passes) INFO("multi_single_cols", h->multi_single_cols) INFO("multi_failed_col", h->multi_failed_col)
   INFO("multi_sliced_fronts", h->mitems_for < 0 ? 0 : h->n_mcut) INFO("multi_slice_items", h->mitems_for < 0 ? 0 : h->n_mslices) INFO("multi_slice_rows", h->multi_slice_rows)
+  INFO("extra_solves", h->extra_solves) INFO("extra_passes", h->extra_passes) INFO("extra_last_status", h->extra_last_status)
   INFO("num_solve", h->num_solve) INFO("num_refined", h->num_refined) INFO("refine_adaptive", h->refine_adaptive)
   INFO("num_passes", h->num_passes) INFO("last_omega", h->last_ctl.omega) INFO("last_iters", h->last_ctl.iters)
   INFO("last_status", h->last_ctl.status) INFO("last_tol", h->last_ctl.tol) INFO("kappa_est", h->last_ctl.kappa)

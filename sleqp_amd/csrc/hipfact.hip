@@ -5,7 +5,7 @@
 // state.  All numerics run on the device; there is no CPU fallback: without a
 // usable GPU hipfact_create fails with HIPFACT_EDEVICE.
 //
-// The host translation unit (the kernels are compiled separately: kernels_factor.hip / kernels_solve.hip, declared in the
+// The host translation unit (the kernels are compiled separately: kernels_factor.hip / kernels_solve.hip / kernels_extra.hip, declared in the
 // generated kernels_decl.h), split by role:
 //   runtime_types.inc   buffers, plan state, the handle          abi_core.inc         create .. solution (SleqpFact)
 //   runtime_plan.inc    upload of a plan, work items             abi_working_set.inc  superset plans, assemble_kkt
@@ -13,6 +13,7 @@
 //   vtable_superset.inc row dictionary (plain vtable)            abi_options.inc      options, info, debug copies
 //   dense_cols.inc      dense Jacobian columns                   krylov_device.inc    device-controlled CG
 //   runtime_multi.inc   blocked solve, 16 right-hand sides       abi_multi.inc        hipfact_solve[_device]_multi
+//   runtime_extra.inc   extra-precise solve (dd_arith.h)         abi_extra.inc        hipfact_solve[_device]_extra, _residual_device
 #include <hip/hip_runtime.h>
 
 #include <dlfcn.h>
@@ -39,20 +40,23 @@
 #include "plan.h"
 #include "tridiag_tr.h"
 
-// the kernels are translation units of their own (kernels_factor.hip, kernels_solve.hip); this one sees their declarations
+// the kernels are translation units of their own (kernels_factor.hip, kernels_solve.hip, kernels_extra.hip); this one sees their declarations
 #include "kernel_types.h"
 #include "kernels_decl.h"
 #include "xcd_place.h"
 #include "multi_slices.h"
+#include "dd_arith.h"
 
 #include "runtime_types.inc"
 #include "runtime_plan.inc"
 #include "runtime_queue.inc"
 #include "runtime_multi.inc"
+#include "runtime_extra.inc"
 
 extern "C" {
 #include "abi_core.inc"
 #include "abi_multi.inc"
+#include "abi_extra.inc"
 #include "abi_working_set.inc"
 #include "abi_krylov.inc"
 #include "abi_options.inc"

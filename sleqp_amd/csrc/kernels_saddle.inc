@@ -317,34 +317,6 @@ __global__ __launch_bounds__(FB) void k_x_saddle(int n, int m, const int* __rest
 //   forward error of a solve with backward error omega is about kappa omega, so well conditioned
 //   systems are accepted after the first pass and ill conditioned ones are refined to the limit.
 
-// block partials of a residual kernel: plain stores, the decision is taken by the kernel behind it
-__device__ __forceinline__ void refine_partials(double* __restrict__ partials, double mr, double mb, double mz) {
-  __shared__ double sh[3][FB / 64];
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    mr = nanmax(mr, __shfl_down(mr, o, 64));
-    mb = nanmax(mb, __shfl_down(mb, o, 64));
-    mz = nanmax(mz, __shfl_down(mz, o, 64));
-  }
-  if ((tid & 63) == 0) {
-    sh[0][tid >> 6] = mr;
-    sh[1][tid >> 6] = mb;
-    sh[2][tid >> 6] = mz;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    for (int q = 1; q < FB / 64; ++q) {
-      mr = nanmax(mr, sh[0][q]);
-      mb = nanmax(mb, sh[1][q]);
-      mz = nanmax(mz, sh[2][q]);
-    }
-    partials[3 * blockIdx.x] = mr;
-    partials[3 * blockIdx.x + 1] = mb;
-    partials[3 * blockIdx.x + 2] = mz;
-  }
-}
-
 // what the lane that holds the sum of column j of K / row k of A does with it (shared by the lane-group sweeps and
 // the workgroup-per-row phase of the long rows and columns)
 __device__ __forceinline__ void resid_col_tail(const SaddleMaps& M, int j, double s, const double* __restrict__ b,

@@ -38,6 +38,7 @@
 
 namespace hipfact {
 #include "kernels_common.inc"
+#include "kernels_residual_common.inc"
 #include "kernels_solve_level.inc"
 #include "kernels_solve_multi.inc"
 #include "kernels_solve_tree.inc"

@@ -26,7 +26,6 @@
 // so it must never find the previous solve's value - the copy of the previous launch is put back to
 // the sentinel by the forward items while this launch exchanges through the other one.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ double nanmax(double a, double b) { return (b > a || b != b) ? b : a; }
 // Reduces the partial maxima a residual kernel has left and updates the control block: one workgroup (any size
 // that is a multiple of 64, at most 1024 threads).  (An election of the last block inside the residual kernel
 // costs more: thousands of blocks each end with a dependent store -> ticket round trip, and increments of one
@@ -120,7 +119,6 @@ __global__ __launch_bounds__(FB) void k_refine_decide(DecideIn D, int first, int
   dev_refine_decide(D, first);
 }
 
-__device__ __forceinline__ int ext_row(const SaddleMaps& M, int s) { return M.cmap ? M.cmap[s] : M.n + s; }
 // one row of t, RL lanes per row (k_rhs_saddle and the forward items: same partial sums, same shuffle tree, same bits)
 __device__ __forceinline__ double rhs_row_tail(const RhsIn& R, int k, double s) {
   // (i == -1: a row of the structure outside the working set, t = 0; i == -2: the row of a late variable x_d in

@@ -265,6 +265,9 @@ struct PlanState : FactorMemo {
   int mitems_for = -1;
   int n_mcut = 0, n_mslices = 0;  // fronts the lists cut, and their slice items (info keys multi_sliced_fronts, multi_slice_items)
   size_t mcnt_bytes = 0;          // the counters, padded to a multiple of 16 bytes: what is cleared in front of every pass
+  // extra-precise solve (runtime_extra.inc): its four vectors b | z | r | dz, N_ext doubles each; they live with the
+  // plan because its solve graphs hold their addresses.  Allocated by the first such call of the state.
+  DevBuf d_xvec;
 
   PlanState() = default;
   PlanState(PlanState&&) = default;
@@ -487,6 +490,14 @@ struct hipfact_handle : PlanState, SingleSolveMemo {
   long multi_solves = 0, multi_cols = 0, multi_blocks = 0, multi_passes = 0, multi_single_cols = 0;
   int multi_failed_col = -1;
   int multi_slice_rows = 128;  // fronts of at least twice this many update rows are cut into row slices of about this height (0: never; multi_slices.h)
+  // extra-precise solve (runtime_extra.inc): control block and partial maxima of its final residual, the partial
+  // maxima of the norm kernel, the pinned words the host reads (four norms, then the control block's copy), the staging
+  // of the host entry point; counters of hipfact_get_info
+  DevBuf d_xctl, d_xnorms, d_xpart, d_xhost;
+  PinBuf h_xout;
+  void* h_xout_dev = nullptr;
+  long extra_solves = 0, extra_passes = 0;
+  int extra_last_status = 0;
 };
 
 struct hipfact_spmat {

@@ -120,6 +120,33 @@ class HipFact:
         self._check(self._lib.hipfact_solve_multi(self._h, rhs.shape[1], _ptr(rhs), _ptr(sol)))
         return sol
 
+    def solve_device_extra(self, d_rhs_ptr: int, d_sol_ptr: int, raise_singular: bool = True) -> dict:
+        """hipfact_solve_device_extra: K z = b for device vectors, refined on double-double residuals; blocks.
+        Returns the hipfact_extra_info as a dict (passes, status, ferr, dz_rel, rho, omega) with the return code under
+        "rc"; raise_singular = False hands HIPFACT_ESINGULAR back there instead of raising."""
+        info = ExtraInfo()
+        rc = self._lib.hipfact_solve_device_extra(self._h, C.c_void_p(d_rhs_ptr), C.c_void_p(d_sol_ptr), C.byref(info))
+        if rc != 0 and not (rc == -3 and not raise_singular):
+            self._check(rc)
+        return info.as_dict(rc)
+
+    def solve_extra(self, b, raise_singular: bool = True):
+        """hipfact_solve_extra: (z, info) with K z = b for a host vector, accurate to the last bits while the factor
+        contracts; info as in solve_device_extra."""
+        rhs = np.ascontiguousarray(b, dtype=np.float64)
+        assert rhs.size == self.N
+        sol = np.empty_like(rhs)
+        info = ExtraInfo()
+        rc = self._lib.hipfact_solve_extra(self._h, _ptr(rhs), _ptr(sol), C.byref(info))
+        if rc != 0 and not (rc == -3 and not raise_singular):
+            self._check(rc)
+        return sol, info.as_dict(rc)
+
+    def residual_device(self, d_b_ptr: int, d_z_ptr: int, d_res_ptr: int, extended: bool = True):
+        """hipfact_residual_device: res = b - K z on the handle's stream (extended: double-double accumulation)."""
+        self._check(self._lib.hipfact_residual_device(self._h, C.c_void_p(d_b_ptr), C.c_void_p(d_z_ptr),
+                                                      C.c_void_p(d_res_ptr), 1 if extended else 0))
+
     def synchronize(self):
         self._check(self._lib.hipfact_synchronize(self._h))
 
@@ -256,6 +283,16 @@ class HipFact:
             self.free()
         except Exception:
             pass
+
+
+class ExtraInfo(C.Structure):
+    """hipfact_extra_info (include/hipfact.h)"""
+    _fields_ = [("passes", C.c_int), ("status", C.c_int), ("ferr", C.c_double), ("dz_rel", C.c_double),
+                ("rho", C.c_double), ("omega", C.c_double)]
+
+    def as_dict(self, rc: int = 0) -> dict:
+        return {"rc": rc, "passes": self.passes, "status": self.status, "ferr": self.ferr, "dz_rel": self.dz_rel,
+                "rho": self.rho, "omega": self.omega}
 
 
 class TrExtra(C.Structure):
