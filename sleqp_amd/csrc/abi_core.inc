@@ -1,6 +1,8 @@
 // abi_core.inc - C ABI: create / free / set_matrix / refactor / solve / solution / condition (the five SleqpFact callbacks bind here)
 // (part of the single translation unit hipfact.hip; included from there, in this order)
 
+static void options_from_environment(hipfact_handle* h);  // abi_options.inc: the HIPFACT_* rows of the option table
+
 int hipfact_create(hipfact_handle** out, int device) {
   if (!out) return HIPFACT_EINVAL;
   *out = nullptr;
@@ -37,27 +39,7 @@ int hipfact_create(hipfact_handle** out, int device) {
     delete h;
     return HIPFACT_EDEVICE;
   }
-  if (const char* s = getenv("HIPFACT_REFINE")) h->refine_steps = atoi(s);
-  if (const char* s = getenv("HIPFACT_DATAFLOW_RETRY")) h->df_retry_every = std::max(0, atoi(s));
-  if (const char* s = getenv("HIPFACT_PULL_MAX")) h->pull_max_children = atoi(s);
-  if (const char* s = getenv("HIPFACT_FACTOR_TOP")) h->factor_top_max = atoi(s);
-  if (const char* s = getenv("HIPFACT_SOLVE_SORTED")) h->solve_sorted = atoi(s) != 0;
-  if (const char* s = getenv("HIPFACT_CHAIN_PAIRS")) h->chain_pairs = atoi(s) != 0;
-  if (const char* s = getenv("HIPFACT_HINT_PEEK")) h->factor_hint_peek = atoi(s) != 0;
-  if (const char* s = getenv("HIPFACT_SPANEL_FOLD")) h->spanel_fold = atoi(s) != 0;
-  if (const char* s = getenv("HIPFACT_RHS_FUSED")) h->rhs_fused = atoi(s) != 0;
-  if (const char* s = getenv("HIPFACT_XUPD_FUSED")) h->xupd_fused = atoi(s) != 0;
-  if (const char* s = getenv("HIPFACT_SOLVE_WHOLE_MAX")) h->solve_whole_max = std::max(SOLVE_PREFETCH, atoi(s));
-  if (const char* s = getenv("HIPFACT_CHECK_LAUNCHES")) h->check_launches = atoi(s) != 0;
-  if (const char* s = getenv("HIPFACT_XUPD_BLOCKS")) h->xupd_blocks = std::max(1, atoi(s));
-  if (const char* s = getenv("HIPFACT_SOLVE_SLICES")) h->solve_slices = atoi(s) != 0;
-  if (const char* s = getenv("HIPFACT_CHAIN_FUSE")) h->chain_fuse = atoi(s) != 0;
-  if (const char* s = getenv("HIPFACT_DECIDE_LAZY")) h->decide_lazy = atoi(s) != 0;
-  if (const char* s = getenv("HIPFACT_GRAPH")) h->use_graph = atoi(s) != 0;
-  if (const char* s = getenv("HIPFACT_TOP_BLOCK_AFTER")) h->top_block_after = std::max(0, atoi(s));
-  if (const char* s = getenv("HIPFACT_BOUNDARY_FAST")) h->boundary_fast = atoi(s) != 0;
-  if (const char* s = getenv("HIPFACT_SOL_SPLIT")) h->sol_split = atoi(s) != 0;
-  if (const char* s = getenv("HIPFACT_XCD_CLASSES")) h->xcd_classes = std::max(1, std::min(XCD_CLASSES_MAX, atoi(s)));
+  options_from_environment(h);
   turn_join(h);
   *out = h;
   return HIPFACT_OK;

@@ -1,6 +1,219 @@
 // abi_options.inc - C ABI: options, debug copies, info counters
 // (part of the single translation unit hipfact.hip; included from there, in this order)
 // ---------------------------------------------------------------------------
+// Every runtime option is ONE row of kOptions: the name hipfact_set_option takes (none: the row is a setting of the
+// environment alone), the HIPFACT_* variable that overrides the default when a handle is created (none: no override),
+// what a call invalidates, the text of the option table in include/hipfact.h (scripts/gen_option_table.py copies name
+// and text from the rows, in this order), and `set`: it turns the double into the stored value - clamps included -,
+// does whatever else belongs to the option alone, and returns 1 if the stored value changed, 0 if not, or a HIPFACT_E*
+// code.  hipfact_set_option is a lookup, `set` and the row's effect; hipfact_create runs `set` on atoi of every variable
+// that is set and applies no effect (a new handle has nothing to drop).  A new option is a new row.
+// "On every call" (FX_GRAPHS, FX_PLANS) and "only on a change" (FX_*_IF_CHANGED) are kept apart as they have grown:
+// a call with the value in force forces new graphs or a new analysis for the former, and callers may rely on that.
+enum OptionEffect {
+  FX_NONE,               // nothing beyond what `set` does
+  FX_GRAPHS,             // drop_graphs: the captured sequences hold the value
+  FX_GRAPHS_IF_CHANGED,  // ... only if the stored value changed
+  FX_PLANS,              // invalidate_plans: the next set_matrix analyses again
+  FX_PLANS_IF_CHANGED,   // ... only if the stored value changed
+};
+struct OptionRow {
+  const char* name;
+  const char* env;
+  OptionEffect effect;
+  int (*set)(hipfact_handle* h, double v);
+  const char* doc;
+};
+// the common `set`: h->field = conv (an expression in v), "changed" by comparison with what was stored
+#define OPT_STORE(field, conv)                 \
+  [](hipfact_handle* h, double v) -> int {     \
+    const auto x = (conv);                     \
+    const bool changed = h->field != x;        \
+    h->field = x;                              \
+    return changed;                            \
+  }
+static const OptionRow kOptions[] = {
+    {"refine_steps", "HIPFACT_REFINE", FX_GRAPHS,
+     [](hipfact_handle* h, double v) -> int {
+       h->refine_steps = std::max(0, (int)v);
+       h->refine_inline = h->refine_steps;
+       return 1;
+     },
+     "correction passes carried by every solve graph (default 1; 0: plain solve, no residual); they return at once when the device-side control block reports convergence"},
+    {"refine_max", nullptr, FX_NONE, OPT_STORE(refine_max, std::max(0, (int)v)),
+     "total correction passes of a solve, including those continued by hipfact_solution / hipfact_check (default 10)"},
+    {"refine_adaptive", nullptr, FX_GRAPHS, OPT_STORE(refine_adaptive, v != 0.0),
+     "0: every in-graph correction pass runs unconditionally"},
+    {"refine_tol", nullptr, FX_GRAPHS, OPT_STORE(refine_tol, v),
+     "forward-error target (default 1e-10): the backward-error tolerance is refine_tol / condition estimate, clamped to [4.5e-16, 1e-12]"},
+    {"fail_omega", nullptr, FX_NONE, OPT_STORE(fail_omega, v),
+     "a solve whose refinement stalls above this backward error is reported as singular (default 1e-8)"},
+    {"static_pivot", nullptr, FX_NONE, OPT_STORE(static_pivot, v != 0.0),
+     "0: a zero / wrongly signed pivot is HIPFACT_ESINGULAR at once (rounds 1 - 5)"},
+    {"static_pivot_delta", nullptr, FX_GRAPHS, OPT_STORE(static_delta, v > 0.0 ? v : 1e-8),
+     "the shift of every pivot of A A^T when a rank-deficient working set is factored with static pivoting (default 1e-8; rows are equilibrated to unit norm)"},
+    {"equilibrate", nullptr, FX_GRAPHS,
+     [](hipfact_handle* h, double v) -> int {
+       h->equilibrate = v != 0.0;
+       h->factored = false;
+       return 1;
+     },
+     "takes effect at the next factorisation"},
+    {"use_graph", "HIPFACT_GRAPH", FX_NONE,
+     [](hipfact_handle* h, double v) -> int {  // (drops the graphs whenever it is 0, not only when it becomes 0)
+       h->use_graph = v != 0.0;
+       if (!h->use_graph) drop_graphs(h);
+       return 1;
+     },
+     "0: enqueue the launch sequences instead of replaying captured hipGraphs"},
+    {"factor_top_max", "HIPFACT_FACTOR_TOP", FX_PLANS, OPT_STORE(factor_top_max, (int)v),
+     "0: one launch per phase and level everywhere"},
+    {"pull_max_children", "HIPFACT_PULL_MAX", FX_PLANS, OPT_STORE(pull_max_children, (int)v),
+     "0: extend-add always through the separate assembly kernel"},
+    {"debug_fake_timeout", nullptr, FX_NONE, OPT_STORE(fake_timeouts, (int)v),
+     "test hook for the fallback to the per-level launches"},
+    {"factor_top_levels", nullptr, FX_PLANS, OPT_STORE(factor_top_levels, std::max(0, (int)v)),
+     "at most this many levels in the single-launch top-of-tree factorisation (tests)"},
+    {"solve_slices", "HIPFACT_SOLVE_SLICES", FX_PLANS_IF_CHANGED, OPT_STORE(solve_slices, v != 0.0),
+     "0: one item per front in the fused solve launch (fronts of up to 1024 rows only)"},
+    {"chain_pairs", "HIPFACT_CHAIN_PAIRS", FX_PLANS_IF_CHANGED, OPT_STORE(chain_pairs, v != 0.0),
+     "dense chains: two fronts per trailing update (0: one Schur update per front)"},
+    {"solve_sorted", "HIPFACT_SOLVE_SORTED", FX_PLANS_IF_CHANGED, OPT_STORE(solve_sorted, v != 0.0),
+     "solve items of a level: biggest fronts first (0: plan order)"},
+    {"solve_whole_max", "HIPFACT_SOLVE_WHOLE_MAX", FX_PLANS_IF_CHANGED, OPT_STORE(solve_whole_max, std::max(SOLVE_PREFETCH, (int)v)),
+     "a front stays ONE solve item up to this many panel entries per thread"},
+    {"xupd_blocks", "HIPFACT_XUPD_BLOCKS", FX_GRAPHS_IF_CHANGED, OPT_STORE(xupd_blocks, std::max(1, (int)v)),
+     "workgroups of the x update inside the tree launch"},
+    {"chain_fuse", "HIPFACT_CHAIN_FUSE", FX_PLANS_IF_CHANGED, OPT_STORE(chain_fuse, v != 0.0),
+     "0: single-front levels of a dense chain run pivot block and panel as two launches instead of one small dataflow launch"},
+    {"cg_residual_update", nullptr, FX_GRAPHS_IF_CHANGED, OPT_STORE(cg_residual_update, v != 0.0),
+     "0: the projected CG keeps r as the reference's loop does"},
+    {"cg_device_loop", nullptr, FX_NONE, OPT_STORE(cg_device_loop, v != 0.0),
+     "0: the host reads the dot products of every CG iteration (steihaug_impl)"},
+    {"lz_device_loop", nullptr, FX_NONE, OPT_STORE(lz_device_loop, v != 0.0),
+     "0: GLTR with the host in every iteration (gltr_impl)"},
+    {"xupd_fused", "HIPFACT_XUPD_FUSED", FX_GRAPHS_IF_CHANGED, OPT_STORE(xupd_fused, v != 0.0),
+     "0: x = b_x - A^T y as a launch of its own behind the tree (k_x_saddle)"},
+    {"refine_check_backoff", nullptr, FX_NONE,
+     [](hipfact_handle* h, double v) -> int {
+       h->refine_check_backoff = std::max(1, (int)v);
+       h->check_interval_now = 0;
+       return 1;
+     },
+     "the interval between residual checks is multiplied by this after every check that passes (default 2; 1: fixed interval), up to 64 solves"},
+    {"refine_check_every", nullptr, FX_NONE,
+     [](hipfact_handle* h, double v) -> int {
+       h->refine_check_every = std::max(1, (int)v);
+       h->check_interval_now = 0;
+       return 1;
+     },
+     "residual check on every k-th solve of a well-conditioned factorisation"},
+    {"decide_lazy", "HIPFACT_DECIDE_LAZY", FX_GRAPHS_IF_CHANGED,
+     [](hipfact_handle* h, double v) -> int {
+       const bool changed = h->decide_lazy != (v != 0.0);
+       if (changed) flush_decide(h);  // (the verdict a graph of the old kind left to the next tree launch)
+       h->decide_lazy = v != 0.0;
+       return changed;
+     },
+     "0: every solve graph ends with its own verdict launch"},
+    {"rhs_fused", "HIPFACT_RHS_FUSED", FX_GRAPHS_IF_CHANGED, OPT_STORE(rhs_fused, v != 0.0),
+     "0: k_rhs_saddle in front of the single-launch solve"},
+    {"spanel_fold", "HIPFACT_SPANEL_FOLD", FX_PLANS_IF_CHANGED, OPT_STORE(spanel_fold, v != 0.0),
+     "0: the solve panels in a launch of their own behind the factorisation"},
+    {"spanel_fold_room", nullptr, FX_PLANS_IF_CHANGED, OPT_STORE(spanel_fold_room, (int)v),
+     "solve-panel items dealt in beside a level's own pivot and panel items of the dataflow launch: workgroup slots per level (default 224)"},
+    {"factor_hint_peek", "HIPFACT_HINT_PEEK", FX_NONE, OPT_STORE(factor_hint_peek, v != 0.0),
+     "0: a refactorisation does not look at the last delivered refinement verdict (every first solve graph carries a correction pass)"},
+    {"top_block_breakeven", nullptr, FX_NONE, OPT_STORE(top_block_breakeven, (int)v),
+     "solves of one factorisation from which forming the dense top block of the solve tree pays (default 48)"},
+    {"solve_fused", nullptr, FX_PLANS, OPT_STORE(solve_fused, v != 0.0),
+     "0: the per-level solve kernels on the factor panels"},
+    {"top_block_after", "HIPFACT_TOP_BLOCK_AFTER", FX_PLANS, OPT_STORE(top_block_after, std::max(0, (int)v)),
+     "the top levels of the solve tree as one dense block from this solve of a factorisation on (0: never)"},
+    {"boundary_fast", "HIPFACT_BOUNDARY_FAST", FX_NONE,
+     [](hipfact_handle* h, double v) -> int {
+       h->boundary_fast = v != 0.0;
+       h->sol_prefetched = false;
+       return 1;
+     },
+     "0: host vectors through pageable borrows and three blocking points (round 3)"},
+    {"validate_rhs", nullptr, FX_NONE, OPT_STORE(validate_rhs, v != 0.0),
+     "walk the index array of every sparse right-hand side on the host (debug)"},
+    {"boundary_profile", nullptr, FX_NONE,
+     [](hipfact_handle* h, double v) -> int {
+       int rc = enter(h);
+       if (rc) return rc;
+       h->bd_profile = v != 0.0;
+       if (h->bd_profile)
+         for (hipEvent_t& ev : h->bd_ev)
+           if (!ev) HCHECK(h, hipEventCreate(&ev));
+       h->bd_stage_us = h->bd_queue_us = h->bd_rhs_us = h->bd_device_us = h->bd_d2h_us = h->bd_wait_us = h->bd_copyout_us = 0;
+       h->bd_count = 0;
+       h->bd_pending = false;
+       return 1;
+     },
+     "where solve + solution spend their time (info keys bd_*); resets the sums"},
+    {"superset_vtable", nullptr, FX_NONE,
+     [](hipfact_handle* h, double v) -> int {
+       const bool changed = h->superset_vtable != (v != 0.0);
+       if (changed) h->vj->clear();  // (the dictionary belongs to the mode that built it)
+       h->superset_vtable = v != 0.0;
+       return changed;
+     },
+     "0: no reuse across working sets (every changed pattern is analysed on its own rows; active bounds are still eliminated - exact_pattern = 1 for K as it is)"},
+    {"spmv_stream", nullptr, FX_NONE, OPT_STORE(spmv_stream, v != 0.0),
+     "0: every sparse product through the lanes-per-row kernel (default: matrices from spmv_stream_min entries on are streamed in row blocks)"},
+    {"spmv_stream_min", nullptr, FX_NONE, OPT_STORE(spmv_stream_min, (long long)v),
+     "entries from which a sparse product is streamed (default 4 M: below, the matrix lives in the Infinity Cache)"},
+    {"exact_pattern", nullptr, FX_NONE,
+     [](hipfact_handle* h, double v) -> int {
+       const bool changed = h->exact_pattern != (v != 0.0);
+       if (changed) h->vj->clear();
+       h->exact_pattern = v != 0.0;
+       return changed;
+     },
+     "1: K is analysed exactly as given - no row dictionary, unit rows of active bounds stay in the structure (what hipfact_reduced_matrix needs)"},
+    {"assemble_superset", nullptr, FX_NONE, OPT_STORE(assemble_superset, v != 0.0),
+     "0: hipfact_assemble_kkt analyses every working set on its own rows (no superset plan)"},
+    {"plan_cache", nullptr, FX_NONE,
+     [](hipfact_handle* h, double v) -> int {
+       h->plan_cache_max = std::max(0, (int)v);
+       while ((int)h->cache.size() > h->plan_cache_max) h->cache.pop_back();
+       return 1;
+     },
+     "inactive plan states kept (LRU); 0: one pattern at a time"},
+    {"profile", nullptr, FX_NONE,
+     [](hipfact_handle* h, double v) -> int {
+       if (h->prof.on) prof_collect(h);
+       if (v < 0)
+         for (int c = 0; c < PC_COUNT; ++c) h->prof.ms[c] = 0, h->prof.max_ms[c] = 0, h->prof.cnt[c] = 0;
+       h->prof.tagged.clear();  // (on every call, not only on a reset)
+       h->prof.on = v > 0;
+       return 1;
+     },
+     "event-time every kernel class; value < 0 resets the counters"},
+    {"ordering", nullptr, FX_PLANS, OPT_STORE(prm.ordering, (int)v),
+     "0 nested dissection + AMD leaves (default), 1 AMD on the whole graph, 2 natural"},
+    {"max_children", nullptr, FX_PLANS, OPT_STORE(prm.max_children, (int)v),
+     "relaxed amalgamation keeps fronts at this many children (default 4 = what the pull extend-add takes in one block)"},
+    {"force_generic", nullptr, FX_PLANS, OPT_STORE(prm.force_generic, v != 0.0),
+     "1: no saddle-point structure detection, static 1 x 1 pivots on K as given (symmetric positive definite input: the PSD shim)"},
+    {"dense_mode", nullptr, FX_PLANS, OPT_STORE(prm.dense_mode, std::min(2, std::max(0, (int)v))),
+     "1: late elimination inside the tree (default), 2: low-rank correction, 0: off"},
+    // settings of the environment alone
+    {nullptr, "HIPFACT_DATAFLOW_RETRY", FX_NONE, OPT_STORE(df_retry_every, std::max(0, (int)v)), nullptr},
+    {nullptr, "HIPFACT_CHECK_LAUNCHES", FX_NONE, OPT_STORE(check_launches, v != 0.0), nullptr},
+    {nullptr, "HIPFACT_SOL_SPLIT", FX_NONE, OPT_STORE(sol_split, v != 0.0), nullptr},
+    {nullptr, "HIPFACT_XCD_CLASSES", FX_NONE, OPT_STORE(xcd_classes, std::max(1, std::min(XCD_CLASSES_MAX, (int)v))), nullptr},
+};
+#undef OPT_STORE
+
+// the HIPFACT_* overrides of a new handle's defaults (hipfact_create)
+static void options_from_environment(hipfact_handle* h) {
+  for (const OptionRow& row : kOptions)
+    if (const char* s = row.env ? getenv(row.env) : nullptr) (void)row.set(h, (double)atoi(s));
+}
+
 int hipfact_set_option(hipfact_handle* h, const char* name, double value) {
   if (!h || !name) return HIPFACT_EINVAL;
   {  // the blocked solve keeps its own option with its code (runtime_multi.inc) and documents it with its entry point
@@ -8,239 +221,12 @@ int hipfact_set_option(hipfact_handle* h, const char* name, double value) {
     const int rc = multi_set_option(h, name, value, known);
     if (known) return rc;
   }
-  if (!strcmp(name, "refine_steps")) {  // correction passes carried by every solve graph (default 1; 0: plain solve, no residual); they return at once when the device-side control block reports convergence
-    h->refine_steps = std::max(0, (int)value);
-    h->refine_inline = h->refine_steps;
-    drop_graphs(h);
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "refine_max")) {  // total correction passes of a solve, including those continued by hipfact_solution / hipfact_check (default 10)
-    h->refine_max = std::max(0, (int)value);
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "refine_adaptive")) {  // 0: every in-graph correction pass runs unconditionally
-    h->refine_adaptive = value != 0.0;
-    drop_graphs(h);
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "refine_tol")) {  // forward-error target (default 1e-10): the backward-error tolerance is refine_tol / condition estimate, clamped to [4.5e-16, 1e-12]
-    h->refine_tol = value;
-    drop_graphs(h);
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "fail_omega")) {  // a solve whose refinement stalls above this backward error is reported as singular (default 1e-8)
-    h->fail_omega = value;
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "static_pivot")) {  // 0: a zero / wrongly signed pivot is HIPFACT_ESINGULAR at once (rounds 1 - 5)
-    h->static_pivot = value != 0.0;
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "static_pivot_delta")) {  // the shift of every pivot of A A^T when a rank-deficient working set is factored with static pivoting (default 1e-8; rows are equilibrated to unit norm)
-    h->static_delta = value > 0.0 ? value : 1e-8;
-    drop_graphs(h);  // (the captured sequence of a shifted factorisation holds the shift)
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "equilibrate")) {  // takes effect at the next factorisation
-    h->equilibrate = value != 0.0;
-    drop_graphs(h);
-    h->factored = false;
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "use_graph")) {  // 0: enqueue the launch sequences instead of replaying captured hipGraphs
-    h->use_graph = value != 0.0;
-    if (!h->use_graph) drop_graphs(h);
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "factor_top_max")) {  // 0: one launch per phase and level everywhere
-    h->factor_top_max = (int)value;
-    invalidate_plans(h);
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "pull_max_children")) {  // 0: extend-add always through the separate assembly kernel
-    h->pull_max_children = (int)value;
-    invalidate_plans(h);
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "debug_fake_timeout")) {  // test hook for the fallback to the per-level launches
-    h->fake_timeouts = (int)value;
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "factor_top_levels")) {  // at most this many levels in the single-launch top-of-tree factorisation (tests)
-    h->factor_top_levels = std::max(0, (int)value);
-    invalidate_plans(h);
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "solve_slices")) {  // 0: one item per front in the fused solve launch (fronts of up to 1024 rows only)
-    if (h->solve_slices != (value != 0.0)) invalidate_plans(h);
-    h->solve_slices = value != 0.0;
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "chain_pairs")) {  // dense chains: two fronts per trailing update (0: one Schur update per front)
-    if (h->chain_pairs != (value != 0.0)) invalidate_plans(h);
-    h->chain_pairs = value != 0.0;
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "solve_sorted")) {  // solve items of a level: biggest fronts first (0: plan order)
-    if (h->solve_sorted != (value != 0.0)) invalidate_plans(h);
-    h->solve_sorted = value != 0.0;
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "solve_whole_max")) {  // a front stays ONE solve item up to this many panel entries per thread
-    const int v = std::max(SOLVE_PREFETCH, (int)value);
-    if (h->solve_whole_max != v) invalidate_plans(h);
-    h->solve_whole_max = v;
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "xupd_blocks")) {  // workgroups of the x update inside the tree launch
-    const int v = std::max(1, (int)value);
-    if (h->xupd_blocks != v) drop_graphs(h);
-    h->xupd_blocks = v;
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "chain_fuse")) {  // 0: single-front levels of a dense chain run pivot block and panel as two launches instead of one small dataflow launch
-    if (h->chain_fuse != (value != 0.0)) invalidate_plans(h);
-    h->chain_fuse = value != 0.0;
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "cg_residual_update")) {  // 0: the projected CG keeps r as the reference's loop does
-    if (h->cg_residual_update != (value != 0.0)) drop_graphs(h);
-    h->cg_residual_update = value != 0.0;
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "cg_device_loop")) {  // 0: the host reads the dot products of every CG iteration (steihaug_impl)
-    h->cg_device_loop = value != 0.0;
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "lz_device_loop")) {  // 0: GLTR with the host in every iteration (gltr_impl)
-    h->lz_device_loop = value != 0.0;
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "xupd_fused")) {  // 0: x = b_x - A^T y as a launch of its own behind the tree (k_x_saddle)
-    if (h->xupd_fused != (value != 0.0)) drop_graphs(h);
-    h->xupd_fused = value != 0.0;
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "refine_check_backoff")) {  // the interval between residual checks is multiplied by this after every check that passes (default 2; 1: fixed interval), up to 64 solves
-    h->refine_check_backoff = std::max(1, (int)value);
-    h->check_interval_now = 0;
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "refine_check_every")) {  // residual check on every k-th solve of a well-conditioned factorisation
-    h->refine_check_every = std::max(1, (int)value);
-    h->check_interval_now = 0;
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "decide_lazy")) {  // 0: every solve graph ends with its own verdict launch
-    if (h->decide_lazy != (value != 0.0)) {
-      flush_decide(h);
-      drop_graphs(h);
-    }
-    h->decide_lazy = value != 0.0;
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "rhs_fused")) {  // 0: k_rhs_saddle in front of the single-launch solve
-    if (h->rhs_fused != (value != 0.0)) drop_graphs(h);
-    h->rhs_fused = value != 0.0;
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "spanel_fold")) {  // 0: the solve panels in a launch of their own behind the factorisation
-    if (h->spanel_fold != (value != 0.0)) invalidate_plans(h);
-    h->spanel_fold = value != 0.0;
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "spanel_fold_room")) {  // solve-panel items dealt in beside a level's own pivot and panel items of the dataflow launch: workgroup slots per level (default 224)
-    if (h->spanel_fold_room != (int)value) invalidate_plans(h);
-    h->spanel_fold_room = (int)value;
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "factor_hint_peek")) {  // 0: a refactorisation does not look at the last delivered refinement verdict (every first solve graph carries a correction pass)
-    h->factor_hint_peek = value != 0.0;
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "top_block_breakeven")) {  // solves of one factorisation from which forming the dense top block of the solve tree pays (default 48)
-    h->top_block_breakeven = (int)value;
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "solve_fused")) {  // 0: the per-level solve kernels on the factor panels
-    h->solve_fused = value != 0.0;
-    invalidate_plans(h);
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "top_block_after")) {  // the top levels of the solve tree as one dense block from this solve of a factorisation on (0: never)
-    h->top_block_after = std::max(0, (int)value);
-    invalidate_plans(h);
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "boundary_fast")) {  // 0: host vectors through pageable borrows and three blocking points (round 3)
-    h->boundary_fast = value != 0.0;
-    h->sol_prefetched = false;
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "validate_rhs")) {  // walk the index array of every sparse right-hand side on the host (debug)
-    h->validate_rhs = value != 0.0;
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "boundary_profile")) {  // where solve + solution spend their time (info keys bd_*); resets the sums
-    int rc = enter(h);
-    if (rc) return rc;
-    h->bd_profile = value != 0.0;
-    if (h->bd_profile)
-      for (hipEvent_t& ev : h->bd_ev)
-        if (!ev) HCHECK(h, hipEventCreate(&ev));
-    h->bd_stage_us = h->bd_queue_us = h->bd_rhs_us = h->bd_device_us = h->bd_d2h_us = h->bd_wait_us = h->bd_copyout_us = 0;
-    h->bd_count = 0;
-    h->bd_pending = false;
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "superset_vtable")) {  // 0: no reuse across working sets (every changed pattern is analysed on its own rows; active bounds are still eliminated - exact_pattern = 1 for K as it is)
-    if (h->superset_vtable != (value != 0.0)) h->vj->clear();  // (the dictionary belongs to the mode that built it)
-    h->superset_vtable = value != 0.0;
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "spmv_stream")) {  // 0: every sparse product through the lanes-per-row kernel (default: matrices from spmv_stream_min entries on are streamed in row blocks)
-    h->spmv_stream = value != 0.0;
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "spmv_stream_min")) {  // entries from which a sparse product is streamed (default 4 M: below, the matrix lives in the Infinity Cache)
-    h->spmv_stream_min = (long long)value;
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "exact_pattern")) {  // 1: K is analysed exactly as given - no row dictionary, unit rows of active bounds stay in the structure (what hipfact_reduced_matrix needs)
-    if (h->exact_pattern != (value != 0.0)) h->vj->clear();
-    h->exact_pattern = value != 0.0;
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "assemble_superset")) {  // 0: hipfact_assemble_kkt analyses every working set on its own rows (no superset plan)
-    h->assemble_superset = value != 0.0;
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "plan_cache")) {  // inactive plan states kept (LRU); 0: one pattern at a time
-    h->plan_cache_max = std::max(0, (int)value);
-    while ((int)h->cache.size() > h->plan_cache_max) h->cache.pop_back();
-    return HIPFACT_OK;
-  }
-  if (!strcmp(name, "profile")) {  // event-time every kernel class; value < 0 resets the counters
-    if (h->prof.on) prof_collect(h);
-    if (value < 0)
-      for (int c = 0; c < PC_COUNT; ++c) h->prof.ms[c] = 0, h->prof.max_ms[c] = 0, h->prof.cnt[c] = 0;
-      h->prof.tagged.clear();
-    h->prof.on = value > 0;
-    return HIPFACT_OK;
-  }
-  bool plan_opt = true;
-  if (!strcmp(name, "ordering"))  // 0 nested dissection + AMD leaves (default), 1 AMD on the whole graph, 2 natural
-    h->prm.ordering = (int)value;
-  else if (!strcmp(name, "max_children"))  // relaxed amalgamation keeps fronts at this many children (default 4 = what the pull extend-add takes in one block)
-    h->prm.max_children = (int)value;
-  else if (!strcmp(name, "force_generic"))  // 1: no saddle-point structure detection, static 1 x 1 pivots on K as given (symmetric positive definite input: the PSD shim)
-    h->prm.force_generic = value != 0.0;
-  else if (!strcmp(name, "dense_mode"))  // 1: late elimination inside the tree (default), 2: low-rank correction, 0: off
-    h->prm.dense_mode = std::min(2, std::max(0, (int)value));
-  else
-    plan_opt = false;
-  if (plan_opt) {
-    invalidate_plans(h);  // next set_matrix re-analyses
+  for (const OptionRow& row : kOptions) {
+    if (!row.name || strcmp(name, row.name)) continue;
+    const int changed = row.set(h, value);
+    if (changed < 0) return changed;
+    if (row.effect == FX_GRAPHS || (row.effect == FX_GRAPHS_IF_CHANGED && changed)) drop_graphs(h);
+    if (row.effect == FX_PLANS || (row.effect == FX_PLANS_IF_CHANGED && changed)) invalidate_plans(h);
     return HIPFACT_OK;
   }
   h->error = std::string("unknown option: ") + name;

@@ -42,7 +42,7 @@ def test_option_table_of_the_header_is_generated_from_the_source():
 
     subprocess.check_call([sys.executable, os.path.join(ROOT, "scripts", "gen_option_table.py"), "--check"])
     src = open(os.path.join(ROOT, "sleqp_amd", "csrc", "abi_options.inc")).read().split("int hipfact_debug_copy")[0]
-    names = re.findall(r'!strcmp\(name, "(\w+)"\)', src)
+    names = re.findall(r'^    \{"(\w+)",', src, flags=re.M)  # the named rows of kOptions
     assert len(names) == len(set(names)) <= 50, len(names)
     # no compile-time experiment switches in the device sources
     for f in _files("sleqp_amd"):

@@ -32,7 +32,7 @@ def test_null_handle_is_rejected(hipfact_lib):
 def test_option_table_is_unchanged():
     subprocess.check_call([sys.executable, os.path.join(ROOT, "scripts", "gen_option_table.py"), "--check"])
     src = open(os.path.join(ROOT, "sleqp_amd", "csrc", "abi_options.inc")).read().split("int hipfact_debug_copy")[0]
-    names = re.findall(r'!strcmp\(name, "(\w+)"\)', src)
+    names = re.findall(r'^    \{"(\w+)",', src, flags=re.M)  # the named rows of kOptions
     assert len(names) == len(set(names)) == 47, len(names)
     assert not [n for n in names if n.startswith("multi_")]
 
