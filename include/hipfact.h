@@ -581,7 +581,7 @@ int hipfact_set_option(hipfact_handle* h, const char* name, double value);
 int hipfact_get_info(const hipfact_handle* h, const char* name, double* value);
 
 /* Debugging aid (tests, scripts): copies the first `bytes` of a named device buffer of the active plan
- * state to the host ("L", "SPf", "SPb", "sitems", "y", "xhat", "ysol", "uvec", "dscale"; "mY": the m x 16 block of
+ * state to the host ("L", "SPf", "sitems", "y", "xhat", "ysol", "uvec", "dscale"; "mY": the m x 16 block of
  * the last pass of the blocked solve, pivot order), or of one of the
  * active host plan's front arrays ("perm", "sn_c0", "sn_r", "sn_rowptr", "sn_rows", "sn_Loff", "late_cols", "sn_level", "dense_cols";
  * int32, except int64 for sn_rowptr and sn_Loff). */

@@ -91,7 +91,7 @@ def run():
     t = (t - t[:, 0].min()) / 100.0  # 100 MHz
     P = Plan(lib, N, cp, ri, vx)
     # level of the item at each forward position (a sliced front has several items): from the items themselves
-    item_dt = np.dtype([("spf", "<i8"), ("spb", "<i8"), ("uoff", "<i8"), ("rowoff", "<i8"), ("c0", "<i4"), ("w", "<i4"), ("r", "<i4"),
+    item_dt = np.dtype([("spf", "<i8"), ("spd", "<i8"), ("uoff", "<i8"), ("rowoff", "<i8"), ("c0", "<i4"), ("w", "<i4"), ("r", "<i4"),
                         ("nchild", "<i4"), ("Qf", "<i4"), ("Ef", "<i4"), ("Pb", "<i4"), ("Eb", "<i4"), ("c_uoff", "<i8", 4),
                         ("c_invoff", "<i4", 4), ("Loff", "<i8"), ("xbegin", "<i4"), ("xend", "<i4"), ("a0", "<i4"), ("a1", "<i4"),
                         ("sl", "<i4"), ("nsl", "<i4"), ("poff", "<i8"), ("plevel", "<i4"), ("pad_", "<i4")])

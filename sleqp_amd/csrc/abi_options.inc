@@ -260,7 +260,6 @@ int hipfact_debug_copy(hipfact_handle* h, const char* name, void* out, size_t by
   if (!strcmp(name, "L")) b = &h->d_L;
   else if (!strcmp(name, "U")) b = &h->d_U;
   else if (!strcmp(name, "SPf")) b = &h->d_SPf;
-  else if (!strcmp(name, "SPb")) b = &h->d_SPb;
   else if (!strcmp(name, "sitems")) b = &h->d_sitems;
   else if (!strcmp(name, "y")) b = &h->d_y;
   else if (!strcmp(name, "xhat")) b = &h->d_xhat;
@@ -393,7 +392,7 @@ int hipfact_get_info(const hipfact_handle* h, const char* name, double* value) {
   INFO("num_perturbed", h->num_perturbed) INFO("static_pivot_runs", h->static_pivot_runs) INFO("static_pivot_shift", h->reg_delta)
   INFO("num_zero_pivots", h->info_host[INFO_ZERO_PIVOT]) INFO("num_neg_pivots", h->info_host[INFO_NEG_PIVOT])
   INFO("cache_hits", h->cache_hits) INFO("plan_swaps", h->plan_swaps) INFO("plans_cached", h->cache.size())
-  INFO("no_dataflow", h->no_dataflow) INFO("dataflow_fallbacks", h->dataflow_fallbacks) INFO("turn_waits", (double)h->turn_waits) INFO("dataflow_rearmed", h->dataflow_rearmed) INFO("fused_solve", h->fused_solve) INFO("spanel_folded", h->sp_folded) INFO("solve_items", h->n_sitems) INFO("chain_levels_fused", [&] { int c = 0; for (const LevelInfo& li : h->levels) c += li.mini_cnt > 0; return c; }()) INFO("solve_panel_bytes", h->sp_bytes) INFO("spf_bytes", (double)h->d_SPf.bytes) INFO("spb_bytes", (double)h->d_SPb.bytes) INFO("sitem_bytes", (double)sizeof(SolveItem)) INFO("N_internal", P.N) INFO("maps_on", h->maps_on) INFO("m_struct", h->m_struct) INFO("analyses", h->analyses) INFO("num_factor", h->num_factor) INFO("cg_device_runs", h->cg_device_runs) INFO("cg_device_fallbacks", h->cg_device_fallbacks) INFO("lz_device_runs", h->lz_device_runs) INFO("lz_device_fallbacks", h->lz_device_fallbacks) INFO("lz_device_iterations", h->lz_device_iterations) INFO("lsqr_runs", h->lsqr_runs) INFO("lsqr_iters", h->lsqr_iters) INFO("dense_columns", h->nd) INFO("late_columns", P.n_late) INFO("late_rows", P.n_late_rows) INFO("m_rows", P.saddle ? P.my : P.m) INFO("vtable_rows", h->vj->rows()) INFO("vtable_retries", h->vtable_retries) INFO("dense_fallbacks", h->dense_fallbacks) INFO("dense_probes", h->dense_probes) INFO("top_block_cols", h->tb_nT) INFO("top_block_below", h->tb_nfb) INFO("top_block_levels", h->tb_levels) INFO("top_block_items", h->tb_ntf) INFO("top_block_builds", h->tb_builds) INFO("top_block_active", h->tb_valid) INFO("superset_vtable", h->superset_vtable) INFO("exact_pattern", h->exact_pattern) INFO("spmv_stream", h->spmv_stream)
+  INFO("no_dataflow", h->no_dataflow) INFO("dataflow_fallbacks", h->dataflow_fallbacks) INFO("turn_waits", (double)h->turn_waits) INFO("dataflow_rearmed", h->dataflow_rearmed) INFO("fused_solve", h->fused_solve) INFO("spanel_folded", h->sp_folded) INFO("solve_items", h->n_sitems) INFO("chain_levels_fused", [&] { int c = 0; for (const LevelInfo& li : h->levels) c += li.mini_cnt > 0; return c; }()) INFO("solve_panel_bytes", h->sp_bytes) INFO("spf_bytes", (double)h->d_SPf.bytes) INFO("sitem_bytes", (double)sizeof(SolveItem)) INFO("N_internal", P.N) INFO("maps_on", h->maps_on) INFO("m_struct", h->m_struct) INFO("analyses", h->analyses) INFO("num_factor", h->num_factor) INFO("cg_device_runs", h->cg_device_runs) INFO("cg_device_fallbacks", h->cg_device_fallbacks) INFO("lz_device_runs", h->lz_device_runs) INFO("lz_device_fallbacks", h->lz_device_fallbacks) INFO("lz_device_iterations", h->lz_device_iterations) INFO("lsqr_runs", h->lsqr_runs) INFO("lsqr_iters", h->lsqr_iters) INFO("dense_columns", h->nd) INFO("late_columns", P.n_late) INFO("late_rows", P.n_late_rows) INFO("m_rows", P.saddle ? P.my : P.m) INFO("vtable_rows", h->vj->rows()) INFO("vtable_retries", h->vtable_retries) INFO("dense_fallbacks", h->dense_fallbacks) INFO("dense_probes", h->dense_probes) INFO("top_block_cols", h->tb_nT) INFO("top_block_below", h->tb_nfb) INFO("top_block_levels", h->tb_levels) INFO("top_block_items", h->tb_ntf) INFO("top_block_builds", h->tb_builds) INFO("top_block_active", h->tb_valid) INFO("superset_vtable", h->superset_vtable) INFO("exact_pattern", h->exact_pattern) INFO("spmv_stream", h->spmv_stream)
   INFO("boundary_fast", h->boundary_fast) INFO("bd_count", h->bd_count) INFO("bd_stage_us", h->bd_stage_us) INFO("bd_queue_us", h->bd_queue_us) INFO("bd_rhs_us", h->bd_rhs_us) INFO("bd_device_us", h->bd_device_us) INFO("bd_d2h_us", h->bd_d2h_us) INFO("bd_wait_us", h->bd_wait_us) INFO("bd_copyout_us", h->bd_copyout_us)
   INFO("multi_solves", h->multi_solves) INFO("multi_cols", h->multi_cols) INFO("multi_blocks", h->multi_blocks)
   INFO("multi_passes", h->multi_passes) INFO("multi_single_cols", h->multi_single_cols) INFO("multi_failed_col", h->multi_failed_col)

@@ -82,16 +82,18 @@ struct TopFItem {
 };
 
 // One front of the fused solve launch (k_solve_tree): everything a workgroup needs in ONE uniform
-// load.  The front's factor is stored twice in "solve panel" form, S = [X; -W] with X = inv(L11)
+// load.  The front's factor is stored once more in "solve panel" form, S = [X; -W] with X = inv(L11)
 // (unit lower) and W = L21 X, so that each sweep is a single product with no dependency between the
 // pivot rows and the update rows (forward: [x^; u] = S f_top + [0; f_below]; backward:
-// x = S^T [D^-1 x^; g]):
-//   forward copy   thread (row i, column class q):   entries S[i, q + Qf e],        e < Ef
-//   backward copy  thread (column k, row class p):   entries S[p + Pb e, k] (rows < w divided by d), e < Eb
-// both laid out thread-major (entry e of thread t at e * threads + t): every load instruction of the
-// workgroup is one contiguous run, and the entries live in registers across the dependency wait.
+// x = S^T [D^-1 x^; g]).  ONE copy serves both sweeps: S column-major with leading dimension ro (the
+// item's rows), Ef * Qf columns (those from w on are zero), behind it - slice 0 only - w doubles 1 / d_i:
+//   forward   thread (row i, column class q), tid = q ro + i:  entries S[i, q + Qf e],  e < Ef
+//             (entry e of thread t at e * threads + t: every load instruction is one contiguous run)
+//   backward  thread (column k, row class p), tid = k Pb + p:  entries S[p + Pb e, k],  e < Eb, rows < w
+//             times 1 / d (a load instruction covers runs of Pb consecutive doubles, one per column)
+// and the entries live in registers across the dependency wait.
 struct SolveItem {
-  long long spf, spb;        // offsets of the two copies in the solve-panel arenas
+  long long spf, spd;        // offsets in the solve-panel arena: the panel; its tail of 1 / d_i (slice 0)
   long long uoff, rowoff;    // own update vector; row structure (front rows -> pivot indices)
   int c0, w, r, nchild;
   int Qf, Ef, Pb, Eb;
@@ -99,7 +101,7 @@ struct SolveItem {
   int c_invoff[MAXCH];       // children's inverse relative indices (which update row lands on front row i)
   long long Loff;            // the front's panel (source of the solve panels)
   int xbegin, xend;          // children beyond the first MAXCH: entries [xbegin, xend) of the overflow lists
-  // A front with more than 1024 rows is several items (slices), each with thread-major copies of ITS rows of S:
+  // A front with more than 1024 rows is several items (slices), each with a panel of ITS rows of S:
   // slice 0 the pivot rows and the update rows [0, a1), slice sl > 0 the update rows [a0, a1).  Forward: every
   // slice forms the front's f_top itself and posts its rows of [x^; u]; backward: the slices sl > 0 post their
   // w partial sums (they only need their ancestors' entries: long before the parent is done), slice 0 polls and

@@ -47,7 +47,7 @@ __device__ __forceinline__ void flag_publish_add(int* __restrict__ addr) {
 // its own behind this one).  Fronts of this launch wait for their pivot and panel workgroups, all others were
 // finished before the launch.
 __device__ __forceinline__ void dev_build_solve_panel(const SolveItem& T, const double* __restrict__ L,
-                                                      double* __restrict__ SPf, double* __restrict__ SPb, double* lds);
+                                                      double* __restrict__ SPf, double* lds);
 
 // LDS: the largest of the roles (pivot: dd | A | Y | scratch | maps; panel: dd | X | maps;
 // Schur: dd | two teams of {SI, SJ, maps}; solve panels: X | 1 / d | tiles | offsets)
@@ -56,8 +56,7 @@ __global__ __launch_bounds__(512) void k_factor_top(const TopFItem* __restrict__
                                                    const int* __restrict__ inv, const int* __restrict__ rel,
                                                    int* __restrict__ bdone, int* __restrict__ cdone,
                                                    int* __restrict__ ddone, double* __restrict__ xarena,
-                                                   const SolveItem* __restrict__ sitems, double* __restrict__ SPf,
-                                                   double* __restrict__ SPb) {
+                                                   const SolveItem* __restrict__ sitems, double* __restrict__ SPf) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const TopFItem& T = items[blockIdx.x];
   const FrontItem& S = T.it;
@@ -84,7 +83,7 @@ __global__ __launch_bounds__(512) void k_factor_top(const TopFItem* __restrict__
       __syncthreads();
     }
     TRW(1);
-    dev_build_solve_panel(sitems[S.part], L, SPf, SPb, lds);
+    dev_build_solve_panel(sitems[S.part], L, SPf, lds);
 #ifdef HIPFACT_TRACE
     __syncthreads();
 #endif
@@ -130,18 +129,11 @@ __global__ __launch_bounds__(512) void k_factor_top(const TopFItem* __restrict__
       const SolveItem& Q = sitems[T.sidx - 1];
       const int w = c.w, r = c.r, lda = c.lda;
       const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-      const long long TSf = (long long)r * Q.Qf, TSb = (long long)w * Q.Pb;
-      double* __restrict__ sf = SPf + Q.spf;
-      double* __restrict__ sb = SPb + Q.spb;
-      for (int k = wave; k < w; k += 8) {
-        const long long of = (long long)(k / Q.Qf) * TSf + (long long)(k % Q.Qf) * r;
-        for (int i = k + lane; i < w; i += 64) sf[of + i] = (i == k) ? 1.0 : c.A[i + k * lda];
-      }
-      for (int i = wave; i < w; i += 8) {
-        const double di = 1.0 / c.dd[i];
-        const long long ob = (long long)(i / Q.Pb) * TSb + (long long)(i % Q.Pb) * w;
-        for (int k = lane; k <= i; k += 64) sb[ob + k] = ((i == k) ? 1.0 : c.A[i + k * lda]) * di;
-      }
+      double* __restrict__ sf = SPf + Q.spf;  // column-major, leading dimension r (= w here)
+      double* __restrict__ sd = SPf + Q.spd;  // the tail of 1 / d_i
+      for (int k = wave; k < w; k += 8)
+        for (int i = k + lane; i < w; i += 64) sf[(long long)k * r + i] = (i == k) ? 1.0 : c.A[i + k * lda];
+      for (int i = threadIdx.x; i < w; i += blockDim.x) sd[i] = 1.0 / c.dd[i];
     }
   } else if (T.role == 1) {
     // panel rows incl. the children's contributions first (the children finished long ago),

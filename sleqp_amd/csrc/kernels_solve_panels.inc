@@ -6,13 +6,14 @@
 // (part of the factorisation translation unit kernels_factor.hip)
 
 // Solve panels of one front from its factored panel (X = inv(L11) strictly lower + pivots on the
-// diagonal, L21 below): W = L21 X on the matrix cores, then both thread-major copies.  One workgroup
+// diagonal, L21 below): W = L21 X on the matrix cores, then the panel (column-major, leading dimension
+// ro: what both sweeps of k_solve_tree read) and, for slice 0, its tail of 1 / d_i.  One workgroup
 // (8 waves) per front, X in LDS; a wave owns 16-row strips of L21, requests its whole strip (the A
 // operands of every step) in one batch, and keeps the strip of W (up to 8 tiles of 16 x 16) in its
 // accumulators.  Padding entries of the arenas and the zeros above the diagonal of X are zero from
 // the upload of the plan and never written.
 __device__ __forceinline__ void dev_build_solve_panel(const SolveItem& T, const double* __restrict__ L,
-                                                      double* __restrict__ SPf, double* __restrict__ SPb, double* lds) {
+                                                      double* __restrict__ SPf, double* lds) {
   const int w = T.w, r = T.r;
   // the item's rows of S: the pivot rows (slice 0 only) and the update rows [ua, ua + u) of the front
   const int ua = T.a0, u = T.a1 - T.a0;
@@ -26,10 +27,6 @@ __device__ __forceinline__ void dev_build_solve_panel(const SolveItem& T, const 
   double* X = lds;                           // wp x wp (ld ldx), unit lower, zero padded
   double* dinv = X + (size_t)ldx * wp;       // wp
   double* tile = dinv + wp + (size_t)wave * (16 * 17);  // per wave: one 16 x 16 tile, row stride 17
-  // where column k of the forward copy and row i of the backward copy start (integer divisions are ~40
-  // instructions each on this hardware: once per column / row instead of once per element)
-  long long* offF = reinterpret_cast<long long*>(dinv + wp + (SPB / 64) * (16 * 17));  // wp
-  long long* offB = offF + wp;                                                          // ro
   // the first strip of this wave: requested before X is staged, so that both arrive together
   const int nstrip = (u + 15) >> 4;
   double av[32];
@@ -64,13 +61,9 @@ __device__ __forceinline__ void dev_build_solve_panel(const SolveItem& T, const 
       }
   }
   for (int k = tid; k < wp; k += SPB) dinv[k] = (k < w) ? 1.0 / Pn[k + (long long)k * r] : 1.0;
-  const int Qf = T.Qf, Pb = T.Pb;
-  const long long TSf = (long long)ro * Qf, TSb = (long long)w * Pb;
-  for (int k = tid; k < wp; k += SPB) offF[k] = (long long)(k / Qf) * TSf + (long long)(k % Qf) * ro;
-  for (int i = tid; i < ro; i += SPB) offB[i] = (long long)(i / Pb) * TSb + (long long)(i % Pb) * w;
   __syncthreads();
-  double* __restrict__ sf = SPf + T.spf;
-  double* __restrict__ sb = SPb + T.spb;
+  double* __restrict__ sf = SPf + T.spf;  // column k at k * ro (a panel is at most 128 x 1152: int indices)
+  const int lb = lk * ro + top + li;      // this lane's entry of a turned tile: column lk (+ 16 kt + 4 q), row li
   // update rows: S[w + a, k] = -W[a, k], W = L21 X.  Strip of 16 rows per wave and turn.
   for (int st = wave; st < nstrip; st += SPB / 64) {
     const int a0 = st << 4;
@@ -99,42 +92,38 @@ __device__ __forceinline__ void dev_build_solve_panel(const SolveItem& T, const 
         av[t] = (rowok && j < w) ? Lr[(long long)j * r] : 0.0;
       }
     }
-    // finished strip: tile by tile through the wave's LDS tile, row-major for the backward copy
-    // (16 consecutive columns per store) and column-major for the forward copy (16 consecutive rows)
+    // finished strip: tile by tile through the wave's LDS tile, which turns it so that a store runs along 16
+    // consecutive rows of a column
 #pragma unroll
     for (int kt = 0; kt < 8; ++kt) {
       if (kt >= nbk) continue;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const int row = lk + 4 * q, k = 16 * kt + li, i = top + a0 + row;
+        const int row = lk + 4 * q;
         tile[row * 17 + li] = -acc[kt][q];
-        if (a0 + row < u && k < w) SPST(&sb[offB[i] + k], -acc[kt][q]);
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const int row = li, col = lk + 4 * q, k = 16 * kt + col, i = top + a0 + row;
-        if (a0 + row < u && k < w) SPST(&sf[offF[k] + i], tile[row * 17 + col]);
+        const int row = li, col = lk + 4 * q, k = 16 * kt + col;
+        if (a0 + row < u && k < w) SPST(&sf[lb + ((16 * kt + 4 * q) * ro + a0)], tile[row * 17 + col]);
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
     }
   }
-  // pivot rows: S[i, k] = X[i, k] (lower triangle); backward copy divided by d_i.  Two passes so that each
-  // copy is written along its contiguous direction (rows i forward, columns k backward).
+  // pivot rows: S[i, k] = X[i, k] (lower triangle), and 1 / d_i behind the panel (the backward sweep scales the pivot
+  // rows with it as it loads them)
   if (top == 0) return;  // (the pivot rows belong to slice 0)
   for (int k = wave; k < w; k += SPB / 64)
-    for (int i = k + lane; i < w; i += 64) SPST(&sf[offF[k] + i], X[i + k * ldx]);
-  for (int i = wave; i < w; i += SPB / 64) {
-    const double di = dinv[i];
-    for (int k = lane; k <= i; k += 64) SPST(&sb[offB[i] + k], X[i + k * ldx] * di);
-  }
+    for (int i = k + lane; i < w; i += 64) SPST(&sf[k * ro + i], X[i + k * ldx]);
+  double* __restrict__ sd = SPf + T.spd;
+  for (int i = tid; i < w; i += SPB) SPST(&sd[i], dinv[i]);
 }
 __global__ __launch_bounds__(SPB) void k_build_solve_panels(const SolveItem* __restrict__ items,
-                                                            const double* __restrict__ L, double* __restrict__ SPf,
-                                                            double* __restrict__ SPb) {
+                                                            const double* __restrict__ L, double* __restrict__ SPf) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
-  dev_build_solve_panel(items[blockIdx.x], L, SPf, SPb, lds);
+  dev_build_solve_panel(items[blockIdx.x], L, SPf, lds);
 }

@@ -11,8 +11,8 @@
 // after level.  With W = L21 X both sweeps are ONE product per front:
 //     forward   [x^; u] = [X; -W] f_top + [0; f_below]
 //     backward  x = [X; -W]^T [D^-1 x^; g]          (since X^T L21^T = W^T)
-// The panels are stored twice, thread-major (SolveItem), so that a thread's share of the front sits
-// in registers BEFORE its dependency wait and the product afterwards is a run of register FMAs
+// The panels are stored ONCE, column-major (SolveItem), and read by both sweeps: a thread's share of the front
+// sits in registers BEFORE its dependency wait and the product afterwards is a run of register FMAs
 // against a vector in LDS; the only cross-thread step is the sum of Qf (Pb) partials through LDS.
 // 2 x nfronts workgroups: blocks [0, nf) forward, children before parents; blocks [nf, 2 nf)
 // backward, parents before children.  Workgroups are dispatched in index order and only ever wait
@@ -252,7 +252,7 @@ __device__ __forceinline__ void dev_solve_fwd(const SolveItem& T, const double* 
 }
 
 template <bool DEFER_RESET>
-__device__ __forceinline__ void dev_solve_bwd(const SolveItem& T, const double* __restrict__ SPb,
+__device__ __forceinline__ void dev_solve_bwd(const SolveItem& T, const double* __restrict__ SPf,
                                               const int* __restrict__ rows, double* __restrict__ y,
                                               double* __restrict__ xhat, double* __restrict__ uvec,
                                               double* __restrict__ ysol, double* __restrict__ spart, double* lds,
@@ -262,30 +262,45 @@ __device__ __forceinline__ void dev_solve_bwd(const SolveItem& T, const double* 
   const int w = T.w, P = T.Pb, E = T.Eb;
   const int a0 = T.a0, nu = T.a1 - T.a0;
   const int top = (T.sl == 0) ? w : 0;
-  const int ro = top + nu;  // rows of this item's panel copy: [pivot rows (slice 0);] update rows [a0, a1)
+  const int ro = top + nu;  // rows of this item's panel: [pivot rows (slice 0);] update rows [a0, a1)
   const int TS = w * P;
   const bool active = tid < TS;
-  const int p = active ? tid / w : 0;
+  // thread (column k, row class p) = k P + p: the P threads of a column read P consecutive rows of it
+  const int k = active ? tid / P : 0;
+  const int p = tid - k * P;
   double* tv = lds;         // ro: [x^; g]
-  double* part = lds + ro;  // P * w <= 1024
-  const double* __restrict__ sp = SPb + T.spb + tid;
+  double* part = lds + ro;  // P * w <= 1024; until the product: 1 / d_i of the pivot rows
+  // (requested in front of the panel: what the first look at the awaited entry depends on)
+  const int myrow = (tid >= top && tid < ro) ? rows[T.rowoff + w + a0 + (tid - top)] : -1;
+  const double dv = (tid < top) ? SPf[T.spd + tid] : 0.0;
+  const double* __restrict__ sp = SPf + T.spf + (long long)k * ro + p;
   double pv[SOLVE_PREFETCH];
-  // (the same for the backward copy: column k of X^T D^-1 holds nothing in the pivot rows in front of row k - for
-  // fixed (p, e) the threads that skip are a suffix of consecutive columns)
-  const int mycol_b = tid - p * w;
+  // (X = inv(L11) is lower triangular: column k holds nothing in the pivot rows in front of row k - the contiguous head
+  // of the column is not fetched; rows from ro on do not exist: the last row class of a column may be short)
 #pragma unroll
   for (int e = 0; e < SOLVE_PREFETCH; ++e) {
     const int row = p + P * e;
-    pv[e] = (active && e < E && !(row < top && row < mycol_b)) ? sp[(long long)e * TS] : 0.0;
+    pv[e] = (active && e < E && row < ro && !(row < top && row < k)) ? sp[P * e] : 0.0;
   }
-  const int myrow = (tid >= top && tid < ro) ? rows[T.rowoff + w + a0 + (tid - top)] : -1;
   // x^ from the forward item of this front (the root turns around here), the ancestors' solution
-  // entries from their backward items: polled one by one, no flag, no fence
-  if (tid < top) {
-    tv[tid] = poll_f64(xhat + T.c0 + tid, info);
-    sent_f64_agent(xhat + T.c0 + tid);  // single consumer: slot ready for the next solve
-  } else if (myrow >= 0) {
-    tv[tid] = poll_f64(ysol + myrow, info);
+  // entries from their backward items: polled one by one, no flag, no fence.  The first look travels beside the
+  // panel; the pivot rows are divided by d while it does (S[i, k] / d_i, rounded once: the entry the backward sweep
+  // has always multiplied with), so that behind the wait there is the product and nothing else.
+  const double* __restrict__ slot = (tid < top) ? xhat + T.c0 + tid : (myrow >= 0 ? ysol + myrow : nullptr);
+  unsigned long long bits = slot ? __hip_atomic_load(reinterpret_cast<const unsigned long long*>(slot), __ATOMIC_RELAXED,
+                                                     __HIP_MEMORY_SCOPE_AGENT)
+                                 : 0ull;
+  if (tid < top) part[tid] = dv;
+  __syncthreads();
+#pragma unroll
+  for (int e = 0; e < SOLVE_PREFETCH; ++e) {
+    const int row = p + P * e;
+    if (active && row < top && row >= k) pv[e] *= part[row];
+  }
+  if (slot) {
+    if (bits == SOLVE_SENT) bits = (unsigned long long)__double_as_longlong(poll_f64(slot, info));
+    tv[tid] = __longlong_as_double((long long)bits);
+    if (tid < top) sent_f64_agent(xhat + T.c0 + tid);  // single consumer: slot ready for the next solve
   }
   // the parent's forward item consumed this front's update vector long ago (it precedes the root's turn) - under a
   // single-product top block its entries for T are read by EVERY item of the block: put back at the end of this item,
@@ -297,10 +312,12 @@ __device__ __forceinline__ void dev_solve_bwd(const SolveItem& T, const double* 
   double acc = 0.0;
 #pragma unroll
   for (int e = 0; e < SOLVE_PREFETCH; ++e)
-    if (e < E) acc = fma(pv[e], tv[min(p + P * e, ro - 1)], acc);  // entries beyond row ro - 1 are stored as zeros
+    if (e < E) acc = fma(pv[e], tv[min(p + P * e, ro - 1)], acc);  // rows beyond ro - 1 count as zeros
+  // (more than SOLVE_PREFETCH entries per thread: Pb = 1024 / w >= 8 then, and these are rows from 32 Pb >= 256 on -
+  // update rows: nothing to divide, nothing to skip)
   for (int e = SOLVE_PREFETCH; e < E; ++e)
-    if (active && !(p + P * e < top && p + P * e < mycol_b)) acc = fma(sp[(long long)e * TS], tv[min(p + P * e, ro - 1)], acc);
-  if (active) part[tid] = acc;
+    if (active) acc = fma(p + P * e < ro ? sp[P * e] : 0.0, tv[min(p + P * e, ro - 1)], acc);
+  if (active) part[p * w + k] = acc;  // (1 / d was last read in front of the barrier above)
   __syncthreads();
   if (tid < w) {
     double s2 = 0.0;
@@ -448,10 +465,10 @@ __device__ __forceinline__ void dev_top_one(const TopBlockIn& B, const TopBlockI
 // scalar kernel over the full square took 620 us per top block in round 4, this one 257 us as one workgroup per tile,
 // 155 + 33 us with the sums cut into segments: k_top_syrk_reduce.)
 // 1 / d_c of the block's pivots, once per top block (the product kernel would fetch each through two dependent loads)
-__global__ __launch_bounds__(FB) void k_top_dinv(int nT, const double* __restrict__ SPb, const long long* __restrict__ dsrc,
+__global__ __launch_bounds__(FB) void k_top_dinv(int nT, const double* __restrict__ SPf, const long long* __restrict__ dsrc,
                                                  double* __restrict__ dinv) {
   const int c = blockIdx.x * FB + threadIdx.x;
-  if (c < nT) dinv[c] = SPb[dsrc[c]];
+  if (c < nT) dinv[c] = SPf[dsrc[c]];
 }
 // The sum over the pivots of a tile is cut into segments of ZS pivots, one workgroup each (the serial loop of the longest
 // tiles - 61 chunks for tile (0, 0) - bounded the unsplit kernel at 257 us): segment s of tile t leaves its 64 x 64
@@ -762,7 +779,7 @@ __device__ __forceinline__ void dev_x_update(const XupdIn& X, int xb, const doub
 // items (items[bwd_off ...]) | the deferred verdict | the x update.  Without a top block: nfwd = nbwd = bwd_off = fronts.
 __global__ __launch_bounds__(ST) void k_solve_tree(const SolveItem* __restrict__ items, int nfwd, int bwd_off, int nbwd,
                                                    TopBlockIn TB,
-                                                   const double* __restrict__ SPf, const double* __restrict__ SPb,
+                                                   const double* __restrict__ SPf,
                                                    const long long* __restrict__ xuoff,
                                                    const int* __restrict__ xinvoff, const int* __restrict__ inv,
                                                    const int* __restrict__ rows, double* __restrict__ y,
@@ -828,9 +845,9 @@ __global__ __launch_bounds__(ST) void k_solve_tree(const SolveItem* __restrict__
     const SolveItem& T = items[bwd_off + (b - nfwd - ntop)];  // second half of the list: the backward order
     // (a child of the top block's fronts, under the single product: its update slots go back to the sentinel late)
     if (TB.ntf > 0 && T.plevel >= TB.ltop)
-      dev_solve_bwd<true>(T, SPb, rows, y, xhat, uvec, ysol2 + (size_t)par * m, spart, lds, info, TB.gathered2 + par, TB.ntf);
+      dev_solve_bwd<true>(T, SPf, rows, y, xhat, uvec, ysol2 + (size_t)par * m, spart, lds, info, TB.gathered2 + par, TB.ntf);
     else
-      dev_solve_bwd<false>(T, SPb, rows, y, xhat, uvec, ysol2 + (size_t)par * m, spart, lds, info);
+      dev_solve_bwd<false>(T, SPf, rows, y, xhat, uvec, ysol2 + (size_t)par * m, spart, lds, info);
   }
   epoch_read_done();
 }

@@ -66,7 +66,7 @@ static int upload(hipfact_handle* h, DevBuf& buf, const std::vector<T, A>& v) {
 // LDS of the solve-panel builder (k_build_solve_panels / role 3 of k_factor_top): X | 1 / d | tiles | offsets
 static size_t solve_panel_lds(int wmax) {
   const size_t wp = (size_t)((wmax + 15) & ~15);
-  return (wp * (wp + 1) + wp + 8 * 16 * 17 + wp + 1024) * sizeof(double);
+  return (wp * (wp + 1) + wp + 8 * 16 * 17) * sizeof(double);  // X | 1 / d | a tile per wave
 }
 
 static int dense_upload(hipfact_handle* h, size_t vec_bytes);
@@ -840,7 +840,7 @@ static int upload_plan(hipfact_handle* h) {
       std::vector<int> fx0(ns, 0), fx1(ns, 0);
       std::vector<long long> fpoff(ns, 0);
       si.reserve(nit);
-      long long spf = 0, spb = 0, spart = 0;
+      long long spf = 0, spart = 0;
       int wmax = 1;
       for (int q = 0; q < nit; ++q) {
         const int s2 = it_front[q], sl = it_sl[q], nsl = it_nsl[q];
@@ -878,15 +878,15 @@ static int upload_plan(hipfact_handle* h) {
         T.poff = fpoff[s2];
         T.a0 = it_a0[q];
         T.a1 = it_a1[q];
-        const int ro = (sl == 0 ? T.w : 0) + (T.a1 - T.a0);  // rows of the item's copies of S
+        const int ro = (sl == 0 ? T.w : 0) + (T.a1 - T.a0);  // rows of the item's panel of S
         T.Qf = std::max(1, std::min(T.w, 1024 / ro));
         T.Ef = (T.w + T.Qf - 1) / T.Qf;
         T.Pb = std::max(1, std::min(ro, 1024 / T.w));
         T.Eb = (ro + T.Pb - 1) / T.Pb;
+        // the panel, column-major ro x (Ef Qf); behind it the w doubles 1 / d_i of slice 0
         T.spf = spf;
-        T.spb = spb;
-        spf += ((long long)T.Ef * ro * T.Qf + 1) & ~1LL;
-        spb += ((long long)T.Eb * T.w * T.Pb + 1) & ~1LL;
+        T.spd = spf + (long long)T.Ef * ro * T.Qf;
+        spf += ((long long)T.Ef * ro * T.Qf + (sl == 0 ? T.w : 0) + 1) & ~1LL;
         wmax = std::max(wmax, T.w);
         si.push_back(T);
       }
@@ -914,10 +914,8 @@ static int upload_plan(hipfact_handle* h) {
         if ((rc = upload(h, h->d_sxinvoff, xinvoff))) return rc;
         cold_tick("  upload_plan: descriptors, items, solve lists");
         HCHECK(h, h->d_SPf.ensure(std::max<size_t>((size_t)spf * sizeof(double), 16)));
-        HCHECK(h, h->d_SPb.ensure(std::max<size_t>((size_t)spb * sizeof(double), 16)));
         HCHECK(h, hipMemsetAsync(h->d_SPf.p, 0, std::max<size_t>((size_t)spf * sizeof(double), 16), h->stream));
-        cold_tick("  upload_plan: solve-panel arenas");
-        HCHECK(h, hipMemsetAsync(h->d_SPb.p, 0, std::max<size_t>((size_t)spb * sizeof(double), 16), h->stream));
+        cold_tick("  upload_plan: solve-panel arena");
         HCHECK(h, h->d_xhat.ensure(std::max<size_t>((size_t)P.m * sizeof(double), 16)));
         HCHECK(h, hipMemsetAsync(h->d_xhat.p, 0xFF, std::max<size_t>((size_t)P.m * sizeof(double), 16), h->stream));
         // partial sums of the backward items of sliced fronts: polled, sentinel between solves
@@ -928,7 +926,7 @@ static int upload_plan(hipfact_handle* h) {
         h->fused_solve = true;
         h->n_sitems = nit;
         for (int q = 0; q < nit; ++q) h->n_sliced += it_sl[q] == 0 && it_nsl[q] > 1;
-        h->sp_bytes = (double)(spf + spb) * sizeof(double);
+        h->sp_bytes = (double)spf * sizeof(double);
         // ---- top block: the last levels (few fronts each: pure hop latency in the solves) as two dense products
         h->tb_nT = h->tb_ntf = h->tb_nfb = h->tb_levels = h->tb_nchunks = 0;
         h->tb_valid = false;
@@ -1017,13 +1015,11 @@ static int upload_plan(hipfact_handle* h) {
                 const int w = si[(size_t)tfronts[(size_t)f2].item].w;
                 for (int j0 = 0; j0 < w; j0 += TOP_CB) chunks.push_back(TopChunk{f2, j0});
               }
-              // where 1 / d of a T-local column sits in the backward solve panel of its front
+              // where 1 / d of a T-local column sits: the tail of its front's solve panel
               std::vector<long long> dsrc((size_t)nT);
               for (const TopFront& F : tfronts) {
                 const SolveItem& T = si[(size_t)F.item];
-                const long long TSb = (long long)T.w * T.Pb;
-                for (int i = 0; i < T.w; ++i)
-                  dsrc[(size_t)(F.tl0 + i)] = T.spb + (long long)(i / T.Pb) * TSb + (long long)(i % T.Pb) * T.w + i;
+                for (int i = 0; i < T.w; ++i) dsrc[(size_t)(F.tl0 + i)] = T.spd + i;
               }
               if ((rc = upload(h, h->d_tb_items, titems))) return rc;
               if ((rc = upload(h, h->d_tb_tpos, tpos))) return rc;

@@ -217,7 +217,7 @@ static int factor_enqueue(hipfact_handle* h) {
       LAUNCH(PC_FACTOR_B, k_factor_top, dim3(li.mini_cnt), dim3(512), li.mini_lds,
              h->d_tfitems.as<TopFItem>() + li.mini_off, h->d_L.as<double>(), h->d_U.as<double>(), h->d_info.as<int>(),
              h->d_inv.as<int>(), h->d_rel.as<int>(), flm, flm + P.nsuper, flm + 2 * P.nsuper, h->d_xarena.as<double>(),
-             nullptr, nullptr, nullptr);
+             nullptr, nullptr);
       launch_schur<false>(h, li, pull);
     } else if (li.split && h->debug_phases == 15) {
       const FrontItem* fit = h->d_fitems.as<FrontItem>();
@@ -247,12 +247,11 @@ static int factor_enqueue(hipfact_handle* h) {
     LAUNCH(PC_FACTOR_T, k_factor_top, dim3(h->ftop_count), dim3(512), h->ftop_lds, h->d_tfitems.as<TopFItem>(),
            h->d_L.as<double>(), h->d_U.as<double>(), h->d_info.as<int>(), h->d_inv.as<int>(), h->d_rel.as<int>(), fl,
            fl + P.nsuper, fl + 2 * P.nsuper, h->d_xarena.as<double>(),
-           h->sp_folded ? h->d_sitems.as<SolveItem>() : nullptr, h->sp_folded ? h->d_SPf.as<double>() : nullptr,
-           h->sp_folded ? h->d_SPb.as<double>() : nullptr);
+           h->sp_folded ? h->d_sitems.as<SolveItem>() : nullptr, h->sp_folded ? h->d_SPf.as<double>() : nullptr);
   }
   if (tree_solve(h) && !(h->sp_folded && lsplit < P.nlevels) && h->n_sitems > 0)
     LAUNCH(PC_SPANEL, k_build_solve_panels, dim3(h->n_sitems), dim3(SPB), h->sp_lds, h->d_sitems.as<SolveItem>(),
-           h->d_L.as<double>(), h->d_SPf.as<double>(), h->d_SPb.as<double>());
+           h->d_L.as<double>(), h->d_SPf.as<double>());
   HCHECK(h, hipGetLastError());
   return dense_setup_async(h);
 }
@@ -535,8 +534,7 @@ static void solve_m_async(hipfact_handle* h, const int* skip, const RhsIn* rhs =
     const size_t tree_lds = (size_t)(TB.ntf > 0 ? TOP_LDS : TREE_LDS) * sizeof(double);
     LAUNCH(PC_TREE, k_solve_tree, dim3(TB.ntr + nfwd + TB.ntf + nbwd + 1 + X.nblocks), dim3(ST), tree_lds, h->d_sitems.as<SolveItem>(),
            nfwd, bwd_off, nbwd, TB,
-           h->d_SPf.as<double>(),
-           h->d_SPb.as<double>(), h->d_sxuoff.as<long long>(), h->d_sxinvoff.as<int>(),
+           h->d_SPf.as<double>(), h->d_sxuoff.as<long long>(), h->d_sxinvoff.as<int>(),
            h->d_inv.as<int>(), h->d_rows.as<int>(), h->d_y.as<double>(),
            h->d_xhat.as<double>(), h->d_uvec.as<double>(), h->d_ysol.as<double>(), P.m, h->d_epoch.as<int>(),
            h->d_info.as<int>(), skip, rhs ? *rhs : RhsIn{},
@@ -840,7 +838,7 @@ static int top_block_build(hipfact_handle* h) {
     HCHECK(h, h->d_tb_zd.ensure((size_t)nT * nT * sizeof(double)));
     const int nt = (nT + ZT - 1) / ZT;
     HCHECK(h, h->d_tb_dinv.ensure((size_t)nT * sizeof(double)));
-    hipLaunchKernelGGL(k_top_dinv, dim3((nT + FB - 1) / FB), dim3(FB), 0, st, nT, h->d_SPb.as<double>(), h->d_tb_dsrc.as<long long>(),
+    hipLaunchKernelGGL(k_top_dinv, dim3((nT + FB - 1) / FB), dim3(FB), 0, st, nT, h->d_SPf.as<double>(), h->d_tb_dsrc.as<long long>(),
                        h->d_tb_dinv.as<double>());
     // (the long sums cut into segments of ZS pivots: partial tiles, then one pass that adds them in order)
     const int ntl = nt * (nt + 1) / 2;

@@ -225,7 +225,7 @@ struct PlanState : FactorMemo {
   bool fused_solve = false;
   size_t sp_lds = 0;
   double sp_bytes = 0;
-  DevBuf d_SPf, d_SPb, d_sitems, d_xhat, d_sxuoff, d_sxinvoff, d_epoch, d_spart;
+  DevBuf d_SPf, d_sitems, d_xhat, d_sxuoff, d_sxinvoff, d_epoch, d_spart;
   int n_sitems = 0;  // items of the fused solve launch: one per front, row slices for fronts of more than 1024 rows
   int n_sliced = 0;  // fronts of the fused solve launch that are cut into row slices (info key solve_sliced_fronts)
   int n_resorted = 0;  // levels whose solve items are not in plan order (solve_sorted; info key solve_resorted_levels)
