@@ -619,6 +619,34 @@ int hipfact_debug_multi_slices(int u, int slice_rows, int* tile_bounds /* cap + 
  * hipfact_extra_info.  Every output pointer may be NULL. */
 int hipfact_debug_extra_rule(int nblocks, int npasses, const double* dn, const double* zn, int pass_cap, int* applied,
                              int* status, double* ferr, double* rho);
+/* The refinement cadence of the single solve as a pure host function (no GPU needed; used by the tests): how many
+ * correction passes the solve graphs carry, which solves take a residual, and which leave their verdict to the next tree
+ * launch.  A script of events runs through the transitions the runtime calls, on one plan of one fresh handle.
+ * knobs: refine_steps, refine_adaptive, refine_check_every, refine_check_backoff, refine_check_max, decide_lazy,
+ * factor_hint_peek.  Event e is events[8 e ..]: kind, flag, then what the host sees of the control block at that moment
+ * (seq, done, status, iters, omega, tol; seq -1: nothing new).  flag: FACTOR 1 = the captured sequence; SOLVE bit 0 =
+ * the tree launch delivers verdicts, bit 1 = every solve of the call is checked; VERDICT the rounds of passes the host
+ * continued (the block is the final one); JUDGE well / not; SET_* the value.  Row e is rows[20 e ..], the state behind
+ * the event: defer, unchecked, key (without the top-block term), flush_first (SOLVE, else 0); refine_inline, inline_probe,
+ * wc_hint; the check interval, solves_since_check, num_checked; solve_seq, ctl_pending, decide_deferred; num_refined,
+ * num_passes; seq_at_factor, hint_seq_seen, first_factor_seq; last_solve_checked; unchecked_solves_ok.
+ * HIPFACT_EINVAL for values out of range, an unknown kind, a RESTORE without a SAVE. */
+enum {
+  HIPFACT_CADENCE_FACTOR = 0,
+  HIPFACT_CADENCE_SOLVE = 1,
+  HIPFACT_CADENCE_VERDICT = 2,
+  HIPFACT_CADENCE_JUDGE = 3,
+  HIPFACT_CADENCE_RESET = 4,
+  HIPFACT_CADENCE_SET_STEPS = 5,
+  HIPFACT_CADENCE_SET_CHECK_EVERY = 6,
+  HIPFACT_CADENCE_SET_CHECK_BACKOFF = 7,
+  HIPFACT_CADENCE_SAVE = 8,
+  HIPFACT_CADENCE_RESTORE = 9,
+  HIPFACT_CADENCE_DEVICE_RESIDUAL = 10,
+  HIPFACT_CADENCE_EVENT_WIDTH = 8,
+  HIPFACT_CADENCE_ROW_WIDTH = 20
+};
+int hipfact_debug_refine_cadence(const int* knobs /* 7 */, int nevents, const double* events, long long* rows);
 /* The double-double accumulate of the residual kernels on the host (the same header, no GPU needed; used by the
  * tests): round(b - sum k[i] z[i]), term i accumulated in pair i % lanes, the pairs added through the kernels' fixed
  * tree (lanes a power of two in [1, 256]: 8 / 16 are the lane groups of a column / a row, 256 a long row's workgroup

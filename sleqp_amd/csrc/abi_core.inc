@@ -256,7 +256,7 @@ static int boundary_download(hipfact_handle* h) {
     HCHECK(h, hipHostGetDevicePointer(&h->h_sol_dev, h->h_sol_pin.p, 0));
   }
   HCHECK(h, h->h_info_pre.ensure(INFO_WORDS * sizeof(int)));
-  if (h->ctl_pending) flush_decide(h);
+  if (cadence(h).verdict_unread()) flush_decide(h);
   if (h->bd_profile) HCHECK(h, hipEventRecord(h->bd_ev[2], h->stream));
   // The x part first, with an event of its own: the AugJac solves ask for solution(0, n) (min-norm, projection:
   // standard_aug_jac.c:337-338, 422-427) or solution(n, N) (LSQ, :382-386) - the former need not wait for the rest.

@@ -568,7 +568,7 @@ static int gltr_impl(hipfact_handle* h, const HessOp& op, const double* gradient
       double* hd = h->h_cg_dots.as<double>() + 2 * 3 * DOT_BLOCKS;
       HCHECK(h, hipMemcpyAsync(hd, delta_dev, (size_t)(8 + xb) * sizeof(double), hipMemcpyDeviceToHost, st));
       HCHECK(h, hipStreamSynchronize(st));
-      const bool checked = h->last_solve_checked;
+      const bool checked = cadence(h).last_checked();
       if ((rc = finish_solve(h, &cont))) return rc;
       if (!cont && !(checked && h->last_ctl.iters > 0)) {
         dots[0] = 0.0;

@@ -36,7 +36,7 @@ static const OptionRow kOptions[] = {
     {"refine_steps", "HIPFACT_REFINE", FX_GRAPHS,
      [](hipfact_handle* h, double v) -> int {
        h->refine_steps = std::max(0, (int)v);
-       h->refine_inline = h->refine_steps;
+       cadence(h).steps_set(cadence_knobs(h));
        return 1;
      },
      "correction passes carried by every solve graph (default 1; 0: plain solve, no residual); they return at once when the device-side control block reports convergence"},
@@ -97,14 +97,14 @@ static const OptionRow kOptions[] = {
     {"refine_check_backoff", nullptr, FX_NONE,
      [](hipfact_handle* h, double v) -> int {
        h->refine_check_backoff = std::max(1, (int)v);
-       h->check_interval_now = 0;
+       cadence(h).check_interval_set();
        return 1;
      },
      "the interval between residual checks is multiplied by this after every check that passes (default 2; 1: fixed interval), up to 64 solves"},
     {"refine_check_every", nullptr, FX_NONE,
      [](hipfact_handle* h, double v) -> int {
        h->refine_check_every = std::max(1, (int)v);
-       h->check_interval_now = 0;
+       cadence(h).check_interval_set();
        return 1;
      },
      "residual check on every k-th solve of a well-conditioned factorisation"},
@@ -316,6 +316,82 @@ int hipfact_debug_multi_slices(int u, int slice_rows, int* tile_bounds, int cap)
   return ns;
 }
 
+// the refinement cadence of the single solve (refine_cadence.h) as a pure host function: a script of events through
+// the transitions the runtime calls, on one plan of one handle
+int hipfact_debug_refine_cadence(const int* knobs, int nevents, const double* events, long long* rows) {
+  using namespace hipfact;
+  if (!knobs || nevents < 0 || (nevents > 0 && (!events || !rows))) return HIPFACT_EINVAL;
+  for (int q = 0; q < 7; ++q)
+    if (knobs[q] < 0 || ((q == 1 || q >= 5) && knobs[q] > 1) || (q >= 2 && q <= 4 && knobs[q] < 1)) return HIPFACT_EINVAL;
+  CadenceKnobs k{knobs[0], knobs[1] != 0, knobs[2], knobs[3], knobs[4], knobs[5] != 0, knobs[6] != 0};
+  FactorCadence f;
+  PlanCadence p;
+  SolveCadence s;
+  LiveCadence l;
+  Cadence cad{f, p, s, l};
+  SavedCadence saved{};
+  bool have_saved = false;
+  for (int e = 0; e < nevents; ++e) {
+    const double* ev = events + (size_t)e * HIPFACT_CADENCE_EVENT_WIDTH;
+    for (int q = 0; q < 6; ++q)
+      if (!(std::fabs(ev[q]) < (double)(1 << 30)) || ev[q] != std::floor(ev[q])) return HIPFACT_EINVAL;
+    const int kind = (int)ev[0], flag = (int)ev[1];
+    const CtlPeek c{(int)ev[2], (int)ev[3], (int)ev[4], (int)ev[5], ev[6], ev[7]};
+    const bool yes_no = flag == 0 || flag == 1;
+    SolveDecision d{false, false, false, 0, 0};
+    switch (kind) {
+      case HIPFACT_CADENCE_FACTOR:
+        if (!yes_no) return HIPFACT_EINVAL;
+        cad.factor_queued(k, flag != 0, c);
+        break;
+      case HIPFACT_CADENCE_SOLVE:
+        if (flag < 0 || flag > 3) return HIPFACT_EINVAL;
+        d = cad.solve_decision(k, (flag & 1) != 0, cad.wants_peek(k) ? c : CtlPeek{-1, 0, 0, 0, 0.0, 0.0}, (flag & 2) != 0);
+        if (d.flush_first) cad.verdict_flushed();
+        cad.solve_queued(k, d);
+        break;
+      case HIPFACT_CADENCE_VERDICT:
+        if (flag < 0) return HIPFACT_EINVAL;
+        cad.verdict_read(k, c);
+        cad.verdict_counted(c, flag);
+        break;
+      case HIPFACT_CADENCE_JUDGE:
+        if (!yes_no) return HIPFACT_EINVAL;
+        cad.judge(k, flag != 0);
+        break;
+      case HIPFACT_CADENCE_RESET: cad.slots_reset(); break;
+      case HIPFACT_CADENCE_SET_STEPS:  // (the clamps of the option rows)
+        k.refine_steps = std::max(0, flag);
+        cad.steps_set(k);
+        break;
+      case HIPFACT_CADENCE_SET_CHECK_EVERY:
+        k.check_every = std::max(1, flag);
+        cad.check_interval_set();
+        break;
+      case HIPFACT_CADENCE_SET_CHECK_BACKOFF:
+        k.check_backoff = std::max(1, flag);
+        cad.check_interval_set();
+        break;
+      case HIPFACT_CADENCE_SAVE:
+        saved = cad.save();
+        have_saved = true;
+        break;
+      case HIPFACT_CADENCE_RESTORE:
+        if (!have_saved) return HIPFACT_EINVAL;
+        cad.put_back(saved);
+        break;
+      case HIPFACT_CADENCE_DEVICE_RESIDUAL: cad.counted_device_residual(); break;
+      default: return HIPFACT_EINVAL;
+    }
+    const long long row[HIPFACT_CADENCE_ROW_WIDTH] = {
+        d.defer, d.unchecked, d.key, d.flush_first, f.refine_inline, f.inline_probe, f.wc_hint, s.check_interval_now,
+        s.solves_since_check, s.num_checked, l.solve_seq, l.ctl_pending, l.decide_deferred, s.num_refined, s.num_passes,
+        p.seq_at_factor, p.hint_seq_seen, p.first_factor_seq, s.last_solve_checked, cad.unchecked_solves_ok(k)};
+    memcpy(rows + (size_t)e * HIPFACT_CADENCE_ROW_WIDTH, row, sizeof row);
+  }
+  return HIPFACT_OK;
+}
+
 int hipfact_get_info(const hipfact_handle* h, const char* name, double* value) {
   if (!h || !name || !value) return HIPFACT_EINVAL;
   const Plan& P = h->plan;
@@ -398,10 +474,10 @@ int hipfact_get_info(const hipfact_handle* h, const char* name, double* value) {
   INFO("multi_passes", h->multi_passes) INFO("multi_single_cols", h->multi_single_cols) INFO("multi_failed_col", h->multi_failed_col)
   INFO("multi_sliced_fronts", h->mitems_for < 0 ? 0 : h->n_mcut) INFO("multi_slice_items", h->mitems_for < 0 ? 0 : h->n_mslices) INFO("multi_slice_rows", h->multi_slice_rows)
   INFO("extra_solves", h->extra_solves) INFO("extra_passes", h->extra_passes) INFO("extra_last_status", h->extra_last_status)
-  INFO("num_solve", h->num_solve) INFO("num_refined", h->num_refined) INFO("refine_adaptive", h->refine_adaptive)
-  INFO("num_passes", h->num_passes) INFO("last_omega", h->last_ctl.omega) INFO("last_iters", h->last_ctl.iters)
+  INFO("num_solve", h->num_solve) INFO("num_refined", h->solve_cad.num_refined) INFO("refine_adaptive", h->refine_adaptive)
+  INFO("num_passes", h->solve_cad.num_passes) INFO("last_omega", h->last_ctl.omega) INFO("last_iters", h->last_ctl.iters)
   INFO("last_status", h->last_ctl.status) INFO("last_tol", h->last_ctl.tol) INFO("kappa_est", h->last_ctl.kappa)
-  INFO("refine_inline", h->refine_inline) INFO("refine_tol", h->refine_tol) INFO("equilibrate", h->equilibrate)
+  INFO("refine_inline", h->factor_cad.refine_inline) INFO("refine_tol", h->refine_tol) INFO("equilibrate", h->equilibrate)
   INFO("factor_top_level", h->ftop_level) INFO("factor_top_count", h->ftop_count) INFO("solve_timeouts", h->h_info.p ? h->h_info.as<int>()[INFO_TIMEOUT] : 0)
   INFO("top_level", 1 << 30)  // the retired two-launch solve route, reported as "off": the benchmark still asks
   INFO("use_graph", h->use_graph) INFO("num_graphs", h->graphs.size()) INFO("max_r", P.max_r) INFO("max_w", P.max_w) INFO("refine_steps", h->refine_steps)
@@ -412,7 +488,7 @@ int hipfact_get_info(const hipfact_handle* h, const char* name, double* value) {
   // plan did with the solve items - the fronts cut into row slices, the levels whose items are not in plan order
   INFO("rhs_in_tree", h->last_rhs_in_tree) INFO("xupd_in_tree", h->last_xupd_in_tree) INFO("xupd_blocks_launched", h->last_xupd_blocks)
   INFO("solve_sliced_fronts", h->n_sliced) INFO("solve_resorted_levels", h->n_resorted) INFO("tree_solve", tree_solve(h))
-  INFO("refine_check_every", h->refine_check_every) INFO("refine_check_interval", h->check_interval_now) INFO("num_checked", h->num_checked)
+  INFO("refine_check_every", h->refine_check_every) INFO("refine_check_interval", h->solve_cad.check_interval_now) INFO("num_checked", h->solve_cad.num_checked)
   INFO("device", h->device) INFO("nnzM", P.Mi.size()) INFO("nnzA", P.Ar_src.size())
   INFO("rows_total", P.sn_rows.size()) INFO("ent_fused", h->ent_fused) INFO("ent_split", h->ent_split)
   INFO("rows_fused", h->rows_fused) INFO("rows_split", h->rows_split)

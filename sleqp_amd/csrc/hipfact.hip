@@ -14,6 +14,8 @@
 //   dense_cols.inc      dense Jacobian columns                   krylov_device.inc    device-controlled CG
 //   runtime_multi.inc   blocked solve, 16 right-hand sides       abi_multi.inc        hipfact_solve[_device]_multi
 //   runtime_extra.inc   extra-precise solve (dd_arith.h)         abi_extra.inc        hipfact_solve[_device]_extra, _residual_device
+//   refine_cadence.h    refinement cadence of the single solve: passes in the graph, residual checks, deferred verdicts
+//                       (pure host rules, like xcd_place.h and multi_slices.h)
 #include <hip/hip_runtime.h>
 
 #include <dlfcn.h>
@@ -45,6 +47,7 @@
 #include "kernels_decl.h"
 #include "xcd_place.h"
 #include "multi_slices.h"
+#include "refine_cadence.h"
 #include "dd_arith.h"
 
 #include "runtime_types.inc"

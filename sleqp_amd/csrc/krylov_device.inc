@@ -391,9 +391,7 @@ static int launch_lz_spmv(hipStream_t st, int L, int n, const LzCtl* c, hipfact_
 
 // The device loops run their projections without a residual check (no host in between to continue a refinement):
 // only on a factorisation that has been judged - no correction pass in its solves
-static bool unchecked_solves_ok(const hipfact_handle* h) {
-  return h->refine_steps == 0 || (h->refine_adaptive && h->refine_inline == 0 && !h->inline_probe);
-}
+static bool unchecked_solves_ok(hipfact_handle* h) { return cadence(h).unchecked_solves_ok(cadence_knobs(h)); }
 
 // ... and the last of those projections (right-hand side b, result in d_cg_z, both untouched since) is verified when
 // the loop has ended, like every k-th solve.  *ok = false: the first pass alone does not meet the tolerance on this
@@ -406,9 +404,9 @@ static int last_unchecked_solve_ok(hipfact_handle* h, const double* b, bool* ok)
   HCHECK(h, hipStreamSynchronize(h->stream));
   RefineCtl rcx;
   memcpy(&rcx, h->h_ctl.p, sizeof(rcx));
-  h->solve_seq++;  // (the device counted a first residual)
+  cadence(h).counted_device_residual();
   *ok = rcx.done && rcx.status == 0;
-  if (!*ok) judge_conditioning(h, false);
+  if (!*ok) cadence(h).judge(cadence_knobs(h), false);
   return HIPFACT_OK;
 }
 

@@ -11,7 +11,7 @@
 // solution differ in scale, and a projection is read from one of them.
 // Every K^-1 is ONE PLAIN single solve (solve_async + finish_solve with refine_steps forced to 0 for the call): graphs,
 // top block, dense-column correction and routes are the single path's.  What that path remembers between solves goes
-// back afterwards as in multi_single_cols (SingleSolveMemo, FactorMemo): the call is not "the last solve".
+// back afterwards as in multi_single_cols (KeptSolveMemo): the call is not "the last solve".
 // The host looks at four norms once per pass - the one synchronisation of a pass, in check_info, which also reads the
 // info words: a dataflow launch whose waits ran out moves the handle to the per-level launches there, and the call
 // starts over on them, once.
@@ -169,8 +169,7 @@ static int solve_extra_device(hipfact_handle* h, const double* d_rhs, double* d_
   const size_t N = (size_t)h->N_ext;
   int rc = extra_workspace(h);
   if (rc) return rc;
-  const SingleSolveMemo keep = *h;
-  const FactorMemo keep_factor = *h;
+  const KeptSolveMemo keep(h);
   const int keep_steps = h->refine_steps;
   h->refine_steps = 0;  // every K^-1 of the loop is one plain solve (its graphs are keyed as such: nothing is dropped)
   hipfact_extra_info out = {0, HIPFACT_EXTRA_PASS_LIMIT, INFINITY, INFINITY, 0.0, NAN};
@@ -182,7 +181,7 @@ static int solve_extra_device(hipfact_handle* h, const double* d_rhs, double* d_
              ? HIPFACT_OK
              : HIPFACT_EDEVICE;
     if (rc == HIPFACT_OK) rc = hipMemsetAsync(h->d_xctl.p, 0, sizeof(RefineCtl), h->stream) == hipSuccess ? HIPFACT_OK : HIPFACT_EDEVICE;
-    if (rc == HIPFACT_OK) rc = extra_loop(h, keep_factor.solves_this_factor, out, c, switched);
+    if (rc == HIPFACT_OK) rc = extra_loop(h, keep.factor.solves_this_factor, out, c, switched);
     if (!(rc == HIPFACT_EINTERNAL && switched && attempt == 0)) break;
     h->error.clear();  // (the per-level launches from here on: the same call once more)
   }
@@ -191,8 +190,7 @@ static int solve_extra_device(hipfact_handle* h, const double* d_rhs, double* d_
     rc = HIPFACT_EDEVICE;
   if (rc == HIPFACT_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = HIPFACT_EDEVICE;
   h->refine_steps = keep_steps;
-  static_cast<SingleSolveMemo&>(*h) = keep;
-  static_cast<FactorMemo&>(*h) = keep_factor.put_back_over(*h);
+  keep.put_back(h);
   if (rc == HIPFACT_EDEVICE && h->error.empty()) h->error = "hipfact_solve_device_extra: device error";
   if (rc) return rc;
   h->extra_solves++;

@@ -241,18 +241,14 @@ static int multi_block(hipfact_handle* h, int nb, int first, const double* d_rhs
 }
 
 // columns of a plan state with the low-rank dense-column correction (dense_mode 2): one by one through the single
-// solve.  Every column is a CHECKED solve (residual, verdict, correction passes: the refine_check_every cadence of the
-// single path is switched off for the call), and what the single path remembers between solves is put back afterwards:
-// SingleSolveMemo and FactorMemo (runtime_types.inc), each as a whole - but for the judgement of a factorisation these
-// columns were the first to judge (FactorMemo::put_back_over).  The columns do use d_y, the epoch and the
-// exchange slots, as every single solve does after another.
+// solve.  Every column is a CHECKED solve (residual, verdict, correction passes: solve_async's all_checked), and what
+// the single path remembers between solves is put back afterwards (KeptSolveMemo, runtime_types.inc) - but for the
+// judgement of a factorisation these columns were the first to judge (Cadence::put_back).  The columns do use d_y, the
+// epoch and the exchange slots, as every single solve does after another.
 static int multi_single_cols(hipfact_handle* h, int nrhs, const double* d_rhs, long long ld_rhs, double* d_sol,
                              long long ld_sol, bool in_place, double* omega) {
   const size_t N = (size_t)h->N_ext;
-  const SingleSolveMemo keep = *h;
-  const FactorMemo keep_factor = *h;
-  h->refine_check_every = 1;
-  h->check_interval_now = 1;
+  const KeptSolveMemo keep(h);
   int rc = HIPFACT_OK;
   for (int j = 0; j < nrhs && rc == HIPFACT_OK; ++j) {
     const double* bj = d_rhs + (size_t)j * ld_rhs;
@@ -260,16 +256,15 @@ static int multi_single_cols(hipfact_handle* h, int nrhs, const double* d_rhs, l
       if (hipMemcpyAsync(h->d_mB.p, bj, N * sizeof(double), hipMemcpyDeviceToDevice, h->stream) != hipSuccess) rc = HIPFACT_EDEVICE;
       bj = h->d_mB.as<double>();
     }
-    h->solves_this_factor = keep_factor.solves_this_factor - 1;  // (solve_async counts it back up: the top block is not formed earlier than without this call)
-    if (rc == HIPFACT_OK) rc = solve_async(h, bj, d_sol + (size_t)j * ld_sol);
+    h->solves_this_factor = keep.factor.solves_this_factor - 1;  // (solve_async counts it back up: the top block is not formed earlier than without this call)
+    if (rc == HIPFACT_OK) rc = solve_async(h, bj, d_sol + (size_t)j * ld_sol, true);
     if (rc == HIPFACT_OK) rc = finish_solve(h);
     if (rc == HIPFACT_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = HIPFACT_EDEVICE;
     if (omega) omega[j] = h->refine_steps > 0 ? h->last_ctl.omega : NAN;
     if (rc == HIPFACT_ESINGULAR) h->multi_failed_col = j;
     h->multi_single_cols++;
   }
-  static_cast<SingleSolveMemo&>(*h) = keep;
-  static_cast<FactorMemo&>(*h) = keep_factor.put_back_over(*h);
+  keep.put_back(h);
   return rc;
 }
 

@@ -263,13 +263,6 @@ static void flush_decide(hipfact_handle* h);
 static void drop_graphs(hipfact_handle* h);
 static int reset_dataflow_state(hipfact_handle* h);
 
-// The judgement "well conditioned": the first pass alone met a quarter of the tolerance.  What follows from it: no
-// correction pass in the solve graphs of this factorisation - or (well = false: the judgement withdrawn) a pass again.
-static inline bool first_pass_sufficed(const RefineCtl& c) { return c.done && c.status == 0 && c.iters == 0 && c.omega <= 0.25 * c.tol; }
-static inline void judge_conditioning(hipfact_handle* h, bool well) {
-  h->wc_hint = well;
-  h->refine_inline = well ? 0 : std::max(h->refine_inline, std::min(h->refine_steps, 1));
-}
 // src: the caller's values on the device (hipfact_refactor_device), copied into d_Kval in front of the factorisation
 static int factor_async(hipfact_handle* h, const double* src = nullptr) {
   const Plan& P = h->plan;
@@ -277,8 +270,8 @@ static int factor_async(hipfact_handle* h, const double* src = nullptr) {
   // of this one.  With the captured sequence both that launch (a no-op on the device when nothing is pending) and the
   // copy of the caller's values are nodes of the graph, keyed by the source pointer - as launches of their own between
   // two graph launches each of them left the chip idle for ~8 us.
-  if (h->no_dataflow && h->df_retry_at >= 0 && h->num_factor >= h->df_retry_at && !h->ctl_pending && !h->decide_deferred &&
-      !h->reg_retry) {
+  if (h->no_dataflow && h->df_retry_at >= 0 && h->num_factor >= h->df_retry_at && !cadence(h).verdict_unread() &&
+      !cadence(h).verdict_outstanding() && !h->reg_retry) {
     // another try with the single-launch kernels (runtime_types.inc: df_retry_every).  The per-level solves have used
     // the update vectors as plain memory: the exchange slots of this plan go back to their sentinels, the graphs of
     // the per-level sequences and the inactive plans (whose slots may have been used the same way) are dropped.
@@ -302,7 +295,7 @@ static int factor_async(hipfact_handle* h, const double* src = nullptr) {
     flush_decide(h);
     if (copy_first) HCHECK(h, hipMemcpyAsync(h->d_Kval.p, src, src_bytes, hipMemcpyDeviceToDevice, h->stream));
   }
-  const bool with_decide = graphed && h->decide_deferred;  // (two variants of the graph: + 4 in its key)
+  const bool with_decide = graphed && cadence(h).verdict_outstanding();  // (two variants of the graph: + 4 in its key)
   const bool with_inactive = diag_inactive_needed(h);      // (k_diag_inactive comes and goes with the working set: + 16)
   auto enqueue_all = [&]() -> int {
     if (graphed) {
@@ -327,7 +320,6 @@ static int factor_async(hipfact_handle* h, const double* src = nullptr) {
   const int variant = (with_decide ? 4 : 0) + (h->reg_delta > 0.0 ? 8 : 0) + (with_inactive ? 16 : 0);
   h->note('F', variant + (graphed ? 0 : 32));
   const int rc = run_cached(h, 0, graphed ? src : nullptr, nullptr, enqueue_all, variant);
-  if (graphed && rc == HIPFACT_OK) h->decide_deferred = false;
   if (rc) return rc;
   h->num_factor++;
   h->sol_prefetched = false;
@@ -336,26 +328,7 @@ static int factor_async(hipfact_handle* h, const double* src = nullptr) {
   h->factored = true;
   h->factor_checked = false;
   h->solved = false;
-  h->ctl_pending = false;
-  // a plan whose previous factorisation needed no correction pass starts without one in its solve graphs (an SQP run
-  // refactors the same pattern with slowly changing values); the first solve is checked as always, and a solve that
-  // does need a pass is continued at the next synchronising entry point, which also puts the pass back
-  // (a caller that solves ONCE per factorisation and never synchronises - a device-resident loop - never reaches the
-  // peek of the second solve: the last verdict that has come back for a factorisation of this plan stands in for it)
-  if (h->first_factor_seq < 0) h->first_factor_seq = h->solve_seq;
-  if (h->factor_hint_peek && h->refine_adaptive && h->refine_steps > 0) {
-    const RefineCtl* hc = h->h_ctl.as<RefineCtl>();
-    const int seq = __atomic_load_n(&hc->seq, __ATOMIC_ACQUIRE);
-    if (seq > h->first_factor_seq && seq > h->hint_seq_seen) {  // (a verdict nobody has looked at yet)
-      h->hint_seq_seen = seq;
-      h->wc_hint = first_pass_sufficed(*hc);
-    }
-  }
-  h->refine_inline = (h->wc_hint && h->refine_adaptive) ? 0 : h->refine_steps;
-  h->inline_probe = true;
-  h->seq_at_factor = h->solve_seq;
-  h->solves_since_check = 0;
-  h->check_interval_now = h->refine_check_every;
+  cadence(h).factor_queued(cadence_knobs(h), graphed, ctl_peek_pinned(h));
   return HIPFACT_OK;
 }
 
@@ -376,8 +349,7 @@ static int reset_dataflow_state(hipfact_handle* h) {
   HCHECK(h, hipMemsetAsync(h->d_ctl.p, 0, sizeof(RefineCtl), st));
   HCHECK(h, hipStreamSynchronize(st));
   memset(h->h_ctl.p, 0, sizeof(RefineCtl));
-  h->solve_seq = h->seq_at_factor = 0;
-  h->ctl_pending = false;
+  cadence(h).slots_reset();
   return HIPFACT_OK;
 }
 
@@ -402,7 +374,7 @@ static void trace_timeout(hipfact_handle* h, const char* msg) {
               P.level_ptr[l + 1] - P.level_ptr[l], open, nb, nc, nd);
     }
   fprintf(stderr, "[hipfact %p] %s; factorisation %ld, solve %ld, turn waits %lld, handles on the device %d\n", (void*)h, msg,
-          (long)h->num_factor, (long)h->solve_seq, h->turn_waits, g_turn[h->device & 15].live.load());
+          (long)h->num_factor, (long)h->live_cad.solve_seq, h->turn_waits, g_turn[h->device & 15].live.load());
   fprintf(stderr, "   first solve workgroup that timed out: %d (items %d, top block %d: %d below)\n",
           h->info_host[INFO_TIMEOUT_WG] ? (1 << 30) - h->info_host[INFO_TIMEOUT_WG] : -1, h->n_sitems, (int)h->tb_valid, h->tb_nfb);
   for (hipfact_handle* o : g_trace_handles)
@@ -693,9 +665,9 @@ static void residual_async(hipfact_handle* h, const double* b, const double* z, 
 // (a synchronising entry point, a refactorisation - the pivot range it is judged against changes -, a solve
 // that does not go through the tree launch); a no-op on the device if it has been delivered already
 static void flush_decide(hipfact_handle* h) {
-  if (!h->decide_deferred) return;
+  if (!cadence(h).verdict_outstanding()) return;
   hipLaunchKernelGGL(k_refine_decide, dim3(1), dim3(FB), 0, h->stream, decide_in(h), 1, 1);
-  h->decide_deferred = false;
+  cadence(h).verdict_flushed();
 }
 
 // (the parked states too: their graphs captured option values - refine_tol, equilibrate, launch variants - by value)
@@ -784,30 +756,23 @@ static int correct_enqueue(hipfact_handle* h, const double* bb, double* z, int p
   return HIPFACT_OK;
 }
 
-// A solve without correction passes in its graph leaves its verdict to the tree launch of the NEXT solve (a
-// workgroup of that launch instead of a one-block launch and its kernel boundary behind every solve).
-static bool defers_decide(const hipfact_handle* h) {
-  return h->decide_lazy && h->refine_steps > 0 && h->refine_adaptive && h->refine_inline == 0 && tree_delivers_verdict(h);
-}
-
-// Keys of the captured solve sequences (run_cached's `passes`, the launch notes): the correction passes in the graph (a
-// solve: -2 with the verdict left to the next tree launch, -1 without a residual), top_block_key added with the top block
+// Keys of the captured solve sequences (run_cached's `passes`, the launch notes): SolveDecision::key (the correction
+// passes in the graph; -2 with the verdict left to the next tree launch - a workgroup of that launch instead of a
+// one-block launch and its kernel boundary behind every solve -, -1 without a residual), top_block_key added with the
+// top block
 static inline int top_block_key(const hipfact_handle* h) { return h->tb_valid ? 1000 : 0; }
-static inline int solve_graph_key(const hipfact_handle* h, bool defer) {
-  return (h->refine_steps > 0 ? (defer ? -2 : h->refine_inline) : -1) + top_block_key(h);
-}
 
 // first pass z = K^-1 b, residual, and the in-graph correction passes
-static int solve_enqueue(hipfact_handle* h, const double* b, double* z) {
+static int solve_enqueue(hipfact_handle* h, const double* b, double* z, const hipfact::SolveDecision& d) {
   const double* bb = b;
   if (h->refine_steps > 0 && b == z) {  // keep a private copy of b for the residual
     HCHECK(h, hipMemcpyAsync(h->d_rhs.p, b, (size_t)h->N_ext * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     bb = h->d_rhs.as<double>();
   }
   solve_once_async(h, bb, z, false, nullptr);
-  if (h->refine_steps > 0 && !h->skip_resid_now) {
-    residual_async(h, bb, z, h->d_res.as<double>(), true, defers_decide(h));
-    return correct_enqueue(h, bb, z, h->refine_inline);
+  if (h->refine_steps > 0 && !d.unchecked) {
+    residual_async(h, bb, z, h->d_res.as<double>(), true, d.defer);
+    return correct_enqueue(h, bb, z, d.passes);
   }
   HCHECK(h, hipGetLastError());
   return HIPFACT_OK;
@@ -874,7 +839,8 @@ static int top_block_touch(hipfact_handle* h) {
   return HIPFACT_OK;
 }
 
-static int solve_async(hipfact_handle* h, const double* b, double* z) {
+// all_checked: every solve of the caller's call takes a residual, whatever the check interval (multi_single_cols)
+static int solve_async(hipfact_handle* h, const double* b, double* z, bool all_checked = false) {
   h->sol_prefetched = false;
   if (h->N_ext == 0) return HIPFACT_OK;
   // the top levels of the tree as one dense block from the top_block_after-th solve of a factorisation on (a caller
@@ -882,44 +848,23 @@ static int solve_async(hipfact_handle* h, const double* b, double* z) {
   // formed once and saves two hops per level and solve)
   ++h->solves_this_factor;
   if (int rc = top_block_touch(h)) return rc;
-  if (h->refine_steps > 0 && h->refine_adaptive && h->inline_probe && h->solve_seq > h->seq_at_factor) {
-    // Has the previous solve of this factorisation been judged yet?  (A peek at the pinned copy, no
-    // synchronisation.)  If its first pass met the tolerance with room to spare, the following
-    // solves drop the correction pass from their graph - its kernels would return at once, but 883
-    // workgroups per launch still have to be dispatched for that.  A solve that does need a pass is
-    // continued at the next synchronising entry point, which also puts the pass back.
-    const RefineCtl* hc = h->h_ctl.as<RefineCtl>();
-    if (__atomic_load_n(&hc->seq, __ATOMIC_ACQUIRE) == h->solve_seq) {
-      judge_conditioning(h, first_pass_sufficed(*hc));
-      h->inline_probe = false;
-    }
-  }
-  const bool defer = defers_decide(h);
-  // (defer <=> the factorisation has been judged well-conditioned: the first pass alone met a quarter of the tolerance)
-  // (the interval between two checks grows while they keep passing - refine_check_backoff, up to refine_check_max
-  // solves: what a check guards against is a factorisation gone bad, and that shows on its first solves)
-  if (h->check_interval_now < 1) h->check_interval_now = h->refine_check_every;
-  const bool unchecked = defer && (!h->inline_probe || h->wc_hint) && h->check_interval_now > 1 &&
-                         (h->solves_since_check % h->check_interval_now) != 0;
-  if (!unchecked && h->refine_check_every > 1 && h->solves_since_check >= h->check_interval_now && h->refine_check_backoff > 1)
-    h->check_interval_now = std::min(std::max(h->refine_check_max, h->refine_check_every), h->check_interval_now * h->refine_check_backoff);
-  h->solves_since_check = unchecked ? h->solves_since_check + 1 : 1;
-  h->num_checked += (!unchecked && h->refine_steps > 0);
-  if (!tree_delivers_verdict(h)) flush_decide(h);  // no tree launch to deliver it
-  h->skip_resid_now = unchecked;
-  h->last_solve_checked = !unchecked;
+  // Has the previous solve of this factorisation been judged yet?  (A peek at the pinned copy, no synchronisation.)  A
+  // graph without the correction pass saves the dispatch of 883 workgroups whose kernels would return at once; a solve
+  // that does need a pass is continued at the next synchronising entry point, which also puts the pass back.
+  hipfact::Cadence cad = cadence(h);
+  const hipfact::CadenceKnobs knobs = cadence_knobs(h);
+  const hipfact::SolveDecision d = cad.solve_decision(knobs, tree_delivers_verdict(h),
+                                                      cad.wants_peek(knobs) ? ctl_peek_pinned(h) : hipfact::CtlPeek{-1, 0, 0, 0, 0.0, 0.0}, all_checked);
+  if (d.flush_first) flush_decide(h);  // no tree launch to deliver it
   // (an unchecked steady-state solve is two launches: queued directly - replaying a two-node graph measures 4-5 us
   // slower per solve than the launches themselves)
-  const int key = solve_graph_key(h, defer);
-  h->note(unchecked ? 'U' : 'S', key);
-  int rc = unchecked ? solve_enqueue(h, b, z) : run_cached(h, 1, b, z, [&] { return solve_enqueue(h, b, z); }, key);
-  h->skip_resid_now = false;
+  const int key = d.key + top_block_key(h);
+  h->note(d.unchecked ? 'U' : 'S', key);
+  const int rc = d.unchecked ? solve_enqueue(h, b, z, d) : run_cached(h, 1, b, z, [&] { return solve_enqueue(h, b, z, d); }, key);
   if (rc) return rc;
-  if (!unchecked) h->decide_deferred = defer;  // (the tree launch of this solve has delivered an older one)
+  cad.solve_queued(knobs, d);
   h->num_solve++;
   h->solved = true;
-  if (h->refine_steps > 0 && !unchecked) h->solve_seq++;
-  h->ctl_pending = h->refine_steps > 0 && (!unchecked || h->ctl_pending);
   h->last_b = (b == z) ? h->d_rhs.as<double>() : b;
   h->last_z = z;
   return HIPFACT_OK;
@@ -969,15 +914,16 @@ static bool stalled_retry_applies(const hipfact_handle* h) { return static_pivot
 // a timed-out dataflow launch.  (synced: the caller has just awaited the stream behind the solve and its verdict)
 static int finish_solve(hipfact_handle* h, bool* continued = nullptr, bool synced = false) {
   if (continued) *continued = false;
-  if (!h->ctl_pending) return HIPFACT_OK;
-  const bool verdict_queued_now = h->decide_deferred;
+  hipfact::Cadence cad = cadence(h);
+  if (!cad.verdict_unread()) return HIPFACT_OK;
+  const bool verdict_queued_now = cad.verdict_outstanding();
   flush_decide(h);
   if (!synced || verdict_queued_now) HCHECK(h, hipStreamSynchronize(h->stream));
   RefineCtl c;
   memcpy(&c, h->h_ctl.p, sizeof(c));
   int more = 0;
   while (!c.done && h->refine_adaptive && c.iters < h->refine_max) {
-    const int passes = std::min(std::max(h->refine_inline, 1), h->refine_max - c.iters);
+    const int passes = std::min(std::max(cad.passes_in_graph(), 1), h->refine_max - c.iters);
     const double* b = h->last_b;
     double* z = h->last_z;
     h->note('C', passes + top_block_key(h));
@@ -987,14 +933,9 @@ static int finish_solve(hipfact_handle* h, bool* continued = nullptr, bool synce
     memcpy(&c, h->h_ctl.p, sizeof(c));
     ++more;
   }
-  h->ctl_pending = false;
+  cad.verdict_read(cadence_knobs(h), ctl_peek(c, c.seq));
   h->last_ctl = c;
   if (more > 0) h->sol_prefetched = false;  // (the copy sent to the host behind the solve is the unrefined one)
-  if (h->inline_probe && h->refine_adaptive && h->refine_steps > 0) {
-    // (the verdict of the first solve of this factorisation, read here instead of at the next solve's peek)
-    if (first_pass_sufficed(c)) judge_conditioning(h, true);
-    h->inline_probe = false;
-  }
   if (continued) *continued = more > 0;
   // A refinement that STALLS on a row-dictionary structure which carries rows outside the working set (unit pivots
   // that take part in the ordering): for a nearly rank-deficient working set the quality of the statically pivoted
@@ -1006,13 +947,7 @@ static int finish_solve(hipfact_handle* h, bool* continued = nullptr, bool synce
     if (rc) return rc;
     return finish_solve(h, continued);
   }
-  if (c.iters > 0) h->num_refined++;
-  h->num_passes += c.iters;
-  // the next solves of this factorisation carry as many passes in their graph as this one needed
-  if (more > 0) {
-    h->refine_inline = std::min(std::max(h->refine_inline, c.iters), 4);
-    h->wc_hint = false;
-  }
+  cadence(h).verdict_counted(ctl_peek(c, c.seq), more);
   const Verdict v = refine_verdict(h, c);
   if (v == Verdict::stalled && stalled_retry_applies(h) && h->last_b && h->last_z) {
     const double* b2 = h->last_b;

@@ -158,26 +158,12 @@ struct GraphList {
   void push_back(const GraphEntry& g) { v.push_back(g); }
 };
 
-// What the single-solve path (solve_async, finish_solve) remembers about the CURRENT factorisation of a plan (it parks
-// with the plan).  Solves that are not to be remembered (multi_single_cols) put it back as a whole.  seq_at_factor,
-// hint_seq_seen, first_factor_seq place the factorisation in the handle's solve_seq, which such solves do advance: not here.
+// What the single-solve path (solve_async, finish_solve) remembers about the CURRENT factorisation of a plan besides
+// its refinement cadence (PlanState::factor_cad); it parks with the plan, and solves that are not to be remembered put
+// it back (KeptSolveMemo).
 struct FactorMemo {
   bool solved = false;           // a single solve has been queued on this factorisation
   long solves_this_factor = 0;   // (the count that forms the top block)
-  int refine_inline = 1;         // correction passes currently carried by the solve graphs
-  bool inline_probe = true;      // the first solve of this factorisation has not been looked at yet
-  bool wc_hint = false;          // the previous factorisation of this plan was judged well-conditioned (first pass enough)
-  // `*this` saved in front of such solves, `now` what they left.  Everything goes back, with ONE exception: a factorisation
-  // not yet judged when saved (inline_probe) keeps the judgement found since, and inline_probe itself is never put back.
-  FactorMemo put_back_over(const FactorMemo& now) const {
-    FactorMemo r = *this;
-    r.inline_probe = now.inline_probe;
-    if (inline_probe) {
-      r.refine_inline = now.refine_inline;
-      r.wc_hint = now.wc_hint;
-    }
-    return r;
-  }
 };
 
 // Everything that belongs to ONE symbolic plan: the plan, its device image, the numeric arenas
@@ -202,9 +188,8 @@ struct PlanState : FactorMemo {
   int n_inactive = 0;         // rows of the structure outside the current working set (cmap == -1): k_diag_inactive writes their unit pivots
   int n_bounds = 0;           // active bounds of the current working set
   unsigned long long use_stamp = 0;  // LRU clock
-  int seq_at_factor = 0;      // handle's solve_seq at the time of the last factorisation
-  int hint_seq_seen = -1;     // the last verdict a refactorisation has looked at (factor_hint_peek)
-  int first_factor_seq = -1;  // handle's solve_seq at the first factorisation of this plan (verdicts behind it belong to its factorisations)
+  hipfact::FactorCadence factor_cad;  // refinement cadence (refine_cadence.h): the part of the current factorisation ...
+  hipfact::PlanCadence plan_cad;      // ... and where the plan's factorisations stand in the handle's count of solves
   GraphList graphs;
   int ftop_level = 1 << 30, ftop_count = 0;
   size_t ftop_lds = 0;
@@ -278,23 +263,14 @@ struct PlanState : FactorMemo {
 #include "vtable_superset.inc"
 #undef VTABLE_SUPERSET_TYPES
 
-// What the single-solve path remembers on the handle for the NEXT call to find: the last solve, the cadence of the
-// residual checks, the counters of hipfact_get_info.  multi_single_cols copies the struct out and back around its columns:
-// a member added here is put back there.  NOT here (the columns really advance them): ctl_pending, solve_seq, decide_deferred.
+// What the single-solve path remembers on the handle for the NEXT call to find besides the cadence of the residual
+// checks (hipfact_handle::solve_cad): the last solve and its verdict.  Put back by KeptSolveMemo.
 struct SingleSolveMemo {
   const double* last_b = nullptr;
   double* last_z = nullptr;
   RefineCtl last_ctl = {1, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0};
-  bool last_solve_checked = true;  // the last solve_async carried a residual (and possibly correction passes)
   bool sol_prefetched = false;     // h_sol_pin holds the solution of the last solve (valid once ev_sol has fired)
-  // Once a factorisation has been judged well-conditioned (its solves meet the tolerance in the first pass with room
-  // to spare: no correction pass in their graph), the residual of K z = b is checked on every k-th solve only - the
-  // reference's MA57 path never checks (fact_ma57.c:18).  1: every solve (the blocked solve's setting for its call).
-  int refine_check_every = 8;
-  int check_interval_now = 0;      // (the interval in force; back to refine_check_every with every factorisation)
-  long solves_since_check = 0;
-  // solves / those whose residual was taken / that applied at least one correction pass / passes applied in total
-  long num_solve = 0, num_checked = 0, num_refined = 0, num_passes = 0;
+  long num_solve = 0;
 };
 
 struct hipfact_handle : PlanState, SingleSolveMemo {
@@ -362,17 +338,17 @@ struct hipfact_handle : PlanState, SingleSolveMemo {
   std::string warning;  // of the last factorisation ("" = none): rank deficiency handled by static pivoting
   bool equilibrate = true;       // row equilibration of the constraint block (saddle mode)
   bool decide_lazy = true;       // verdict of a solve without correction passes delivered by the next tree launch
-  int refine_check_backoff = 2;  // the interval (refine_check_every, SingleSolveMemo) is multiplied by this after every periodic check (1 = fixed interval)
+  // refinement cadence (refine_cadence.h; cadence(h) below): what is remembered between solves, what every solve advances
+  hipfact::SolveCadence solve_cad;
+  hipfact::LiveCadence live_cad;
+  int refine_check_every = 8;    // a factorisation judged well-conditioned takes the residual on every k-th solve only (the reference's MA57 path never checks, fact_ma57.c:18)
+  int refine_check_backoff = 2;  // the interval is multiplied by this after every periodic check (1 = fixed interval)
   int refine_check_max = 64;     // ... up to this many solves between two checks
   double pivot_ratio = 1.0;      // largest / smallest positive pivot of the last factorisation (check_info)
   bool no_solve_retry = false;   // (a probe solve: no change of plan behind a stalled refinement)
   long dense_probes = 0;
-  bool skip_resid_now = false;   // (the solve being queued is one of the unchecked ones)
-  bool decide_deferred = false;  // ... and such a verdict is outstanding
-  bool decide_rides = false;     // (during factor_enqueue) it is delivered by the first block of k_row_scale
+  bool decide_rides = false;     // (during factor_enqueue) a pending verdict is delivered by the first block of k_row_scale
   const double* vals_ride = nullptr;  // (during factor_enqueue) the caller's device values: k_row_scale reads them there and writes d_Kval
-  bool ctl_pending = false;      // the control block of the last solve has not been looked at yet
-  int solve_seq = 0;             // solves with a residual queued since the control block was last cleared
   bool use_graph = true;         // replay captured hipGraphs instead of re-enqueueing ~100 launches
   // The single-launch dataflow kernels rely on workgroups being dispatched in index order (observed per XCD on every
   // gfx9 part, documented nowhere; the XCDs do not wait for one another - struct Turn, k_solve_tree's epoch).  Their
@@ -498,6 +474,35 @@ struct hipfact_handle : PlanState, SingleSolveMemo {
   void* h_xout_dev = nullptr;
   long extra_solves = 0, extra_passes = 0;
   int extra_last_status = 0;
+};
+
+// The refinement cadence of the handle (refine_cadence.h): its four parts, the option values it reads, and what the
+// host sees of a control block.
+static inline hipfact::Cadence cadence(hipfact_handle* h) { return {h->factor_cad, h->plan_cad, h->solve_cad, h->live_cad}; }
+static inline hipfact::CadenceKnobs cadence_knobs(const hipfact_handle* h) {
+  return {h->refine_steps, h->refine_adaptive, h->refine_check_every, h->refine_check_backoff, h->refine_check_max, h->decide_lazy,
+          h->factor_hint_peek};
+}
+static inline hipfact::CtlPeek ctl_peek(const RefineCtl& c, int seq) { return {seq, c.done, c.status, c.iters, c.omega, c.tol}; }
+// ... of the pinned copy, as it stands (no synchronisation)
+static inline hipfact::CtlPeek ctl_peek_pinned(const hipfact_handle* h) {
+  const RefineCtl* hc = h->h_ctl.as<RefineCtl>();
+  return ctl_peek(*hc, __atomic_load_n(&hc->seq, __ATOMIC_ACQUIRE));
+}
+
+// What the single-solve path remembers between solves, saved in front of solves that are not to be remembered (the
+// columns of multi_single_cols, the plain solves of the extra-precise solve) and put back behind them: the call is not
+// "the last solve".  What goes back, and what does not, is Cadence::put_back's to say.
+struct KeptSolveMemo {
+  SingleSolveMemo single;
+  FactorMemo factor;
+  hipfact::SavedCadence cad;
+  explicit KeptSolveMemo(hipfact_handle* h) : single(*h), factor(*h), cad(cadence(h).save()) {}
+  void put_back(hipfact_handle* h) const {
+    static_cast<SingleSolveMemo&>(*h) = single;
+    static_cast<FactorMemo&>(*h) = factor;
+    cadence(h).put_back(cad);
+  }
 };
 
 struct hipfact_spmat {

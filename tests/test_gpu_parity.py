@@ -1564,6 +1564,124 @@ def test_residual_checked_on_every_kth_solve_only(fact):
     assert fact.info("refine_check_interval") == 8
 
 
+# what test_refinement_cadence_solve_by_solve records behind every solve (and behind the one hipfact_check): num_solve,
+# num_checked, num_refined, num_passes, refine_check_interval, refine_inline, last_status - as the commit before
+# refine_cadence.h gave them.  Factorisation 1 (a new plan): solve 1 carries the pass and is judged at solve 2's peek;
+# checks at 1, 4, 10, 22 (the interval becomes 6, 12, 24 behind them).  Factorisation 2 starts without the pass
+# (factor_hint_peek) and checks the same solves; the row behind its solve 10 stands twice (behind hipfact_check).
+_CADENCE_TABLE = [
+    (1, 1, 0, 0, 3, 1, 0), (2, 1, 0, 0, 3, 0, 0), (3, 1, 0, 0, 3, 0, 0), (4, 2, 0, 0, 6, 0, 0), (5, 2, 0, 0, 6, 0, 0),
+    (6, 2, 0, 0, 6, 0, 0), (7, 2, 0, 0, 6, 0, 0), (8, 2, 0, 0, 6, 0, 0), (9, 2, 0, 0, 6, 0, 0), (10, 3, 0, 0, 12, 0, 0),
+    (11, 3, 0, 0, 12, 0, 0), (12, 3, 0, 0, 12, 0, 0), (13, 3, 0, 0, 12, 0, 0), (14, 3, 0, 0, 12, 0, 0), (15, 3, 0, 0, 12, 0, 0),
+    (16, 3, 0, 0, 12, 0, 0), (17, 3, 0, 0, 12, 0, 0), (18, 3, 0, 0, 12, 0, 0), (19, 3, 0, 0, 12, 0, 0), (20, 3, 0, 0, 12, 0, 0),
+    (21, 3, 0, 0, 12, 0, 0), (22, 4, 0, 0, 24, 0, 0), (23, 4, 0, 0, 24, 0, 0), (24, 4, 0, 0, 24, 0, 0), (25, 4, 0, 0, 24, 0, 0),
+    (26, 4, 0, 0, 24, 0, 0), (27, 4, 0, 0, 24, 0, 0), (28, 4, 0, 0, 24, 0, 0), (29, 4, 0, 0, 24, 0, 0), (30, 4, 0, 0, 24, 0, 0),
+    (31, 5, 0, 0, 3, 0, 0), (32, 5, 0, 0, 3, 0, 0), (33, 5, 0, 0, 3, 0, 0), (34, 6, 0, 0, 6, 0, 0), (35, 6, 0, 0, 6, 0, 0),
+    (36, 6, 0, 0, 6, 0, 0), (37, 6, 0, 0, 6, 0, 0), (38, 6, 0, 0, 6, 0, 0), (39, 6, 0, 0, 6, 0, 0), (40, 7, 0, 0, 12, 0, 0),
+    (40, 7, 0, 0, 12, 0, 0), (41, 7, 0, 0, 12, 0, 0), (42, 7, 0, 0, 12, 0, 0), (43, 7, 0, 0, 12, 0, 0), (44, 7, 0, 0, 12, 0, 0),
+    (45, 7, 0, 0, 12, 0, 0), (46, 7, 0, 0, 12, 0, 0), (47, 7, 0, 0, 12, 0, 0), (48, 7, 0, 0, 12, 0, 0), (49, 7, 0, 0, 12, 0, 0),
+    (50, 7, 0, 0, 12, 0, 0), (51, 7, 0, 0, 12, 0, 0), (52, 8, 0, 0, 24, 0, 0), (53, 8, 0, 0, 24, 0, 0), (54, 8, 0, 0, 24, 0, 0),
+    (55, 8, 0, 0, 24, 0, 0), (56, 8, 0, 0, 24, 0, 0), (57, 8, 0, 0, 24, 0, 0), (58, 8, 0, 0, 24, 0, 0), (59, 8, 0, 0, 24, 0, 0),
+    (60, 8, 0, 0, 24, 0, 0),
+]
+
+
+def test_refinement_cadence_solve_by_solve():
+    """The cadence of the single solve (sleqp_amd/csrc/refine_cadence.h) on the device, solve by solve: two
+    factorisations of one system, 30 solves each with refine_check_every 3, backoff 2 (refine_check_max is no runtime
+    option but fixed at 64; within 30 solves a bound of 12 would change no check, only the interval behind solve 22), the
+    stream awaited behind every solve (so that every peek finds what the device has delivered) and one hipfact_check behind
+    solve 10 of the second factorisation.  The counters and the cadence's info keys behind every solve equal a table
+    of literals, the same script of events through hipfact_debug_refine_cadence gives the same table, and every
+    solution has the bits of the same sequence with a check behind every solve."""
+    import ctypes as C
+
+    from sleqp_amd import _lib
+    from sleqp_amd.fact import HipFact
+    from sleqp_amd.sparse import SleqpMat
+
+    hip = C.CDLL("libamdhip64.so")  # (device buffers from the runtime the library is linked against)
+
+    def to_device(a):
+        p = C.c_void_p()
+        assert hip.hipMalloc(C.byref(p), C.c_size_t(a.nbytes)) == 0
+        assert hip.hipMemcpy(p, a.ctypes.data_as(C.c_void_p), C.c_size_t(a.nbytes), 1) == 0
+        return p
+
+    def to_host(p, n):
+        out = np.empty(n)
+        assert hip.hipMemcpy(out.ctypes.data_as(C.c_void_p), p, C.c_size_t(out.nbytes), 2) == 0
+        return out
+
+    J, vi, ci, _ = _problem(1000, 500, "b", 0.0, 4)
+    N, kc, kr, kd = oracle.fill_aug_jac(1000, 500, J.indptr, J.indices, J.data, vi, ci)
+    rng = np.random.default_rng(44)
+    rhs = [rng.standard_normal(N) for _ in range(5)]
+    d_vals = to_device(np.ascontiguousarray(kd, dtype=np.float64))
+    d_rhs = [to_device(b) for b in rhs]
+    d_sol = to_device(np.zeros(N))
+    keys = ("num_solve", "num_checked", "num_refined", "num_passes", "refine_check_interval", "refine_inline", "last_status")
+    FACTOR, SOLVE, VERDICT = 0, 1, 2
+    runs = {}
+    for every in (3, 1):
+        f = HipFact(device=0)  # (a handle of its own per run: the same plan history in both)
+        f.set_option("refine_check_every", every)
+        f.set_option("refine_check_backoff", 2)
+        table, sols, script = [], [], []
+        for rep in range(2):
+            if rep == 0:
+                f.set_matrix(SleqpMat(N, N, kc, kr, kd))
+                assert f.info("saddle") == 1.0 and f.info("m") > 0 and f.info("tree_solve") == 1.0
+            else:
+                f.refactor_device(d_vals.value)
+            script.append(FACTOR)
+            for i in range(30):
+                f.solve_device(d_rhs[i % len(rhs)].value, d_sol.value)
+                f.synchronize()
+                script.append(SOLVE)
+                table.append(tuple(int(f.info(k)) for k in keys))
+                sols.append(to_host(d_sol, N))
+                if rep == 1 and i == 9:
+                    f.check()
+                    script.append(VERDICT)
+                    table.append(tuple(int(f.info(k)) for k in keys))
+        assert f.info("dataflow_fallbacks") == 0 and f.info("solve_timeouts") == 0
+        runs[every] = (table, sols, script)
+        f.free()
+    for p_ in [d_vals, d_sol] + d_rhs:
+        assert hip.hipFree(p_) == 0
+    table, sols, script = runs[3]
+    for row in table:
+        print(row)
+    assert table == _CADENCE_TABLE
+    # the same events through the header alone.  What the host's peek finds: every first residual queued so far has been
+    # judged, except that of a last solve that left its verdict to the next launch
+    lib = _lib.load()
+    knobs = np.array([1, 1, 3, 2, 64, 1, 1], dtype=np.int32)
+    events, rows, nsolve = [], [], 0
+    for kind in script:
+        judged = rows[-1][10] - rows[-1][12] if rows else 0  # (solve_seq - decide_deferred behind the last event)
+        # flag: FACTOR the captured sequence, SOLVE the tree launch delivers verdicts, VERDICT nothing continued by the
+        # host; then the control block: seq, done, status 0, no pass, omega 0 <= tol / 4
+        events.append((kind, 0 if kind == VERDICT else 1, judged, 1, 0, 0, 0.0, 1.0))
+        ev = np.array(events, dtype=np.float64)
+        out = np.zeros((len(events), 20), dtype=np.int64)
+        assert lib.hipfact_debug_refine_cadence(knobs.ctypes.data_as(C.c_void_p), len(events), ev.ctypes.data_as(C.c_void_p),
+                                                out.ctypes.data_as(C.c_void_p)) == 0
+        rows.append(tuple(int(v) for v in out[-1]))
+    replay = []  # (num_solve, num_checked, num_refined, num_passes, refine_check_interval, refine_inline)
+    for kind, r in zip(script, rows):
+        nsolve += kind == SOLVE
+        if kind != FACTOR:
+            replay.append((nsolve, r[9], r[13], r[14], r[7], r[4]))
+    assert replay == [t[:6] for t in table]
+    # unchecked solves and checked ones: the same bits
+    assert [t[1] for t in runs[1][0]] == [t[0] for t in runs[1][0]]  # (every solve checked there)
+    assert len(sols) == len(runs[1][1]) == 60
+    for a, b in zip(sols, runs[1][1]):
+        assert np.array_equal(a, b)
+
+
 def test_dense_chain_levels_as_small_dataflow_launches(fact):
     """Single-front levels of a dense chain below the top-of-tree launch run their pivot and panel items as ONE
     small dataflow launch (panel workgroups following the posted pivot block) instead of two launches.  Agreement with
