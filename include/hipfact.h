@@ -240,6 +240,64 @@ int hipfact_solve_extra(hipfact_handle* h, const double* rhs, double* sol, hipfa
  * d_b or d_z (HIPFACT_EINVAL); HIPFACT_ESTATE before a factorisation.  Deterministic: the same bits on every call. */
 int hipfact_residual_device(hipfact_handle* h, const double* d_b, const double* d_z, double* d_res, int extended);
 
+/* ---- condition estimate: ||K||_1 ||K^-1||_1 from a handful of blocked solves -----------------------------------
+ * hipfact_condition returns the ratio of the pivots of the block-diagonal factor: a proxy for the conditioning of the
+ * reduced matrix S^, not of K.  This call estimates the 1-norm condition number of K itself (LAPACK's xSYCON / xLACN2,
+ * MA57's estimate): norm1 = ||K||_1 exactly, from the column sums of |K| taken by the walk of the residual kernels - the
+ * matrix residuals are taken against, inactive rows of a superset plan left out -, and inv_norm1 = a lower bound of
+ * ||K^-1||_1 from the block 1-norm estimator of Higham and Tisseur (SIAM J. Matrix Anal. Appl. 21, 2000, Algorithm 2.4)
+ * with t = 16 columns, the width of a full block of hipfact_solve_device_multi.  A = K^-1 is symmetric, so one kind of
+ * product serves.  The rule (sleqp_amd/csrc/condest_rule.h), without a random number generator:
+ *   N <= 16: X = I, one block; inv_norm1 is the largest column 1-norm of K^-1 and exact = 1.
+ *   N > 16:  X[i][j] = s(i, j) / N, s(i, 0) = +1, else with u = (i 2654435761 + j 40503 + 12345) mod 2^32,
+ *            u = (u 2246822519) mod 2^32: s = +1 if bit 16 of u is 0, else -1.  Then for k = 1 .. 5:
+ *     1. Y = A X, c_j = ||Y_j||_1, jb the first index of the maximum, est = c_jb; k >= 2 and est <= est_old: stop NO_GAIN
+ *        with the old estimate and witness.  Otherwise witness = Y_jb, ind_best = ind[jb] (k >= 2); k = 5: stop ITMAX.
+ *     2. S = sign(Y), sign(0) = +1; k >= 2 and every column of S parallel to one of the previous S: stop PARALLEL.
+ *     3. Z = A S, h_i = max_j |Z_ij|; k >= 2 and max_i h_i == h[ind_best]: stop MAX_AT_BEST.
+ *     4. the indices by h descending, the lower index first among equals; k >= 2 and the first 16 all used before: stop
+ *        REVISIT; otherwise ind = the first up to 16 unused indices, X = their unit vectors (zero columns behind them).
+ * The witness certifies the bound: ||witness||_1 = inv_norm1, and witness = K^-1 e_column (column >= 0) or K^-1 times
+ * start column -1 - column.  equilibrated = 0: the caller's K in the caller's numbering.  equilibrated != 0: K^ = D K D,
+ * the matrix the factorisation works on - D = diag(I, row scales of the constraint block) in saddle mode (powers of
+ * two; K^^-1 X = D^-1 K^-1 D^-1 X is formed with exact scalings around the same solve), the identity in generic mode,
+ * which scales nothing.  norm1, inv_norm1 and the witness are reported in the space asked for.
+ * The call BLOCKS, with the contract of hipfact_solve_device_multi and hipfact_solve_device_extra: on entry it does what
+ * hipfact_check does; HIPFACT_ESTATE before a factorisation; it does not become "the last solve" - hipfact_solution*
+ * still return the earlier single solve, and a single solve issued afterwards gives the bits it would have given without
+ * this call.  Every K^-1 X is one call into the blocked solve's internal path with 16 columns, in place, with the
+ * options in force (row slices, per-column verdicts, the route through single solves on dense_mode = 2 plans; the
+ * "multi_*" counters count them); a column that makes the blocked solve return HIPFACT_ESINGULAR makes this call return
+ * it.  A failed workspace allocation returns HIPFACT_ENOMEM and leaves the handle usable for
+ * single and blocked solves.  The same handle state gives the same bits on every call: every sum and every selection
+ * has a fixed order.  Cost: blocks x one full block of the blocked solve plus the estimator's own kernels (a pass over
+ * the block and one host synchronisation per product); blocks <= 9, 4 on every system tried (EXPERIMENTS.md,
+ * "Condition estimate").
+ * Info: "cond_estimates" calls that ran, "cond_blocks" blocked passes they asked for, "cond_last" the last cond1.
+ * Option "condition_estimate" (hipfact_set_option; the estimate's own, kept out of the table below; readable through
+ * hipfact_get_info): 0 (default) hipfact_condition returns the pivot ratio; 1: cond1 of the caller's K from this
+ * estimator; 2: cond1 of the equilibrated K^; anything else is HIPFACT_EINVAL.  kappa_est and the refinement tolerance
+ * do not depend on it. */
+enum { HIPFACT_COND_STOP_EXACT = 0,      /* N <= 16: every column of K^-1 was formed */
+       HIPFACT_COND_STOP_NO_GAIN = 1,    /* the estimate did not grow */
+       HIPFACT_COND_STOP_PARALLEL = 2,   /* every sign column parallel to one of the previous block */
+       HIPFACT_COND_STOP_MAX_AT_BEST = 3,/* max_i h_i is attained at the best index */
+       HIPFACT_COND_STOP_REVISIT = 4,    /* the 16 largest h_i are all at indices already used */
+       HIPFACT_COND_STOP_ITMAX = 5 };
+typedef struct hipfact_cond_info {
+  double norm1;      /* ||K||_1 of the matrix the residual kernels take residuals against */
+  double inv_norm1;  /* the estimate of ||K^-1||_1: the 1-norm of the witness */
+  double cond1;      /* norm1 * inv_norm1 */
+  double omega;      /* largest backward error over the columns solved, as "last_omega" defines it */
+  int exact;         /* 1 with STOP_EXACT */
+  int iterations;    /* of the estimator */
+  int blocks;        /* passes of 16 columns it asked the blocked solve for */
+  int column;        /* >= 0: witness = K^-1 e_column; -1 - j: witness = K^-1 (start column j) */
+  int stop;          /* HIPFACT_COND_STOP_* */
+} hipfact_cond_info;
+int hipfact_condition_estimate(hipfact_handle* h, int equilibrated, hipfact_cond_info* info /* nullable */,
+                               double* d_witness /* nullable, device, N doubles */);
+
 /* Blocks until the queued work has finished and reports what the asynchronous
  * entry points above could not: a singular / rank-deficient factorisation
  * (HIPFACT_ESINGULAR), a solve whose iterative refinement stalled far above its
@@ -619,6 +677,17 @@ int hipfact_debug_multi_slices(int u, int slice_rows, int* tile_bounds /* cap + 
  * hipfact_extra_info.  Every output pointer may be NULL. */
 int hipfact_debug_extra_rule(int nblocks, int npasses, const double* dn, const double* zn, int pass_cap, int* applied,
                              int* status, double* ferr, double* rho);
+/* The rule of hipfact_condition_estimate (sleqp_amd/csrc/condest_rule.h) with products by a dense N x N matrix A
+ * (column-major, ld >= N), no GPU needed; used by the tests.  The column 1-norms are summed in row order; norm1, cond1
+ * and omega are left NaN, because this entry point gets no K.  history: the indices the rule used, in order, -1 behind
+ * them (cap entries).  HIPFACT_EINVAL for N <= 0, ld < N, NULL A. */
+int hipfact_debug_condest_dense(int N, const double* A, long long ld, hipfact_cond_info* info,
+                                double* witness /* nullable */, int* history /* nullable, cap entries */, int cap);
+/* The same driver on a recorded sequence of reductions instead of products (the pass cap is tested on one that never
+ * stops): record k holds 37 doubles - the 16 column norms of iteration k + 1, 1 if every sign column is parallel, max h,
+ * h[ind_best], the history indices in front of the best unused index, the number of unused candidates and 16 of them.
+ * HIPFACT_EINVAL when the records end before the rule does (N > 16 needs up to 5). */
+int hipfact_debug_condest_recorded(int N, int nrecords, const double* records, hipfact_cond_info* info);
 /* The refinement cadence of the single solve as a pure host function (no GPU needed; used by the tests): how many
  * correction passes the solve graphs carry, which solves take a residual, and which leave their verdict to the next tree
  * launch.  A script of events runs through the transitions the runtime calls, on one plan of one fresh handle.

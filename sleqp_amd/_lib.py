@@ -28,6 +28,7 @@ SYMBOLS = [
     "hipfact_create", "hipfact_free", "hipfact_retain", "hipfact_last_error", "hipfact_last_warning", "hipfact_set_matrix", "hipfact_solve_sparse",
     "hipfact_solve_dense", "hipfact_solution", "hipfact_solution_view", "hipfact_condition", "hipfact_refactor_device",
     "hipfact_solve_device", "hipfact_solve_device_multi", "hipfact_solve_multi",
+    "hipfact_condition_estimate", "hipfact_debug_condest_dense", "hipfact_debug_condest_recorded",
     "hipfact_solve_device_extra", "hipfact_solve_extra", "hipfact_residual_device", "hipfact_debug_extra_rule", "hipfact_debug_dd_residual", "hipfact_solution_device", "hipfact_synchronize", "hipfact_check", "hipfact_stream",
     "hipfact_assemble_kkt", "hipfact_reduced_matrix", "hipfact_spmat_create", "hipfact_spmat_update_values", "hipfact_spmat_free",
     "hipfact_spmat_mult_vec", "hipfact_spmat_mult_vec_trans", "hipfact_spmat_mult_vec_sym",
@@ -80,6 +81,10 @@ def load() -> C.CDLL:
         lib.hipfact_debug_extra_rule.argtypes = [ci, ci, vp, vp, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(cd), C.POINTER(cd)]
         lib.hipfact_debug_dd_residual.argtypes = [ci, vp, vp, cd, ci]
         lib.hipfact_debug_dd_residual.restype = cd
+    if hasattr(lib, "hipfact_condition_estimate"):
+        lib.hipfact_condition_estimate.argtypes = [vp, ci, vp, vp]
+        lib.hipfact_debug_condest_dense.argtypes = [ci, vp, C.c_longlong, vp, vp, vp, ci]
+        lib.hipfact_debug_condest_recorded.argtypes = [ci, ci, vp, vp]
     lib.hipfact_solution_device.argtypes = [vp, C.POINTER(vp)]
     lib.hipfact_synchronize.argtypes = [vp]
     lib.hipfact_check.argtypes = [vp]

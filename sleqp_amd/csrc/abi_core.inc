@@ -592,6 +592,12 @@ int hipfact_condition(hipfact_handle* h, double* condition) {
   if (rc) return rc;
   if ((rc = require_factor(h, "hipfact_condition"))) return rc;
   if (!condition) return HIPFACT_EINVAL;
+  if (h->condition_estimate != 0) {  // option "condition_estimate": cond1 of K (1) / of the equilibrated K^ (2)
+    hipfact_cond_info ci;
+    if ((rc = hipfact_condition_estimate(h, h->condition_estimate == 2, &ci, nullptr))) return rc;
+    *condition = ci.cond1;
+    return HIPFACT_OK;
+  }
   const Plan& P = h->plan;
   if (P.nsuper == 0) {
     *condition = 1.0;

@@ -221,6 +221,11 @@ int hipfact_set_option(hipfact_handle* h, const char* name, double value) {
     const int rc = multi_set_option(h, name, value, known);
     if (known) return rc;
   }
+  {  // ... and so does the condition estimate (runtime_condest.inc)
+    bool known = false;
+    const int rc = condest_set_option(h, name, value, known);
+    if (known) return rc;
+  }
   for (const OptionRow& row : kOptions) {
     if (!row.name || strcmp(name, row.name)) continue;
     const int changed = row.set(h, value);
@@ -256,6 +261,7 @@ int hipfact_debug_copy(hipfact_handle* h, const char* name, void* out, size_t by
   if (!strcmp(name, "late_cols")) return host_copy(P.late_cols);
   if (!strcmp(name, "sn_level")) return host_copy(P.sn_level);
   if (!strcmp(name, "dense_cols")) return host_copy(P.dense_cols);
+  if (!strcmp(name, "cond_history")) return host_copy(h->cond_history);  // index history of the last condition estimate
   const DevBuf* b = nullptr;
   if (!strcmp(name, "L")) b = &h->d_L;
   else if (!strcmp(name, "U")) b = &h->d_U;
@@ -268,6 +274,16 @@ int hipfact_debug_copy(hipfact_handle* h, const char* name, void* out, size_t by
   else if (!strcmp(name, "dscale")) b = &h->d_dscale;
   else if (!strcmp(name, "Kval")) b = &h->d_Kval;
   else if (!strcmp(name, "mY")) b = &h->d_mY;  // the last block of the blocked solve: m x MR, pivot order
+  if (!strcmp(name, "cond_d")) {  // diag(D) of the last condition estimate, caller's numbering (behind blocks, witness, h, a)
+    const size_t N = (size_t)h->N_ext, off = (2 * COND_T + 3) * N * sizeof(double);
+    if (!h->d_cblk.p || bytes > N * sizeof(double)) {
+      h->error = "hipfact_debug_copy: unknown buffer or size";
+      return HIPFACT_EINVAL;
+    }
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    HCHECK(h, hipMemcpy(out, h->d_cblk.as<char>() + off, bytes, hipMemcpyDeviceToHost));
+    return HIPFACT_OK;
+  }
   if (!b || !b->p || bytes > b->bytes) {
     h->error = "hipfact_debug_copy: unknown buffer or size";
     return HIPFACT_EINVAL;
@@ -473,6 +489,7 @@ int hipfact_get_info(const hipfact_handle* h, const char* name, double* value) {
   INFO("multi_solves", h->multi_solves) INFO("multi_cols", h->multi_cols) INFO("multi_blocks", h->multi_blocks)
   INFO("multi_passes", h->multi_passes) INFO("multi_single_cols", h->multi_single_cols) INFO("multi_failed_col", h->multi_failed_col)
   INFO("multi_sliced_fronts", h->mitems_for < 0 ? 0 : h->n_mcut) INFO("multi_slice_items", h->mitems_for < 0 ? 0 : h->n_mslices) INFO("multi_slice_rows", h->multi_slice_rows)
+  INFO("cond_estimates", h->cond_estimates) INFO("cond_blocks", h->cond_blocks) INFO("cond_last", h->cond_last) INFO("condition_estimate", h->condition_estimate)
   INFO("extra_solves", h->extra_solves) INFO("extra_passes", h->extra_passes) INFO("extra_last_status", h->extra_last_status)
   INFO("num_solve", h->num_solve) INFO("num_refined", h->solve_cad.num_refined) INFO("refine_adaptive", h->refine_adaptive)
   INFO("num_passes", h->solve_cad.num_passes) INFO("last_omega", h->last_ctl.omega) INFO("last_iters", h->last_ctl.iters)

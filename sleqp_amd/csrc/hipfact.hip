@@ -14,6 +14,7 @@
 //   dense_cols.inc      dense Jacobian columns                   krylov_device.inc    device-controlled CG
 //   runtime_multi.inc   blocked solve, 16 right-hand sides       abi_multi.inc        hipfact_solve[_device]_multi
 //   runtime_extra.inc   extra-precise solve (dd_arith.h)         abi_extra.inc        hipfact_solve[_device]_extra, _residual_device
+//   runtime_condest.inc 1-norm condition estimate (condest_rule.h) abi_condest.inc      hipfact_condition_estimate, _debug_condest_*
 //   refine_cadence.h    refinement cadence of the single solve: passes in the graph, residual checks, deferred verdicts
 //                       (pure host rules, like xcd_place.h and multi_slices.h)
 #include <hip/hip_runtime.h>
@@ -48,6 +49,7 @@
 #include "xcd_place.h"
 #include "multi_slices.h"
 #include "refine_cadence.h"
+#include "condest_rule.h"
 #include "dd_arith.h"
 
 #include "runtime_types.inc"
@@ -55,11 +57,13 @@
 #include "runtime_queue.inc"
 #include "runtime_multi.inc"
 #include "runtime_extra.inc"
+#include "runtime_condest.inc"
 
 extern "C" {
 #include "abi_core.inc"
 #include "abi_multi.inc"
 #include "abi_extra.inc"
+#include "abi_condest.inc"
 #include "abi_working_set.inc"
 #include "abi_krylov.inc"
 #include "abi_options.inc"

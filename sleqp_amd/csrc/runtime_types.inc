@@ -253,6 +253,10 @@ struct PlanState : FactorMemo {
   // extra-precise solve (runtime_extra.inc): its four vectors b | z | r | dz, N_ext doubles each; they live with the
   // plan because its solve graphs hold their addresses.  Allocated by the first such call of the state.
   DevBuf d_xvec;
+  // condition estimate (runtime_condest.inc), N_ext each: two N x 16 blocks, the witness, h, a = |K| v and the diagonal
+  // of D as doubles (d_cblk); two generations of sign words (d_cwords); the `used` bytes (d_cused).  They live with the
+  // plan because the single-solve route of a dense_mode = 2 plan captures graphs on the blocks' columns.
+  DevBuf d_cblk, d_cwords, d_cused;
 
   PlanState() = default;
   PlanState(PlanState&&) = default;
@@ -474,6 +478,16 @@ struct hipfact_handle : PlanState, SingleSolveMemo {
   void* h_xout_dev = nullptr;
   long extra_solves = 0, extra_passes = 0;
   int extra_last_status = 0;
+  // condition estimate (runtime_condest.inc): the partials of its reductions and the history list, the pinned block
+  // the host reads (norms, parallel flags, the selection); the option "condition_estimate" (what hipfact_condition
+  // returns: 0 the pivot ratio, 1 / 2 cond1 of K / of the equilibrated K^); counters of hipfact_get_info
+  DevBuf d_cpart;
+  PinBuf h_cout;
+  void* h_cout_dev = nullptr;
+  int condition_estimate = 0;
+  long cond_estimates = 0, cond_blocks = 0;
+  double cond_last = 0.0;
+  std::vector<int> cond_history;  // the index history of the last estimate, -1 behind it (hipfact_debug_copy "cond_history")
 };
 
 // The refinement cadence of the handle (refine_cadence.h): its four parts, the option values it reads, and what the

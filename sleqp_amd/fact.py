@@ -142,6 +142,25 @@ class HipFact:
             self._check(rc)
         return sol, info.as_dict(rc)
 
+    def condition_estimate(self, equilibrated: bool = False, want_witness: bool = False) -> dict:
+        """hipfact_condition_estimate: the 1-norm condition number of K (equilibrated: of K^ = D K D) from blocked
+        solves; blocks.  Returns the hipfact_cond_info as a dict (norm1, inv_norm1, cond1, omega, exact, iterations,
+        blocks, column, stop), with "history" (the indices the rule used) and, on request, "witness" (N doubles with
+        ||witness||_1 = inv_norm1)."""
+        import torch
+
+        info = CondInfo()
+        wit = torch.empty(max(self.N, 1), dtype=torch.float64, device=f"cuda:{int(self.info('device'))}") if want_witness else None
+        self._check(self._lib.hipfact_condition_estimate(self._h, 1 if equilibrated else 0, C.byref(info),
+                                                         C.c_void_p(wit.data_ptr()) if want_witness else None))
+        out = info.as_dict()
+        hist = np.empty(80, dtype=np.int32)
+        self._check(self._lib.hipfact_debug_copy(self._h, b"cond_history", _ptr(hist), hist.nbytes))
+        out["history"] = [int(i) for i in hist if i >= 0]
+        if want_witness:
+            out["witness"] = wit[:self.N].cpu().numpy()
+        return out
+
     def residual_device(self, d_b_ptr: int, d_z_ptr: int, d_res_ptr: int, extended: bool = True):
         """hipfact_residual_device: res = b - K z on the handle's stream (extended: double-double accumulation)."""
         self._check(self._lib.hipfact_residual_device(self._h, C.c_void_p(d_b_ptr), C.c_void_p(d_z_ptr),
@@ -293,6 +312,36 @@ class ExtraInfo(C.Structure):
     def as_dict(self, rc: int = 0) -> dict:
         return {"rc": rc, "passes": self.passes, "status": self.status, "ferr": self.ferr, "dz_rel": self.dz_rel,
                 "rho": self.rho, "omega": self.omega}
+
+
+class CondInfo(C.Structure):
+    """hipfact_cond_info (include/hipfact.h)"""
+    _fields_ = [("norm1", C.c_double), ("inv_norm1", C.c_double), ("cond1", C.c_double), ("omega", C.c_double),
+                ("exact", C.c_int), ("iterations", C.c_int), ("blocks", C.c_int), ("column", C.c_int), ("stop", C.c_int)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+COND_STOPS = ["EXACT", "NO_GAIN", "PARALLEL", "MAX_AT_BEST", "REVISIT", "ITMAX"]
+
+
+def condest_dense(A) -> dict:
+    """hipfact_debug_condest_dense: the rule of hipfact_condition_estimate with products by the dense matrix A, on the
+    host (no GPU).  Returns the info as a dict with "history" and "witness"."""
+    A = np.asfortranarray(A, dtype=np.float64)
+    assert A.ndim == 2 and A.shape[0] == A.shape[1], A.shape
+    N = A.shape[0]
+    info = CondInfo()
+    wit = np.empty(N)
+    hist = np.empty(80, dtype=np.int32)
+    rc = _lib.load().hipfact_debug_condest_dense(N, _ptr(A), N, C.byref(info), _ptr(wit), _ptr(hist), hist.size)
+    if rc != 0:
+        raise HipfactError(rc, "hipfact_debug_condest_dense")
+    out = info.as_dict()
+    out["history"] = [int(i) for i in hist if i >= 0]
+    out["witness"] = wit
+    return out
 
 
 class TrExtra(C.Structure):
