@@ -240,6 +240,63 @@ int hipfact_solve_extra(hipfact_handle* h, const double* rhs, double* sol, hipfa
  * d_b or d_z (HIPFACT_EINVAL); HIPFACT_ESTATE before a factorisation.  Deterministic: the same bits on every call. */
 int hipfact_residual_device(hipfact_handle* h, const double* d_b, const double* d_z, double* d_res, int extended);
 
+/* ---- extra-precise blocked solve: the refinement above for 16 right-hand sides per pass ------------------------
+ * K Z = B for nrhs columns, every column refined on double-double residuals by the rule of hipfact_solve_device_extra,
+ * in blocks of 16: the contract is the union of hipfact_solve_device_multi's and hipfact_solve_device_extra's.  Per
+ * block: Z = K^-1 B; then per pass R = B - K Z as pairs for all open columns in ONE walk over K (every index, value and
+ * map entry of K is read once per walk, not once per column), dZ = K^-1 R, the norms of every column, ONE host
+ * synchronisation, the rule per column, z_j += dz_j for the columns whose rule said so.  Every K^-1 is one plain
+ * blocked pass (both sweeps over the factor panels and the back end, no fp64 residual, whatever refine_steps is; the
+ * row slices of "multi_slice_rows" apply as in hipfact_solve_device_multi).
+ * Layout and overlap as hipfact_solve_device_multi: column j at ptr + j ld, ld >= N, the doubles between N and ld are
+ * never written; d_sol == d_rhs only with equal ld (the call works on a copy of B), any other overlap is
+ * HIPFACT_EINVAL, as are nrhs < 0, ld < N and NULL arrays; nrhs == 0 returns HIPFACT_OK; HIPFACT_ESTATE before a
+ * factorisation.  The call BLOCKS; on entry it does what hipfact_check does; it does not become "the last solve":
+ * hipfact_solution* still return the earlier single solve, and a single solve issued afterwards gives the bits it
+ * would have given without this call.
+ * Column j runs the rule above UNCHANGED on its own norms (per block [0, n) / [n, N) in saddle mode, one block in
+ * generic mode; at most refine_max passes); info[j] is its hipfact_extra_info.  A column whose rule has ended is
+ * frozen: it is left out of every later residual, sweep (swept as zeros), norm and update; a block ends when all its
+ * columns have ended.  The bits of a column's solution and of info[j] depend on that column, K and the options only -
+ * not on its position, on nrhs or on what the other columns hold.  They are NOT those of hipfact_solve_device_extra
+ * on the same column: the blocked sweeps sum in another order.
+ * Return code: one more double-double residual of every returned column is judged as the blocked solve judges a
+ * column's first residual; info[j].omega is that backward error.  A column above fail_omega, or outside the range of a
+ * statically pivoted rank-deficient K, makes the call return HIPFACT_ESINGULAR and info "multi_failed_col" names the
+ * first such column (-1: none); unlike hipfact_solve_device_multi, d_sol and info are then still written for every
+ * column, as the single extra-precise solve does.  A column with a NaN or an Inf comes back non-finite with status
+ * NONFINITE and is HIPFACT_OK on its own account; its neighbours are solved as if it were not there.
+ * A plan with the low-rank dense-column correction (dense_mode = 2 and dense columns present) runs its columns one
+ * by one through hipfact_solve_device_extra's path inside this call: each gets the bits of that call; info
+ * "multi_single_cols" counts them, "extra_solves" / "extra_passes" do not.
+ * The workspace is allocated by the first call of a plan; when that fails the call returns
+ * HIPFACT_ENOMEM and the handle stays usable.
+ * Info: "extra_multi_solves" calls that ran, "extra_multi_cols" their columns, "extra_multi_passes" corrections
+ * applied, summed over the columns; "multi_blocks" and "multi_passes" count the blocks and the passes over the factor
+ * as for hipfact_solve_device_multi (a block: 1 + the passes of its longest-running column).
+ * From which nrhs the call pays (measured on the MI355X, EXPERIMENTS.md, "Blocked extra-precise solve"): a block costs
+ * the same whatever it holds, so use full blocks.  Against back-to-back hipfact_solve_device_extra calls on the same
+ * columns one full block costs 0.47 x their time per column on the headline workload (banded, 150 000 unknowns: 218
+ * against 467 us, 2 corrections per column either way; 0.45 x at nrhs = 64) and 0.36 x on the dense-chain workload
+ * (15 000 unknowns: 470 against 1287 us).  With 467 / (16 x 218) = 0.13 of a block per single call, the break-even is
+ * nrhs = 8 on the headline workload and nrhs = 6 on the dense chain, if the columns need about the same number of passes. */
+int hipfact_solve_device_multi_extra(hipfact_handle* h, int nrhs, const double* d_rhs, long long ld_rhs, double* d_sol,
+                                     long long ld_sol, hipfact_extra_info* info /* nrhs entries, nullable */);
+/* The same for host arrays, both N x nrhs column-major with leading dimension N (sol may be rhs); staged through a
+ * device buffer of the handle.  With HIPFACT_ESINGULAR sol is still written. */
+int hipfact_solve_multi_extra(hipfact_handle* h, int nrhs, const double* rhs, double* sol,
+                              hipfact_extra_info* info /* nullable */);
+
+/* d_res_j = d_b_j - K d_z_j for nrhs columns (column j at ptr + j ld, ld >= N, the doubles between N and ld are never
+ * written), queued on the handle's stream without synchronisation like hipfact_residual_device.  extended != 0: the
+ * double-double residual of up to 16 columns per walk over K, every column bit for bit what
+ * hipfact_residual_device(extended = 1) gives for it (the values 4, 8 and 16 ask for that many columns per walk - a
+ * measurement aid; any other non-zero value leaves the number to the library).  extended = 0: the fp64 residual kernel
+ * column by column.  d_res must not overlap d_b or d_z (HIPFACT_EINVAL, as for nrhs < 0, ld < N and NULL arrays);
+ * nrhs == 0 returns HIPFACT_OK; HIPFACT_ESTATE before a factorisation.  Deterministic: the same bits on every call. */
+int hipfact_residual_device_multi(hipfact_handle* h, int nrhs, const double* d_b, long long ld_b, const double* d_z,
+                                  long long ld_z, double* d_res, long long ld_res, int extended);
+
 /* ---- condition estimate: ||K||_1 ||K^-1||_1 from a handful of blocked solves -----------------------------------
  * hipfact_condition returns the ratio of the pivots of the block-diagonal factor: a proxy for the conditioning of the
  * reduced matrix S^, not of K.  This call estimates the 1-norm condition number of K itself (LAPACK's xSYCON / xLACN2,
@@ -677,6 +734,16 @@ int hipfact_debug_multi_slices(int u, int slice_rows, int* tile_bounds /* cap + 
  * hipfact_extra_info.  Every output pointer may be NULL. */
 int hipfact_debug_extra_rule(int nblocks, int npasses, const double* dn, const double* zn, int pass_cap, int* applied,
                              int* status, double* ferr, double* rho);
+/* The column bookkeeping of a block of hipfact_solve_device_multi_extra as a pure host function (no GPU needed; used by
+ * the tests): the rule above per column, on recorded norms.  dn / zn hold npasses x ncols x nblocks values, pass by
+ * pass and column by column (1 <= ncols <= 16, nblocks 1 or 2, pass_cap >= 1, else HIPFACT_EINVAL); the values of a
+ * column that is not open in a pass are not read.  Returns the number of passes the block runs (it ends with the last
+ * of its columns, or with the sequence); open_mask[k], k < npasses: bit j set when column j takes part in pass k (0
+ * behind the block's end); info[j]: passes, status (-1 when the sequence ended before the column's rule did), ferr,
+ * dz_rel and rho of column j as hipfact_debug_extra_rule gives them for that column alone (omega: NaN).  open_mask and
+ * info may be NULL. */
+int hipfact_debug_multi_extra_schedule(int ncols, int nblocks, int npasses, const double* dn, const double* zn,
+                                       int pass_cap, unsigned int* open_mask, hipfact_extra_info* info);
 /* The rule of hipfact_condition_estimate (sleqp_amd/csrc/condest_rule.h) with products by a dense N x N matrix A
  * (column-major, ld >= N), no GPU needed; used by the tests.  The column 1-norms are summed in row order; norm1, cond1
  * and omega are left NaN, because this entry point gets no K.  history: the indices the rule used, in order, -1 behind

@@ -29,7 +29,9 @@ SYMBOLS = [
     "hipfact_solve_dense", "hipfact_solution", "hipfact_solution_view", "hipfact_condition", "hipfact_refactor_device",
     "hipfact_solve_device", "hipfact_solve_device_multi", "hipfact_solve_multi",
     "hipfact_condition_estimate", "hipfact_debug_condest_dense", "hipfact_debug_condest_recorded",
-    "hipfact_solve_device_extra", "hipfact_solve_extra", "hipfact_residual_device", "hipfact_debug_extra_rule", "hipfact_debug_dd_residual", "hipfact_solution_device", "hipfact_synchronize", "hipfact_check", "hipfact_stream",
+    "hipfact_solve_device_extra", "hipfact_solve_extra", "hipfact_residual_device", "hipfact_debug_extra_rule", "hipfact_debug_dd_residual",
+    "hipfact_solve_device_multi_extra", "hipfact_solve_multi_extra", "hipfact_residual_device_multi", "hipfact_debug_multi_extra_schedule",
+    "hipfact_solution_device", "hipfact_synchronize", "hipfact_check", "hipfact_stream",
     "hipfact_assemble_kkt", "hipfact_reduced_matrix", "hipfact_spmat_create", "hipfact_spmat_update_values", "hipfact_spmat_free",
     "hipfact_spmat_mult_vec", "hipfact_spmat_mult_vec_trans", "hipfact_spmat_mult_vec_sym",
     "hipfact_spmat_mult_device", "hipfact_steihaug_solve", "hipfact_tr_solve", "hipfact_tr_solve_ex", "hipfact_lsqr_solve", "hipfact_tridiag_tr", "hipfact_set_option", "hipfact_get_info", "hipfact_debug_copy", "hipfact_debug_pool_selftest",
@@ -81,6 +83,12 @@ def load() -> C.CDLL:
         lib.hipfact_debug_extra_rule.argtypes = [ci, ci, vp, vp, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(cd), C.POINTER(cd)]
         lib.hipfact_debug_dd_residual.argtypes = [ci, vp, vp, cd, ci]
         lib.hipfact_debug_dd_residual.restype = cd
+    if hasattr(lib, "hipfact_solve_device_multi_extra"):
+        ll = C.c_longlong
+        lib.hipfact_solve_device_multi_extra.argtypes = [vp, ci, vp, ll, vp, ll, vp]
+        lib.hipfact_solve_multi_extra.argtypes = [vp, ci, vp, vp, vp]
+        lib.hipfact_residual_device_multi.argtypes = [vp, ci, vp, ll, vp, ll, vp, ll, ci]
+        lib.hipfact_debug_multi_extra_schedule.argtypes = [ci, ci, ci, vp, vp, ci, vp, vp]
     if hasattr(lib, "hipfact_condition_estimate"):
         lib.hipfact_condition_estimate.argtypes = [vp, ci, vp, vp]
         lib.hipfact_debug_condest_dense.argtypes = [ci, vp, C.c_longlong, vp, vp, vp, ci]

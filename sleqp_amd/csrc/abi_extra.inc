@@ -77,21 +77,10 @@ int hipfact_residual_device(hipfact_handle* h, const double* d_b, const double* 
     return HIPFACT_EINVAL;
   }
   Turn turn(h);
-  if (extended) {
+  if (extended)
     residual_dd_async(h, d_b, d_z, d_res, nullptr);
-  } else {
-    const Plan& P = h->plan;
-    if (P.saddle) {
-      LAUNCH(PC_RESID, k_residual_saddle, dim3(resid_blocks(P)), dim3(FB), 0, P.n, P.m, h->d_Kp.as<int>(),
-             h->d_Ki.as<int>(), h->d_Kval.as<double>(), h->d_Ar_ptr.as<int>(), h->d_Ar_col.as<int>(),
-             (masked_rows(h) ? h->d_Ar_full : h->d_Ar_val).as<double>(), h->d_perm.as<int>(), saddle_maps(h), d_b, d_z,
-             d_res, (const RefineCtl*)nullptr, (double*)nullptr, 1, (int*)nullptr);
-    } else {
-      LAUNCH(PC_RESID, k_residual_sym, dim3(resid_blocks(P)), dim3(FB), 0, P.N, h->d_Kp.as<int>(), h->d_Ki.as<int>(),
-             h->d_Kval.as<double>(), h->d_Tp.as<int>(), h->d_Ti.as<int>(), h->d_Tsrc.as<int>(), d_b, d_z, d_res,
-             (const RefineCtl*)nullptr, (double*)nullptr, 1, (int*)nullptr);
-    }
-  }
+  else
+    residual_fp64_async(h, d_b, d_z, d_res);
   HCHECK(h, hipGetLastError());
   return HIPFACT_OK;
 }

@@ -491,6 +491,7 @@ int hipfact_get_info(const hipfact_handle* h, const char* name, double* value) {
   INFO("multi_sliced_fronts", h->mitems_for < 0 ? 0 : h->n_mcut) INFO("multi_slice_items", h->mitems_for < 0 ? 0 : h->n_mslices) INFO("multi_slice_rows", h->multi_slice_rows)
   INFO("cond_estimates", h->cond_estimates) INFO("cond_blocks", h->cond_blocks) INFO("cond_last", h->cond_last) INFO("condition_estimate", h->condition_estimate)
   INFO("extra_solves", h->extra_solves) INFO("extra_passes", h->extra_passes) INFO("extra_last_status", h->extra_last_status)
+  INFO("extra_multi_solves", h->extra_multi_solves) INFO("extra_multi_cols", h->extra_multi_cols) INFO("extra_multi_passes", h->extra_multi_passes)
   INFO("num_solve", h->num_solve) INFO("num_refined", h->solve_cad.num_refined) INFO("refine_adaptive", h->refine_adaptive)
   INFO("num_passes", h->solve_cad.num_passes) INFO("last_omega", h->last_ctl.omega) INFO("last_iters", h->last_ctl.iters)
   INFO("last_status", h->last_ctl.status) INFO("last_tol", h->last_ctl.tol) INFO("kappa_est", h->last_ctl.kappa)

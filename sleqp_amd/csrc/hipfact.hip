@@ -14,6 +14,7 @@
 //   dense_cols.inc      dense Jacobian columns                   krylov_device.inc    device-controlled CG
 //   runtime_multi.inc   blocked solve, 16 right-hand sides       abi_multi.inc        hipfact_solve[_device]_multi
 //   runtime_extra.inc   extra-precise solve (dd_arith.h)         abi_extra.inc        hipfact_solve[_device]_extra, _residual_device
+//   runtime_multi_extra.inc blocked extra-precise solve         abi_multi_extra.inc  hipfact_solve[_device]_multi_extra, _residual_device_multi
 //   runtime_condest.inc 1-norm condition estimate (condest_rule.h) abi_condest.inc      hipfact_condition_estimate, _debug_condest_*
 //   refine_cadence.h    refinement cadence of the single solve: passes in the graph, residual checks, deferred verdicts
 //                       (pure host rules, like xcd_place.h and multi_slices.h)
@@ -57,12 +58,14 @@
 #include "runtime_queue.inc"
 #include "runtime_multi.inc"
 #include "runtime_extra.inc"
+#include "runtime_multi_extra.inc"
 #include "runtime_condest.inc"
 
 extern "C" {
 #include "abi_core.inc"
 #include "abi_multi.inc"
 #include "abi_extra.inc"
+#include "abi_multi_extra.inc"
 #include "abi_condest.inc"
 #include "abi_working_set.inc"
 #include "abi_krylov.inc"

@@ -70,6 +70,16 @@ struct MultiIn {
   long long ldy;
   double* __restrict__ U;             // update blocks, MR doubles per update row
 };
+// The columns of a blocked double-double residual / norm launch (kernels_saddle_dd_multi.inc): column slot q of B, Z and
+// R at b + q ldb, z + q ldz, res + q ldr; the launch works on the nc slots col[0 .. nc).
+struct DdCols {
+  const double* b;
+  const double* z;
+  double* res;
+  long long ldb, ldz, ldr;
+  int nc;
+  int col[MR];
+};
 // (working-set maps and equilibration of the saddle-point front end: described with the saddle kernels below)
 struct SaddleMaps {
   const int* __restrict__ vmap;

@@ -77,6 +77,21 @@ static void residual_dd_async(hipfact_handle* h, const double* b, const double* 
   }
 }
 
+// res = b - K z in fp64, as every checked solve takes it, without a control block or block maxima
+static void residual_fp64_async(hipfact_handle* h, const double* b, const double* z, double* res) {
+  const Plan& P = h->plan;
+  if (P.saddle) {
+    LAUNCH(PC_RESID, k_residual_saddle, dim3(resid_blocks(P)), dim3(FB), 0, P.n, P.m, h->d_Kp.as<int>(),
+           h->d_Ki.as<int>(), h->d_Kval.as<double>(), h->d_Ar_ptr.as<int>(), h->d_Ar_col.as<int>(),
+           (masked_rows(h) ? h->d_Ar_full : h->d_Ar_val).as<double>(), h->d_perm.as<int>(), saddle_maps(h), b, z, res,
+           (const RefineCtl*)nullptr, (double*)nullptr, 1, (int*)nullptr);
+  } else {
+    LAUNCH(PC_RESID, k_residual_sym, dim3(resid_blocks(P)), dim3(FB), 0, P.N, h->d_Kp.as<int>(), h->d_Ki.as<int>(),
+           h->d_Kval.as<double>(), h->d_Tp.as<int>(), h->d_Ti.as<int>(), h->d_Tsrc.as<int>(), b, z, res,
+           (const RefineCtl*)nullptr, (double*)nullptr, 1, (int*)nullptr);
+  }
+}
+
 static const int g_maxabs_cap = 256;  // workgroups (= partial maxima) of k_block_maxabs
 
 // workspace: the vectors with the plan state, the small blocks with the handle; the handle stays usable when it fails

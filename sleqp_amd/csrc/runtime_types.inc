@@ -253,6 +253,9 @@ struct PlanState : FactorMemo {
   // extra-precise solve (runtime_extra.inc): its four vectors b | z | r | dz, N_ext doubles each; they live with the
   // plan because its solve graphs hold their addresses.  Allocated by the first such call of the state.
   DevBuf d_xvec;
+  // blocked extra-precise solve (runtime_multi_extra.inc): the blocks Z | dZ, MR columns of N_ext doubles each (B and
+  // R are the blocked solve's d_mB and d_mR).  Allocated by the first such call of the state.
+  DevBuf d_xmvec;
   // condition estimate (runtime_condest.inc), N_ext each: two N x 16 blocks, the witness, h, a = |K| v and the diagonal
   // of D as doubles (d_cblk); two generations of sign words (d_cwords); the `used` bytes (d_cused).  They live with the
   // plan because the single-solve route of a dense_mode = 2 plan captures graphs on the blocks' columns.
@@ -478,6 +481,13 @@ struct hipfact_handle : PlanState, SingleSolveMemo {
   void* h_xout_dev = nullptr;
   long extra_solves = 0, extra_passes = 0;
   int extra_last_status = 0;
+  // blocked extra-precise solve (runtime_multi_extra.inc): the partial maxima of its norm kernel (4 per workgroup and
+  // column), the pinned 4 x MR norms the host reads once per pass, the staging of the host entry point; counters of
+  // hipfact_get_info
+  DevBuf d_xmpart, d_xmhost;
+  PinBuf h_xmout;
+  void* h_xmout_dev = nullptr;
+  long extra_multi_solves = 0, extra_multi_cols = 0, extra_multi_passes = 0;
   // condition estimate (runtime_condest.inc): the partials of its reductions and the history list, the pinned block
   // the host reads (norms, parallel flags, the selection); the option "condition_estimate" (what hipfact_condition
   // returns: 0 the pivot ratio, 1 / 2 cond1 of K / of the equilibrated K^); counters of hipfact_get_info

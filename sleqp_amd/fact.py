@@ -142,6 +142,40 @@ class HipFact:
             self._check(rc)
         return sol, info.as_dict(rc)
 
+    def solve_device_multi_extra(self, d_rhs_ptr: int, ld_rhs: int, d_sol_ptr: int, ld_sol: int, nrhs: int,
+                                 raise_singular: bool = True) -> list:
+        """hipfact_solve_device_multi_extra: K Z = B for nrhs device columns (column j at ptr + 8 j ld), every column
+        refined on double-double residuals, 16 columns per pass; blocks.  Returns the hipfact_extra_info of every
+        column as a dict (solve_device_extra), each with the call's return code under "rc"."""
+        infos = (ExtraInfo * max(int(nrhs), 1))()
+        rc = self._lib.hipfact_solve_device_multi_extra(self._h, int(nrhs), C.c_void_p(d_rhs_ptr), int(ld_rhs),
+                                                        C.c_void_p(d_sol_ptr), int(ld_sol), infos)
+        if rc != 0 and not (rc == -3 and not raise_singular):
+            self._check(rc)
+        return [infos[j].as_dict(rc) for j in range(max(int(nrhs), 0))]
+
+    def solve_multi_extra(self, B, raise_singular: bool = True):
+        """hipfact_solve_multi_extra: (Z, infos) with K Z = B for a host N x k array in either memory order, every
+        column accurate to the last bits while the factor contracts; infos as in solve_device_multi_extra."""
+        B = np.asarray(B, dtype=np.float64)
+        assert B.ndim == 2 and B.shape[0] == self.N, B.shape
+        rhs = np.asfortranarray(B)
+        sol = np.empty_like(rhs, order="F")
+        k = rhs.shape[1]
+        infos = (ExtraInfo * max(k, 1))()
+        rc = self._lib.hipfact_solve_multi_extra(self._h, k, _ptr(rhs), _ptr(sol), infos)
+        if rc != 0 and not (rc == -3 and not raise_singular):
+            self._check(rc)
+        return sol, [infos[j].as_dict(rc) for j in range(k)]
+
+    def residual_device_multi(self, d_b_ptr: int, ld_b: int, d_z_ptr: int, ld_z: int, d_res_ptr: int, ld_res: int,
+                              nrhs: int, extended=True):
+        """hipfact_residual_device_multi: res_j = b_j - K z_j for nrhs device columns on the handle's stream
+        (extended: double-double accumulation, up to 16 columns per walk over K; 4, 8 or 16: that many per walk)."""
+        self._check(self._lib.hipfact_residual_device_multi(self._h, int(nrhs), C.c_void_p(d_b_ptr), int(ld_b),
+                                                            C.c_void_p(d_z_ptr), int(ld_z), C.c_void_p(d_res_ptr),
+                                                            int(ld_res), int(extended)))
+
     def condition_estimate(self, equilibrated: bool = False, want_witness: bool = False) -> dict:
         """hipfact_condition_estimate: the 1-norm condition number of K (equilibrated: of K^ = D K D) from blocked
         solves; blocks.  Returns the hipfact_cond_info as a dict (norm1, inv_norm1, cond1, omega, exact, iterations,
