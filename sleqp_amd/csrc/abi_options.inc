@@ -204,6 +204,7 @@ static const OptionRow kOptions[] = {
     {nullptr, "HIPFACT_DATAFLOW_RETRY", FX_NONE, OPT_STORE(df_retry_every, std::max(0, (int)v)), nullptr},
     {nullptr, "HIPFACT_CHECK_LAUNCHES", FX_NONE, OPT_STORE(check_launches, v != 0.0), nullptr},
     {nullptr, "HIPFACT_SOL_SPLIT", FX_NONE, OPT_STORE(sol_split, v != 0.0), nullptr},
+    {nullptr, "HIPFACT_IDX64", FX_NONE, OPT_STORE(idx64, v != 0.0), nullptr},
     {nullptr, "HIPFACT_XCD_CLASSES", FX_NONE, OPT_STORE(xcd_classes, std::max(1, std::min(XCD_CLASSES_MAX, (int)v))), nullptr},
 };
 #undef OPT_STORE
@@ -513,6 +514,7 @@ int hipfact_get_info(const hipfact_handle* h, const char* name, double* value) {
   INFO("long_row_segments", h->n_rseg) INFO("row_scale_blocks", row_scale_in_sequence(h) ? h->rs_grid : 0)
   INFO("arena_fill_bytes", arena_fill_bytes(P))
   INFO("xcd_classes", h->xcd_classes) INFO("dealt_multi_item_fronts", h->dealt_multi) INFO("long_prod_segments", h->n_lprod)
+  INFO("long_col_segments", h->n_cseg) INFO("idx32", h->idx32) INFO("prod_packed", h->prod_packed)
   INFO("active_bounds", h->maps_on ? h->n_bounds : 0)
   // (hipfact_refactor_device takes the caller's values as the structure's own, entry by entry)
   INFO("values_in_place",

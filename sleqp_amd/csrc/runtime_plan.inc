@@ -201,7 +201,7 @@ static int upload_plan(hipfact_handle* h) {
   if ((rc = upload(h, h->d_rows, P.sn_rows))) return rc;
   if ((rc = upload(h, h->d_rel, P.rel))) return rc;
   if ((rc = upload(h, h->d_child, P.child_idx))) return rc;
-  h->idx32 = P.saddle && P.L_size < (1LL << 32) && P.nprod < (1LL << 32);
+  h->idx32 = P.saddle && !h->idx64 && P.L_size < (1LL << 32) && P.nprod < (1LL << 32);
   if (h->idx32) {
     std::vector<unsigned int> t32(P.Mtarget.begin(), P.Mtarget.end());
     if ((rc = upload(h, h->d_Mtarget, t32))) return rc;

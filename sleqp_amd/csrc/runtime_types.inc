@@ -422,6 +422,7 @@ struct hipfact_handle : PlanState, SingleSolveMemo {
   hipEvent_t ev_rhs[2] = {nullptr, nullptr}, ev_sol = nullptr, ev_sol_x = nullptr;  // ev_sol_x: entries [0, sol_nx) have arrived
   int sol_nx = 0;
   bool sol_split = true;         // the x part of the solution is downloaded first, with an event of its own
+  bool idx64 = false;            // HIPFACT_IDX64: upload_plan keeps 64-bit product-list pointers and panel targets (tests)
   bool ev_rhs_used[2] = {false, false};
   int rhs_slot = 0;
   bool boundary_fast = true;     // option: off = the round-3 path (pageable borrows, three blocking points)

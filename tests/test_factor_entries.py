@@ -9,8 +9,10 @@ import ctypes as C
 
 import numpy as np
 import pytest
+import scipy.sparse as sp
 
 import factor_check as fc
+import front_end_cases as fe
 from plan_emul import EmulFactor, Plan
 from sleqp_amd import synth
 
@@ -59,7 +61,12 @@ class Case:
 
     def __init__(self, lib, name, monkeypatch):
         self.name = name
-        if name == "saddle_bounds":
+        self.dyadic = name in fe.NAMES
+        if self.dyadic:
+            self.fe = fe.case(name)
+            self.env = self.fe.env
+            self.K = self.fe.K
+        elif name == "saddle_bounds":
             self.env = {}
             self.K = fc.saddle_case()
         elif name == "saddle_late_columns":
@@ -73,6 +80,10 @@ class Case:
             self.P = Plan(lib, *self.K)
         N, cp, ri, vx = self.K
         self.b = np.random.default_rng(11).standard_normal(N)
+        if self.dyadic:  # (N up to 8900: no dense K; the reference factor comes from saddle_ref as for the other saddle cases)
+            self.ref = None
+            self.kappa, self.z = self._reduced_reference() if self.fe.dense_reference else (None, None)
+            return
         Kd = fc.generic_m(N, cp, ri, vx, np.arange(N))
         self.kappa = float(np.linalg.cond(Kd))
         if not self.P.saddle:
@@ -87,6 +98,41 @@ class Case:
             self.ref = None
             Lk, dk = fc.reference_factor(Kd)  # K itself, natural order: quasi-definite ([I A^T; A 0])
             self.z = fc.ld_solve(Lk, dk, self.b)
+
+    def _reduced_reference(self):
+        """(cond_2(K), the solution of K z = b in long double) of a dyadic case without a dense K.  K = [I A^T; A 0]
+        has the eigenvalues 1 (n - rank times) and (1 +- sqrt(1 + 4 sigma^2)) / 2 over the singular values sigma of A,
+        unit rows included.  The solution in reduced form, with x_B = beta on the active bounds: S y = A_f b_f -
+        (b_y - A_B beta) over the free columns, S = A_f A_f^T exact in fp64 (the 53-bit precondition) and factored in
+        long double (m <= 320), x_f = b_f - A_f^T y, and the multiplier of a bound b_j - beta - (A^T y)_j."""
+        LD = np.longdouble
+        N, cp, ri, vx = self.K
+        n, A, keep, unit = fc.saddle_parts(N, cp, ri, vx)
+        sig = np.linalg.svd(A.toarray(), compute_uv=False)
+        assert len(sig) == N - n <= n and sig.min() > 0
+        lam = np.concatenate([(1 + np.sqrt(1 + 4 * sig ** 2)) / 2, (np.sqrt(1 + 4 * sig ** 2) - 1) / 2,
+                              [1.0] if n > len(sig) else []])
+        kappa = float(lam.max() / lam.min())
+        fe.assert_exact_precondition(self.fe)
+        Ak = sp.csr_matrix(A[keep])
+        assert Ak.shape[0] <= 320
+        fixcol = np.asarray(A[unit].indices, dtype=np.int64)
+        free = np.ones(n, dtype=bool)
+        free[fixcol] = False
+        b = self.b.astype(LD)
+        beta = b[n + unit]
+        Af = sp.csr_matrix(Ak[:, np.flatnonzero(free)])
+        Sm = (Af @ Af.T).toarray()
+        Afd = Af.toarray().astype(LD)
+        t = Afd @ b[:n][free] - (b[n + keep] - Ak[:, fixcol].toarray().astype(LD) @ beta)
+        Lu, d = fc.reference_factor(Sm)
+        y = fc.ld_solve(Lu, d, t)
+        z = np.empty(N, dtype=LD)
+        z[np.flatnonzero(free)] = b[:n][free] - Afd.T @ y
+        z[fixcol] = beta
+        z[n + keep] = y
+        z[n + unit] = b[fixcol] - beta - Ak[:, fixcol].toarray().astype(LD).T @ y
+        return kappa, z
 
     def saddle_ref(self, dscale, S, my):
         """M from K on the handle's own structure and row scales: the scales of the constraint rows are the host's
@@ -105,6 +151,8 @@ class Case:
         f, _ = np.frexp(s)
         clear = (f > 0.5 + 8 * U) & (f < 1.0 - 8 * U)  # (2 ulp of the sum of squares cannot move these)
         assert np.array_equal(dscale[yk][clear], d_host[clear])
+        if self.dyadic:  # the sums of squares are exact: the rule decides every row, no doubtful band
+            assert np.array_equal(dscale[yk], d_host), np.flatnonzero(dscale[yk] != d_host)
         assert np.all(dscale == np.exp2(np.round(np.log2(dscale))))  # powers of two
         M = M * dscale[:, None] * dscale[None, :]
         Lu, d = fc.reference_factor(M)
@@ -125,6 +173,18 @@ def case(request, hipfact_lib, monkeypatch):
     return c
 
 
+def _assert_front_end_branches(f, c):
+    """The handle's structure keeps the rows and columns of J whole (active bounds are marked, not cut): the long-row
+    and long-column segments of the case, its bounds, and 32-bit indices."""
+    rows, cols = np.diff(sp.csr_matrix(c.J).indptr), np.diff(c.J.indptr)
+    want = {"long_row_segments": sum(-(-int(x) // fe.LONG_SEG) for x in rows if x > fe.LONG_ROW),
+            "long_col_segments": sum(-(-int(x) // fe.LONG_SEG) for x in cols if x > fe.LONG_COL),
+            "active_bounds": c.n_bounds, "idx32": 1}
+    got = {k: int(f.info(k)) for k in want}
+    assert got == want, (c.name, got, want)
+    assert want["long_row_segments"] > 0 or want["long_col_segments"] > 0
+
+
 def _solve_err(f, c):
     f.solve(c.b)
     z = f.solution_raw(0, len(c.b))
@@ -132,9 +192,13 @@ def _solve_err(f, c):
 
 
 CRAFTED = ["arrow_spd", "arrow_quasidef", "arrow_wide_update", "saddle_bounds", "saddle_late_columns"]
+# the dyadic saddle systems at the size edges of the front end (front_end_cases.py): their sums of squares, S and
+# M = D S D are exact, so the row scales must be the host rule's on every row and what compare_fronts shows is the
+# factorisation alone.  Measured on MI355X: see EXPERIMENTS.md, "the front end at its size edges".
+FRONT_END = ["rows", "rows_bounds", "cols", "cols_bounds", "rows_late"]
 
 
-@pytest.mark.parametrize("case", CRAFTED, indirect=True)
+@pytest.mark.parametrize("case", CRAFTED + FRONT_END, indirect=True)
 def test_crafted_factor_on_every_route(case):
     """Every route's factor against the long-double reference, front by front; the route is shown to have run by its
     counters; refinement-free solves (one handle also with top_block_after 1) within 64 kappa u.  Measured on MI355X
@@ -143,7 +207,11 @@ def test_crafted_factor_on_every_route(case):
     The generic cases run on the handle's own plan, proven identical to the host plan.  The saddle cases (active
     bounds; four dense columns eliminated late, M = [S_s A_d; A_d^T -I]) go through the row dictionary, whose plan of
     the reduced rows is not the host analysis (one front more): their factor is laid out on the structure the handle
-    reports (`device_plan_arrays`), and the reference L is shown to vanish outside it."""
+    reports (`device_plan_arrays`), and the reference L is shown to vanish outside it.
+
+    The cases of FRONT_END (dyadic, N up to 8900) take cond(K) from the singular values of A and their long-double
+    solution from the reduced system (`Case._reduced_reference`); their row scales must be the host rule's on every
+    row.  Measured on MI355X: worst 2.2e-15 / 1.5e-15 / 1.6e-15, solves 0.49 kappa u (`cols`)."""
     c = case
     report = {}
     for route, opts in list(ROUTES.items()) + [("top_block_after_1", {"top_block_after": 1})]:
@@ -158,6 +226,8 @@ def test_crafted_factor_on_every_route(case):
             L, dscale = fc.device_factor(f)
             if c.P.saddle:
                 assert f.info("late_columns") == c.P.n_late and f.info("m_rows") == c.P.my
+                if c.dyadic:
+                    _assert_front_end_branches(f, c.fe)
                 if c.ref is None:
                     c.saddle_ref(dscale, S, c.P.my)
             worst = fc.compare_fronts(L, c.ref, S, TOL)
@@ -172,6 +242,20 @@ def test_crafted_factor_on_every_route(case):
             f.free()
     # the routes ran: the dataflow launch for the top levels by default, never without it or without pulls
     d = report["defaults"]
+    if c.dyadic and int((S.sn_r.astype(np.int64) ** 2 * np.diff(S.sn_c0)).max()) < 200000:
+        # small fronts only (`rows`: M has 48 rows): no front reaches the work r^2 w = 2e5 from which a level is split
+        # into pivot, panel and Schur launches.  The levels below factor_top_level are one k_factor_level launch each,
+        # the others one dataflow launch - none without it or without pulls.  What these cases are for lies in front
+        # of the factor: the row scales, compared on every row above, and M = D S D
+        for route, r in report.items():
+            below = min(r["factor_top_level"], r["nlevels"])
+            assert r["prof_factor_count"] == below and r["prof_factorT_count"] == (below < r["nlevels"]), route
+            assert r["prof_factorB_count"] == r["prof_factorC_count"] == r["prof_factorD_count"] == 0, route
+        for route in ("factor_top_max_0", "pull_max_children_0"):
+            assert report[route]["factor_top_level"] >= report[route]["nlevels"], route
+        if c.name == "rows_late":
+            assert c.P.n_late > 0 and d["factor_top_level"] < d["nlevels"]
+        return
     assert d["prof_factorT_count"] >= 1 and d["factor_top_level"] < d["nlevels"]
     for route in ("factor_top_max_0", "pull_max_children_0"):
         r = report[route]
@@ -183,7 +267,7 @@ def test_crafted_factor_on_every_route(case):
     assert report["chain_fuse_0"]["chain_levels_fused"] == 0 and report["chain_pairs_0"]["chain_pairs"] == 0
     if c.name == "arrow_wide_update":  # its border is a chain: one level of it runs as a fused mini launch by default
         assert d["chain_levels_fused"] >= 1
-    if c.name == "saddle_late_columns":
+    if c.name in ("saddle_late_columns", "rows_late"):
         assert c.P.n_late > 0
 
 
@@ -343,5 +427,42 @@ def test_saddle_factor_is_invariant_under_power_of_two_scaling_of_the_jacobian()
             L, d = fc.device_factor(f)
             assert np.array_equal(L, L0), k
             assert np.array_equal(d, d0 * 2.0 ** -k), k
+        # `rows` of front_end_cases.py: the second pass of k_row_scale, the long-row segments and their norms
+        c = fe.case("rows")
+        _set(f, *c.K)
+        assert f.info("long_row_segments") > 0
+        L0, d0 = fc.device_factor(f)
+        for k in (-100, -25, 25, 100):
+            _set(f, *synth.kkt_lower_from_jacobian(c.J * 2.0 ** k))
+            L, d = fc.device_factor(f)
+            assert np.array_equal(L, L0), k
+            assert np.array_equal(d, d0 * 2.0 ** -k), k
+    finally:
+        f.free()
+
+
+@pytest.mark.parametrize("case", FRONT_END, indirect=True)
+def test_front_end_factor_is_bitwise_repeatable_with_other_values_in_between(case):
+    """Three factorisations of the same values with other values in between give the same factor and row scales bit
+    for bit: the segment counters of k_long_row_norm and k_mvals_prod are handed back at zero, no partial sum of an
+    earlier factorisation is read."""
+    c = case
+    N, cp, ri, vx = c.K
+    n = c.fe.n
+    vx2 = vx * (1.0 + 0.25 * np.random.default_rng(2).random(vx.size))
+    vx2[cp[:n]] = 1.0  # (the unit diagonal stays, and so do the unit rows of the bounds: same saddle structure)
+    vx2[vx == 1.0] = 1.0
+    f = _hipfact({})
+    try:
+        _set(f, N, cp, ri, vx)
+        _assert_front_end_branches(f, c.fe)
+        L1, d1 = fc.device_factor(f)
+        for _ in range(2):
+            _set(f, N, cp, ri, vx2)
+            L_other, d_other = fc.device_factor(f)
+            assert not np.array_equal(L_other, L1)
+            _set(f, N, cp, ri, vx)
+            L, d = fc.device_factor(f)
+            assert np.array_equal(L, L1) and np.array_equal(d, d1)
     finally:
         f.free()

@@ -2,7 +2,9 @@
 off, every solve route's y and full solution against long-double sweeps on the device's OWN factor, each entry within
 the running error bound of its own sums (a graded right-hand side and unit vectors: small entries must be right too;
 the zero vector gives exactly zero).  Route against route, residuals and refined solves cannot see an error the routes
-share or one that is small against the norm; these tests look at the sweeps themselves.
+share or one that is small against the norm; these tests look at the sweeps themselves.  The cases of
+front_end_cases.py (ENDS) add the solve ends at their size edges: rows of more than 1024 entries (rhs_long_rows),
+columns of more than 256 and of more than 2048 (x_long_cols, one and two segments), with integer right-hand sides.
 
 Each test prints the worst error / bound ratio of its route (a ratio above the margin of 2 fails); EXPERIMENTS.md
 records them."""
@@ -12,8 +14,9 @@ import numpy as np
 import pytest
 
 import factor_check as fc
+import front_end_cases as fe
 import solve_check as sc
-from test_factor_entries import CRAFTED, _device_buf, _set, case  # noqa: F401  (the Case machinery and its cache)
+from test_factor_entries import CRAFTED, FRONT_END, _device_buf, _set, case  # noqa: F401  (the Case machinery and its cache)
 
 pytestmark = pytest.mark.gpu
 
@@ -21,6 +24,11 @@ pytestmark = pytest.mark.gpu
 # roots keep the plan from forming one; the saddle cases have three levels, the wide fronts are sliced)
 CASES = CRAFTED + ["arrow_one_root"]
 SPAN = 1024  # rows of a front the fused launch takes without slices (the contract of solve_slices 0)
+# the solve ends at their size edges (front_end_cases.py: rhs_long_rows from k_rhs_saddle, x_long_cols from the tree
+# launch and - xupd_fused 0, rhs_fused 0 - from k_x_saddle), with integer right-hand sides: t is then exact, the x
+# update keeps its running bound
+ENDS = FRONT_END + ["cols_many_segments"]
+ENDS_ROUTES = ["defaults", "rhs_fused_0", "xupd_fused_0", "xupd_blocks_1", "use_graph_0"]
 
 # name -> (options, cases it runs on (None: all)).  The right-hand side and the x update exist in saddle mode only: on
 # the generic arrows those three routes would launch what `defaults` does.
@@ -78,7 +86,10 @@ class Reference:
                                       mask_cols=np.setdiff1d(dcols, fixed))
         else:
             self.ends = sc.GenericEnds(self.S.perm)
-        self.B = sc.right_hand_sides(self.S, self.ends.caller_of_pivot, N)
+        if getattr(c, "dyadic", False):  # (a case of front_end_cases.py; other modules hand in cases of their own)
+            self.names, self.B = fe.RHS_NAMES, fe.right_hand_sides(c.fe, self.ends.caller_of_pivot, N)
+        else:
+            self.names, self.B = sc.RHS_NAMES, sc.right_hand_sides(self.S, self.ends.caller_of_pivot, N)
         T, eT, mT = self.ends.rhs(self.B)
         self.res = self.sw.solve(T, eT, mT)
         self.Z, self.eZ, _ = self.ends.solution(self.B, self.res)
@@ -125,6 +136,7 @@ def _check_solve(f, ref, j, what):
 
 
 PAIRS = [(c, r) for c in CASES for r, (_, only) in ROUTES.items() if only is None or c in only]
+PAIRS += [(c, r) for c in ENDS for r in ENDS_ROUTES]
 
 
 @pytest.mark.parametrize("case,route", PAIRS, indirect=["case"])
@@ -135,15 +147,16 @@ def test_sweeps_entry_by_entry_on_every_solve_route(case, route):
     alone and the later ones through the top block where the plan has one; top_block_after 1 has all of them there."""
     c = case
     opts = ROUTES[route][0]
-    assert (c.P.max_r <= SPAN) == (c.name in ROUTES["solve_slices_0"][1])  # the option's contract excludes exactly these
-    assert c.P.saddle == (c.name in SADDLE)
+    if c.name in CASES:
+        assert (c.P.max_r <= SPAN) == (c.name in ROUTES["solve_slices_0"][1])  # the option's contract excludes exactly these
+    assert c.P.saddle == (c.name in SADDLE + ENDS)
     f = _handle(opts)
     try:
         _set(f, *c.K)
         ref = _reference(c, f)
         worst_y = worst_z = 0.0
         active = []
-        for j, name in enumerate(sc.RHS_NAMES):
+        for j, name in enumerate(ref.names):
             qy, qz = _check_solve(f, ref, j, f"{route} {c.name} {name}")
             worst_y, worst_z = max(worst_y, qy), max(worst_z, qz)
             active.append(int(f.info("top_block_active")))
@@ -159,7 +172,11 @@ def test_sweeps_entry_by_entry_on_every_solve_route(case, route):
         elif c.name.startswith("arrow") and c.name != "arrow_wide_update":
             assert k["spanel_folded"] == 1  # (by default the solve panels are built inside the factorisation's launch)
         # what the last solve launched: in saddle mode the right-hand side and the x update ride in the tree launch
-        assert k["rhs_in_tree"] == (c.P.saddle and fused and route != "rhs_fused_0")
+        # (long rows are formed by whole workgroups of k_rhs_saddle on every route - rhs_long_rows -, never by the 16
+        #  lanes a forward item of the tree launch gives a row: the cases of ENDS with long rows, none of the others)
+        long_rows = f.info("long_row_segments") > 0
+        assert long_rows == (c.dyadic and len(c.fe.long_rows) > 0)
+        assert k["rhs_in_tree"] == (c.P.saddle and fused and route != "rhs_fused_0" and not long_rows)
         whole = c.P.saddle and fused and route not in ("rhs_fused_0", "xupd_fused_0")
         assert k["xupd_in_tree"] == whole
         assert (k["xupd_blocks_launched"] > 0) == whole and (k["xupd_blocks_launched"] == 1) == (route == "xupd_blocks_1")
@@ -167,6 +184,11 @@ def test_sweeps_entry_by_entry_on_every_solve_route(case, route):
         assert k["solve_resorted_levels"] == 0 or route != "solve_sorted_0"
         if c.name in ("arrow_spd", "arrow_quasidef", "arrow_one_root"):
             assert (k["solve_resorted_levels"] > 0) == (route != "solve_sorted_0")
+        if c.dyadic:  # the long rows and columns of the case are segments of this handle's solve ends
+            nr, nc = int(f.info("long_row_segments")), int(f.info("long_col_segments"))
+            assert nr + nc > 0 and (nr > 0) == (len(c.fe.long_rows) > 0) and (nc > 0) == (len(c.fe.long_cols) > 0)
+            if c.name == "cols_many_segments":
+                assert nc == 2
         if route == "dense_mode_2":  # four columns in the correction, none eliminated late, no fallback to S with them
             assert k["dense_columns"] == 4 and k["late_columns"] == 0 and k["dense_fallbacks"] == 0
         else:
