@@ -697,7 +697,8 @@ int hipfact_get_info(const hipfact_handle* h, const char* name, double* value);
 
 /* Debugging aid (tests, scripts): copies the first `bytes` of a named device buffer of the active plan
  * state to the host ("L", "SPf", "sitems", "y", "xhat", "ysol", "uvec", "dscale"; "mY": the m x 16 block of
- * the last pass of the blocked solve, pivot order), or of one of the
+ * the last pass of the blocked solve, pivot order; "res": the last residual of the single solve, caller's numbering;
+ * "norms": the partial maxima (r, b, z per block, info "resid_blocks" blocks) its kernel left), or of one of the
  * active host plan's front arrays ("perm", "sn_c0", "sn_r", "sn_rowptr", "sn_rows", "sn_Loff", "late_cols", "sn_level", "dense_cols";
  * int32, except int64 for sn_rowptr and sn_Loff). */
 int hipfact_debug_copy(hipfact_handle* h, const char* name, void* out, size_t bytes);

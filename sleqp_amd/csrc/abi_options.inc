@@ -206,6 +206,7 @@ static const OptionRow kOptions[] = {
     {nullptr, "HIPFACT_SOL_SPLIT", FX_NONE, OPT_STORE(sol_split, v != 0.0), nullptr},
     {nullptr, "HIPFACT_IDX64", FX_NONE, OPT_STORE(idx64, v != 0.0), nullptr},
     {nullptr, "HIPFACT_XCD_CLASSES", FX_NONE, OPT_STORE(xcd_classes, std::max(1, std::min(XCD_CLASSES_MAX, (int)v))), nullptr},
+    {nullptr, "HIPFACT_RESID_FROM_X", FX_NONE, OPT_STORE(resid_from_x, std::max(0, std::min(3, (int)v))), nullptr},
 };
 #undef OPT_STORE
 
@@ -274,6 +275,8 @@ int hipfact_debug_copy(hipfact_handle* h, const char* name, void* out, size_t by
   else if (!strcmp(name, "uvec")) b = &h->d_uvec;
   else if (!strcmp(name, "dscale")) b = &h->d_dscale;
   else if (!strcmp(name, "Kval")) b = &h->d_Kval;
+  else if (!strcmp(name, "res")) b = &h->d_res;      // the last residual of the single solve, caller's numbering
+  else if (!strcmp(name, "norms")) b = &h->d_norms;  // ... and the partial maxima (r, b, z per block) its kernel left
   else if (!strcmp(name, "mY")) b = &h->d_mY;  // the last block of the blocked solve: m x MR, pivot order
   if (!strcmp(name, "cond_d")) {  // diag(D) of the last condition estimate, caller's numbering (behind blocks, witness, h, a)
     const size_t N = (size_t)h->N_ext, off = (2 * COND_T + 3) * N * sizeof(double);
@@ -513,6 +516,8 @@ int hipfact_get_info(const hipfact_handle* h, const char* name, double* value) {
   INFO("rows_fused", h->rows_fused) INFO("rows_split", h->rows_split)
   INFO("long_row_segments", h->n_rseg) INFO("row_scale_blocks", row_scale_in_sequence(h) ? h->rs_grid : 0)
   INFO("arena_fill_bytes", arena_fill_bytes(P))
+  // the mode of the first residual of a checked solve on this plan, and the residual launches queued in either mode
+  INFO("resid_blocks", resid_blocks(P)) INFO("resid_from_x", resid_from_x(h)) INFO("resid_queued_from_x", h->resid_queued_from_x) INFO("resid_queued_full", h->resid_queued_full)
   INFO("xcd_classes", h->xcd_classes) INFO("dealt_multi_item_fronts", h->dealt_multi) INFO("long_prod_segments", h->n_lprod)
   INFO("long_col_segments", h->n_cseg) INFO("idx32", h->idx32) INFO("prod_packed", h->prod_packed)
   INFO("active_bounds", h->maps_on ? h->n_bounds : 0)

@@ -116,6 +116,10 @@ struct XupdIn {
   int acc;
   int nblocks;
   double* __restrict__ dot_out;  // per workgroup: partial of b_x . z_x (the r.g of a CG iteration), or null
+  // res non-null (plain assignment only): the lane group of a column that is not long also leaves res[j] = b_j - (K z)_j
+  // with the bits the column sweep of k_residual_saddle would give it (x_col_resid); Kval: K's own values, for the diagonal
+  const double* __restrict__ Kval;
+  double* __restrict__ res;
 };
 struct CgCtl {
   double rg, z_nrm_sq, rel_tol_sq, rad_sq, alpha, beta, tau;

@@ -280,19 +280,26 @@ __global__ __launch_bounds__(FB) void k_x_saddle(int n, int m, const int* __rest
                                                  const int* __restrict__ perm, SaddleMaps M,
                                                  const double* __restrict__ yp, const double* __restrict__ b,
                                                  double* __restrict__ z, const int* __restrict__ skip,
-                                                 int* __restrict__ epoch) {
+                                                 int* __restrict__ epoch, const double* __restrict__ Kval,
+                                                 double* __restrict__ res) {
   if (skip && *skip) return;
   if (epoch && blockIdx.x == 0 && threadIdx.x == 0) *epoch += 1;  // the fused solve launch before this one is over
   const int sub = threadIdx.x % CL;
   const int cpb = FB / CL;
   for (int j = blockIdx.x * cpb + threadIdx.x / CL; j < n; j += gridDim.x * cpb) {
     double s = 0.0;
-    const int e1 = Kp[j + 1];
-    if (e1 - Kp[j] - 1 > LONG_COL) continue;  // (uniform over the lane group; x_long_cols below)
-    for (int e = Kp[j] + 1 + sub; e < e1; e += CL) s += Ksc[e] * yp[Kc_y[e]];
+    const int e0 = Kp[j] + 1 + sub, e1 = Kp[j + 1];
+    if (e1 - (e0 - sub) > LONG_COL) continue;  // (uniform over the lane group; x_long_cols below)
+    for (int e = e0; e < e1; e += CL) s += Ksc[e] * yp[Kc_y[e]];
+    const double part = s;
 #pragma unroll
     for (int o = CL / 2; o > 0; o >>= 1) s += __shfl_down(s, o, CL);
     if (sub == 0) (void)x_col_write(M, j, s, b, z, ACC ? 1 : 0);
+    if (!ACC && res)  // (uniform; res null: z alone, as ever)
+      x_col_resid(M, j, sub, true, part, s, b, sub == CL - 1 ? Kval[e0 - CL] : 0.0, res, [&](double r) {
+        for (int e = e0; e < e1; e += CL) r += Ksc[e] * yp[Kc_y[e]];
+        return r;
+      });
   }
   if (M.ncseg > 0) {
     __shared__ double lsum[FB / 64];
@@ -357,6 +364,11 @@ __device__ __forceinline__ void resid_row_tail(const SaddleMaps& M, int k, const
 // res = b - K z for the saddle matrix (columns < n of the lower CSC hold I and A), in the caller's
 // numbering.  Two sweeps with cooperative lanes (8 per column of K, 16 per row of A); the last
 // block updates the refinement control block (ctl null: plain residual).
+// from_x > 0: the x update in front of this launch has left res[j] of every column that is not long (XupdIn::res,
+// x_col_resid: the same bits).  The column half then gathers nothing: one thread per column streams res, b and z into
+// the maxima (and takes the unit row of an active bound, as resid_col_tail does), on gridDim.x >> from_x of the blocks -
+// the gathers of the row half are what the launch waits for.  Long columns and the row half as ever; the number of
+// partial maxima does not change, and maxima do not depend on how the work is dealt to the blocks.
 __global__ __launch_bounds__(FB) void k_residual_saddle(int n, int m, const int* __restrict__ Kp,
                                                         const int* __restrict__ Ki, const double* __restrict__ Kval,
                                                         const int* __restrict__ Ar_ptr, const int* __restrict__ Ar_col,
@@ -364,17 +376,35 @@ __global__ __launch_bounds__(FB) void k_residual_saddle(int n, int m, const int*
                                                         const int* __restrict__ perm, SaddleMaps M,
                                                         const double* __restrict__ b, const double* __restrict__ z,
                                                         double* __restrict__ res, const RefineCtl* __restrict__ ctl,
-                                                        double* __restrict__ partials, int first, int* __restrict__ defer) {
+                                                        double* __restrict__ partials, int first, int* __restrict__ defer,
+                                                        int from_x) {
   if (ctl && !first && ctl->done) return;
   double mr = 0.0, mb = 0.0, mz = 0.0;
   __shared__ double lsum[FB / 64];
   // The two sweeps are chains of three dependent gathers each (pointer -> index / value -> vector entry);
   // the first half of the grid takes the columns of K, the second half the rows of A, side by side.
-  const int nbx = (int)gridDim.x >> 1;
+  const int nbx = from_x > 0 ? max(1, (int)gridDim.x >> from_x) : (int)gridDim.x >> 1;
   if ((int)blockIdx.x < nbx) {
     const int sub = threadIdx.x % CL;
     const int cpb = FB / CL;
-    const int iters = (n + nbx * cpb - 1) / (nbx * cpb);
+    const int iters = from_x > 0 ? 0 : (n + nbx * cpb - 1) / (nbx * cpb);
+    if (from_x > 0)
+      for (int j = blockIdx.x * FB + threadIdx.x; j < n; j += nbx * FB) {
+        if (M.ncseg > 0 && Kp[j + 1] - Kp[j] - 1 > LONG_COL) continue;  // (the long-column phase below)
+        const double bj = b[j], zj = z[j], rj = res[j];
+        const int v = M.vmap ? M.vmap[j] : -1;
+        if (v >= 0) {  // the bound's own row x_j = b_v: resid_col_tail
+          const double zv = z[v], bv = b[v];
+          const double rv = bv - zj;
+          res[v] = rv;
+          mr = nanmax(mr, fabs(rv));
+          mb = fmax(mb, fabs(bv));
+          mz = fmax(mz, fabs(zv));
+        }
+        mr = nanmax(mr, fabs(rj));
+        mb = fmax(mb, fabs(bj));
+        mz = fmax(mz, fabs(zj));
+      }
     for (int it = 0; it < iters; ++it) {  // uniform trip count (the shuffles need whole groups)
       const int j = (it * nbx + blockIdx.x) * cpb + threadIdx.x / CL;
       double s = 0.0;

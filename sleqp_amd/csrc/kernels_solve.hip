@@ -98,7 +98,7 @@ INST_LSQR(16)
 INST_LSQR(64)
 #undef INST_LSQR
 template __global__ void k_x_saddle<true>(int, int, const int*, const double*, const int*, const int*, SaddleMaps,
-                                          const double*, const double*, double*, const int*, int*);
+                                          const double*, const double*, double*, const int*, int*, const double*, double*);
 template __global__ void k_x_saddle<false>(int, int, const int*, const double*, const int*, const int*, SaddleMaps,
-                                           const double*, const double*, double*, const int*, int*);
+                                           const double*, const double*, double*, const int*, int*, const double*, double*);
 }  // namespace hipfact

@@ -666,6 +666,46 @@ __device__ __forceinline__ double x_col_write(const SaddleMaps& M, int j, double
   z[j] = zj;
   return bj * zj;
 }
+// The x half of the FIRST residual from the x update's own sums (XupdIn::res, plain assignment): r_j = b_j - (K z)_j of
+// a column that is not long, with exactly the bits the column sweep of k_residual_saddle leaves - which only repeats the
+// x update's products (the row scales are powers of two: Kval[e] (d_k y^_k) and Ksc[e] y^_k are the same double, and a
+// row outside the working set contributes 0 y^_k = 0 here and nothing there) to obtain the rounding error of z_j.  The
+// two sweeps associate differently: lane L >= 1 of the residual sums what lane L - 1 of the x update sums, in the same
+// order, and lane 0 sums diag z_j first and then what the x update's LAST lane sums.  So that lane adds its products once
+// more behind diag z_j (resum), and the residual's shuffle tree (4, 2, 1) runs over the lanes rotated by one: the total
+// arrives in the last lane, which subtracts it from b_j as resid_col_tail does (active bound: the multiplier's unit
+// entry last).  Called by all CL lanes of the group (ok: uniform).  part: the lane's own sum in front of the x update's
+// tree, tot: that tree's total (lane 0).  Where d_k y^_k or a product is subnormal or overflows, the two forms of a
+// product can differ in the last bit: r_j then differs by one rounding of what is itself rounding noise.
+template <class Resum>
+__device__ __forceinline__ void x_col_resid(const SaddleMaps& M, int j, int sub, bool ok, double part, double tot,
+                                            const double* __restrict__ b, double diag, double* __restrict__ res,
+                                            Resum resum) {
+  const bool last = ok && sub == CL - 1;
+  tot = __shfl(tot, 0, CL);
+  double s = part, bj = 0.0, mult = 0.0;
+  int v = -1;
+  if (last) {
+    bj = b[j];
+    v = M.vmap ? M.vmap[j] : -1;
+    double zj;  // (what x_col_write has stored, from the same expressions)
+    if (v >= 0) {
+      const double beta = b[v];
+      zj = beta;
+      mult = (bj - beta) - tot;
+    } else
+      zj = bj - tot;
+    s = 0.0;
+    s += diag * zj;
+    s = resum(s);
+  }
+#pragma unroll
+  for (int o = CL / 2; o > 0; o >>= 1) s += __shfl(s, (sub + o) & (CL - 1), CL);
+  if (last) {
+    if (v >= 0) s += mult;
+    res[j] = bj - s;
+  }
+}
 // the long columns of K (SaddleMaps::cseg: dense Jacobian columns), one workgroup of NT threads per segment; POLL:
 // the entries of y^ are polled (inside the tree launch).  Returns (thread 0) the columns' share of b_x . z_x.
 template <bool POLL, int NT>
@@ -707,7 +747,7 @@ __device__ __forceinline__ void dev_x_update(const XupdIn& X, int xb, const doub
     ysc = M.dscale[k0];
   }
   for (int jb = xb * cpb + threadIdx.x / XL; jb < X.n; jb += XP * stride) {
-    double val[XP][XE];
+    double val[XP][XE], dg[XP];
     int idx[XP][XE], enext[XP], eend[XP];
     bool colok[XP];
 #pragma unroll
@@ -725,6 +765,7 @@ __device__ __forceinline__ void dev_x_update(const XupdIn& X, int xb, const doub
       }
       enext[p] = e0 + XL * XE;
       eend[p] = e1;
+      dg[p] = (X.res && ok && sub == XL - 1) ? X.Kval[e0 - XL] : 0.0;  // (the column's diagonal: x_col_resid)
     }
     unsigned long long bits[XP][XE];
 #pragma unroll
@@ -735,17 +776,26 @@ __device__ __forceinline__ void dev_x_update(const XupdIn& X, int xb, const doub
 #pragma unroll
     for (int p = 0; p < XP; ++p) {
       const int j = jb + p * stride;
-      double s = 0.0;
+      double s = 0.0, yv[XE];
 #pragma unroll
       for (int t = 0; t < XE; ++t)
         if (idx[p][t] >= 0) {
-          const double yv = (bits[p][t] == SOLVE_SENT) ? poll_f64(ys + idx[p][t], info) : __longlong_as_double((long long)bits[p][t]);
-          s += val[p][t] * yv;
+          yv[t] = (bits[p][t] == SOLVE_SENT) ? poll_f64(ys + idx[p][t], info) : __longlong_as_double((long long)bits[p][t]);
+          s += val[p][t] * yv[t];
         }
       for (int e = enext[p]; e < eend[p]; e += XL) s += X.Ksc[e] * poll_f64(ys + X.Kc_y[e], info);
+      const double part = s;
 #pragma unroll
       for (int o = XL / 2; o > 0; o >>= 1) s += __shfl_down(s, o, XL);
       if (sub == 0 && colok[p]) dsum += x_col_write(M, j, s, X.b, X.z, X.acc);
+      if (X.res)  // (uniform) the first XE products are still in registers, the tail's operands are read again
+        x_col_resid(M, j, sub, colok[p], part, s, X.b, dg[p], X.res, [&](double r) {
+#pragma unroll
+          for (int t = 0; t < XE; ++t)
+            if (idx[p][t] >= 0) r += val[p][t] * yv[t];
+          for (int e = enext[p]; e < eend[p]; e += XL) r += X.Ksc[e] * poll_f64(ys + X.Kc_y[e], info);
+          return r;
+        });
     }
   }
   if (M.ncseg > 0) {  // (uniform)

@@ -85,6 +85,17 @@ static inline bool row_scale_in_sequence(const hipfact_handle* h) {
   const Plan& P = h->plan;
   return P.saddle && P.n > 0 && P.m > 0;
 }
+// The x update leaves the x half of the FIRST residual of a checked solve on its way (XupdIn::res) and the residual
+// kernel's column half only streams it (k_residual_saddle, from_x): 0 for today's full column sweep, otherwise the
+// share of the residual's grid the column half gets (gridDim.x >> from_x).  Decided HERE only, and only where the bits
+// are shown to be equal: a saddle plan whose scaled values are K's own times the row scale in every column (no dense
+// column, no late variable: masked_rows), whatever the working-set maps say (x_col_resid covers active bounds; a row
+// outside the working set has zero values).  solve_enqueue asks for it for the first pass alone - a residual behind a
+// correction pass, the Krylov loops, the blocked and the extra-precise solves never do.
+static inline int resid_from_x(const hipfact_handle* h) {
+  const Plan& P = h->plan;
+  return (P.saddle && P.n > 0 && P.m > 0 && h->nd == 0 && P.n_late == 0 && h->refine_steps > 0) ? h->resid_from_x : 0;
+}
 // The launch routes of a handle, each decided HERE only.  dataflow_factor: the top levels (and the pivot blocks of chain
 // levels) are single dataflow launches; tree_solve: the sweeps of a solve are the one tree launch (k_solve_tree), not the
 // per-level kernels; tree_delivers_verdict: ... and every solve has it (its extra workgroup delivers a deferred
@@ -534,12 +545,14 @@ static void launch_rhs_saddle(hipfact_handle* h, const SaddleMaps& M, const doub
          h->d_Ar_col.as<int>(), h->d_Ar_val.as<double>(), h->d_perm.as<int>(), M, b, y ? y : h->d_y.as<double>(), skip);
 }
 // z = (acc: z +) the solution in the caller's numbering, from y and the leaf columns of K (saddle mode)
+// (res: the x half of the first residual on the way, XupdIn::res; plain assignment only)
 static void launch_x_saddle(hipfact_handle* h, const SaddleMaps& M, const double* b, double* z, bool acc, const int* skip,
-                            int* epoch, const double* y = nullptr) {
+                            int* epoch, const double* y = nullptr, double* res = nullptr) {
   const Plan& P = h->plan;
   auto go = [&](auto ACC) {
     LAUNCH(PC_XUPD, k_x_saddle<decltype(ACC)::value>, dim3(nblocks((long long)P.n * 8)), dim3(FB), 0, P.n, P.m, h->d_Kp.as<int>(),
-           h->d_Ksc.as<double>(), h->d_Kc_y.as<int>(), h->d_perm.as<int>(), M, y ? y : h->d_y.as<double>(), b, z, skip, epoch);
+           h->d_Ksc.as<double>(), h->d_Kc_y.as<int>(), h->d_perm.as<int>(), M, y ? y : h->d_y.as<double>(), b, z, skip, epoch,
+           h->d_Kval.as<double>(), acc ? nullptr : res);
   };
   acc ? go(std::true_type()) : go(std::false_type());
 }
@@ -580,6 +593,8 @@ static void solve_once_async(hipfact_handle* h, const double* b, double* z, bool
   // fused solve launch: the kernel behind it advances the epoch of its double-buffered exchange slots
   int* epoch = (tree && P.m > 0) ? h->d_epoch.as<int>() : nullptr;
   h->last_rhs_in_tree = h->last_xupd_in_tree = h->last_xupd_blocks = 0;
+  // (the x half of the residual is asked of the first pass of a checked solve alone: solve_enqueue)
+  double* const x_res = (acc || raw) ? nullptr : h->x_res_out;
   if (P.saddle) {
     const SaddleMaps M = saddle_maps(h);
     // The shape of the launches: the forward items of the tree launch form their own rows of the right-hand side,
@@ -608,13 +623,15 @@ static void solve_once_async(hipfact_handle* h, const double* b, double* z, bool
           X.dot_out = h->x_dot_out;
           h->x_dot_blocks = X.nblocks;
         }
+        X.Kval = h->d_Kval.as<double>();
+        X.res = x_res;
       }
       h->last_rhs_in_tree = rhs_in_tree;
       h->last_xupd_in_tree = whole;
       h->last_xupd_blocks = X.nblocks;
       solve_m_async(h, skip, (rhs_in_tree || whole) ? &R : nullptr, whole ? &X : nullptr);
     }
-    if (!whole) launch_x_saddle(h, M, b, z, acc, skip, epoch);
+    if (!whole) launch_x_saddle(h, M, b, z, acc, skip, epoch, nullptr, x_res);
   } else {
     launch_rhs_perm(h, b, skip);
     solve_m_async(h, skip);
@@ -640,8 +657,9 @@ static DecideIn decide_in(hipfact_handle* h, int col) {
 
 // res = b - K z; updates the refinement control block (first: the residual of the first pass).  defer: no verdict
 // launch behind it - the next tree launch (or flush_decide) delivers it.  col: decide_in
+// from_x: resid_from_x, when the x update in front has left the x half in res
 static void residual_async(hipfact_handle* h, const double* b, const double* z, double* res, bool first,
-                           bool defer = false, int col = -1) {
+                           bool defer = false, int col = -1, int from_x = 0) {
   const Plan& P = h->plan;
   const DecideIn D = decide_in(h, col);
   RefineCtl* ctl = D.ctl;
@@ -652,7 +670,8 @@ static void residual_async(hipfact_handle* h, const double* b, const double* z, 
            h->d_Ki.as<int>(), h->d_Kval.as<double>(), h->d_Ar_ptr.as<int>(), h->d_Ar_col.as<int>(),
            (masked_rows(h) ? h->d_Ar_full : h->d_Ar_val).as<double>(), h->d_perm.as<int>(), saddle_maps(h), b, z, res, ctl,
            norms,
-           first ? 1 : 0, dflag);
+           first ? 1 : 0, dflag, from_x);
+    ++(from_x > 0 ? h->resid_queued_from_x : h->resid_queued_full);
   } else {
     LAUNCH(PC_RESID, k_residual_sym, dim3(resid_blocks(P)), dim3(FB), 0, P.N, h->d_Kp.as<int>(), h->d_Ki.as<int>(),
            h->d_Kval.as<double>(), h->d_Tp.as<int>(), h->d_Ti.as<int>(), h->d_Tsrc.as<int>(), b, z, res, ctl,
@@ -759,19 +778,24 @@ static int correct_enqueue(hipfact_handle* h, const double* bb, double* z, int p
 // Keys of the captured solve sequences (run_cached's `passes`, the launch notes): SolveDecision::key (the correction
 // passes in the graph; -2 with the verdict left to the next tree launch - a workgroup of that launch instead of a
 // one-block launch and its kernel boundary behind every solve -, -1 without a residual), top_block_key added with the
-// top block
+// top block, resid_x_key with the first residual's x half taken from the x update (per share of the grid)
 static inline int top_block_key(const hipfact_handle* h) { return h->tb_valid ? 1000 : 0; }
+static inline int resid_x_key(int from_x) { return 2000 * from_x; }
 
 // first pass z = K^-1 b, residual, and the in-graph correction passes
-static int solve_enqueue(hipfact_handle* h, const double* b, double* z, const hipfact::SolveDecision& d) {
+static int solve_enqueue(hipfact_handle* h, const double* b, double* z, const hipfact::SolveDecision& d, int from_x) {
   const double* bb = b;
   if (h->refine_steps > 0 && b == z) {  // keep a private copy of b for the residual
     HCHECK(h, hipMemcpyAsync(h->d_rhs.p, b, (size_t)h->N_ext * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     bb = h->d_rhs.as<double>();
   }
+  const bool checked = h->refine_steps > 0 && !d.unchecked;
+  if (!checked) from_x = 0;
+  h->x_res_out = from_x > 0 ? h->d_res.as<double>() : nullptr;
   solve_once_async(h, bb, z, false, nullptr);
-  if (h->refine_steps > 0 && !d.unchecked) {
-    residual_async(h, bb, z, h->d_res.as<double>(), true, d.defer);
+  h->x_res_out = nullptr;
+  if (checked) {
+    residual_async(h, bb, z, h->d_res.as<double>(), true, d.defer, -1, from_x);
     return correct_enqueue(h, bb, z, d.passes);
   }
   HCHECK(h, hipGetLastError());
@@ -858,9 +882,10 @@ static int solve_async(hipfact_handle* h, const double* b, double* z, bool all_c
   if (d.flush_first) flush_decide(h);  // no tree launch to deliver it
   // (an unchecked steady-state solve is two launches: queued directly - replaying a two-node graph measures 4-5 us
   // slower per solve than the launches themselves)
-  const int key = d.key + top_block_key(h);
+  const int from_x = d.unchecked ? 0 : resid_from_x(h);
+  const int key = d.key + top_block_key(h) + resid_x_key(from_x);
   h->note(d.unchecked ? 'U' : 'S', key);
-  const int rc = d.unchecked ? solve_enqueue(h, b, z, d) : run_cached(h, 1, b, z, [&] { return solve_enqueue(h, b, z, d); }, key);
+  const int rc = d.unchecked ? solve_enqueue(h, b, z, d, 0) : run_cached(h, 1, b, z, [&] { return solve_enqueue(h, b, z, d, from_x); }, key);
   if (rc) return rc;
   cad.solve_queued(knobs, d);
   h->num_solve++;

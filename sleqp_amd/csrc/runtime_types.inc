@@ -384,6 +384,11 @@ struct hipfact_handle : PlanState, SingleSolveMemo {
   int x_dot_blocks = 0;
   int xupd_blocks = 256;      // workgroups of the x update inside the tree launch (xupd_fused)
   bool solve_sorted = true;   // solve items of a level: biggest fronts first
+  // HIPFACT_RESID_FROM_X (0-3; runtime_queue.inc: resid_from_x): the x update leaves the x half of a checked solve's first
+  // residual and the residual kernel's column half streams it on 1 / 2^value of its grid; 0: the full column sweep
+  int resid_from_x = 3;
+  double* x_res_out = nullptr;  // set around the first pass of a checked solve (solve_enqueue): where the x update leaves it
+  long resid_queued_from_x = 0, resid_queued_full = 0;  // saddle residual launches queued (or captured) in either mode
   int xcd_classes = 8;        // HIPFACT_XCD_CLASSES (1-16): classes the rows of k_row_scale and the items of the per-level panel / Schur launches are dealt to (1: plain order)
   int factor_top_max = 160;   // levels with at most this many fronts join the single-launch top-of-tree factorisation (0: off)
   int factor_top_levels = 1 << 20;  // at most this many levels in the single-launch top-of-tree factorisation (tests)
