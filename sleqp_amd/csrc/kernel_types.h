@@ -70,7 +70,7 @@ struct MultiIn {
   long long ldy;
   double* __restrict__ U;             // update blocks, MR doubles per update row
 };
-// The columns of a blocked double-double residual / norm launch (kernels_saddle_dd_multi.inc): column slot q of B, Z and
+// The columns of a double-double residual / norm launch (kernels_saddle_dd.inc, kernels_saddle_dd_multi.inc): column slot q of B, Z and
 // R at b + q ldb, z + q ldz, res + q ldr; the launch works on the nc slots col[0 .. nc).
 struct DdCols {
   const double* b;

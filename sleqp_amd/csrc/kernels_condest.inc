@@ -1,5 +1,5 @@
 // kernels_condest.inc - the estimator's own kernels of hipfact_condition_estimate (runtime_condest.inc; the rule is
-// condest_rule.h): a = |K| v by the walk of the residual kernels, the start block and blocks of unit vectors, the pass
+// condest_rule.h): a = |K| v by the walk of kernels_k_walk.inc, the start block and blocks of unit vectors, the pass
 // over Y (column 1-norms, S = sign(Y), sign words), the parallel test on the sign words, h_i = max_j |Z_ij| and the
 // selection, the power-of-two scalings of a block.
 // (the translation unit kernels_extra.hip)
@@ -11,20 +11,8 @@
 constexpr int COND_GRID = 256;  // workgroups (= partials) of the pass, parallel and selection kernels at most
 
 // ---- a = |K| v ----------------------------------------------------------------------------------------------------------
-// sum over the workgroup in a fixed order (valid in thread 0).  lds: FB / 64 doubles.
-__device__ __forceinline__ double cond_block_sum(double s, double* lds) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = s;
-  __syncthreads();
-  double a = 0.0;
-  if (threadIdx.x == 0)
-    for (int q = 0; q < FB / 64; ++q) a += lds[q];
-  return a;
-}
-// what the lane that holds the sum of column j of K / row k of A does with it (resid_col_tail / resid_row_tail with
-// |.| on every term: the unit row of an active bound, the division by the row's scale)
+// what the lane that holds the sum of column j of K / row k of A does with it (the tails of the residual with |.| on
+// every term: the unit row of an active bound, the division by the row's scale)
 __device__ __forceinline__ void cond_col_tail(const SaddleMaps& M, int j, double s, const double* __restrict__ v,
                                               double* __restrict__ a) {
   const int b = M.vmap ? M.vmap[j] : -1;
@@ -39,94 +27,37 @@ __device__ __forceinline__ void cond_row_tail(const SaddleMaps& M, int k, const 
   const int i = ext_row(M, perm[k]);
   if (i >= 0) a[i] = s / M.dscale[k];
 }
-// The walk of k_residual_saddle_dd (lane groups, maps, masked rows through Ar_val, a long row or column by the ONE
-// workgroup that holds its segment 0) with fabs on every term: a = |K| v for the matrix residuals are taken against.
+// The accumulator policy of the walk of kernels_k_walk.inc with |.| on every term: plain fp64 sums, one column, no block
+// maxima.  A term is ONE fused multiply-add, written out: that is what the compiler made of `s += fabs(k) * v` in the
+// kernels this policy replaces, and norm1 keeps their bits only as long as it stays one.
+struct AbsProduct {
+  using sum_t = double;
+  static constexpr int cnt = 1;
+  const double* __restrict__ v;
+  double* __restrict__ a;
+  __device__ __forceinline__ static double zero() { return 0.0; }
+  __device__ __forceinline__ void add(double& s, int, double kv, int i) const { s = fma(fabs(kv), v[i], s); }
+  __device__ __forceinline__ void col_tail(const SaddleMaps& M, int j, int, double s) const { cond_col_tail(M, j, s, v, a); }
+  __device__ __forceinline__ void row_tail(const SaddleMaps& M, int k, const int* __restrict__ perm, int, double s) const {
+    cond_row_tail(M, k, perm, s, a);
+  }
+  __device__ __forceinline__ void sym_tail(int j, int, double s) const { a[j] = s; }
+};
+// a = |K| v for the matrix residuals are taken against (masked rows through Ar_val)
 __global__ __launch_bounds__(FB) void k_cond_abs_saddle(int n, int m, const int* __restrict__ Kp, const int* __restrict__ Ki,
                                                         const double* __restrict__ Kval, const int* __restrict__ Ar_ptr,
                                                         const int* __restrict__ Ar_col, const double* __restrict__ Ar_val,
                                                         const int* __restrict__ perm, SaddleMaps M,
                                                         const double* __restrict__ v, double* __restrict__ a) {
-  __shared__ double lsum[FB / 64];
-  const int nbx = (int)gridDim.x >> 1;
-  if ((int)blockIdx.x < nbx) {
-    const int sub = threadIdx.x % CL;
-    const int cpb = FB / CL;
-    const int iters = (n + nbx * cpb - 1) / (nbx * cpb);
-    for (int it = 0; it < iters; ++it) {  // uniform trip count (the shuffles need whole groups)
-      const int j = (it * nbx + blockIdx.x) * cpb + threadIdx.x / CL;
-      double s = 0.0;
-      bool mine = j < n;
-      if (mine) {
-        const int e1 = Kp[j + 1];
-        if (e1 - Kp[j] - 1 > LONG_COL)
-          mine = false;
-        else
-          for (int e = Kp[j] + sub; e < e1; e += CL) {
-            const int i = Ki[e];
-            const int zi = i < n ? i : ext_row(M, i - n);
-            if (zi >= 0) s += fabs(Kval[e]) * v[zi];
-          }
-      }
-#pragma unroll
-      for (int o = CL / 2; o > 0; o >>= 1) s += __shfl_down(s, o, CL);
-      if (sub == 0 && mine) cond_col_tail(M, j, s, v, a);
-    }
-    for (int q = blockIdx.x; q < M.ncseg; q += nbx) {
-      const LongSeg sg = M.cseg[q];
-      if (sg.idx != 0) continue;  // (uniform over the workgroup)
-      const int j = sg.id;
-      double s = 0.0;
-      for (int e = Kp[j] + (int)threadIdx.x; e < Kp[j + 1]; e += FB) {
-        const int i = Ki[e];
-        const int zi = i < n ? i : ext_row(M, i - n);
-        if (zi >= 0) s += fabs(Kval[e]) * v[zi];
-      }
-      s = cond_block_sum(s, lsum);
-      if (threadIdx.x == 0) cond_col_tail(M, j, s, v, a);
-    }
-  } else {
-    const int nby = (int)gridDim.x - nbx, by = (int)blockIdx.x - nbx;
-    const int sub = threadIdx.x % RL;
-    const int rpb = FB / RL;
-    const int iters = (m + nby * rpb - 1) / (nby * rpb);
-    for (int it = 0; it < iters; ++it) {
-      const int k = (it * nby + by) * rpb + threadIdx.x / RL;
-      double s = 0.0;
-      bool mine = k < m;
-      if (mine) {
-        const int p1 = Ar_ptr[k + 1];
-        if (p1 - Ar_ptr[k] > LONG_ROW)
-          mine = false;
-        else
-          for (int p = Ar_ptr[k] + sub; p < p1; p += RL) s += fabs(Ar_val[p]) * v[Ar_col[p]];
-      }
-#pragma unroll
-      for (int o = RL / 2; o > 0; o >>= 1) s += __shfl_down(s, o, RL);
-      if (sub == 0 && mine) cond_row_tail(M, k, perm, s, a);
-    }
-    for (int q = by; q < M.nrseg; q += nby) {
-      const LongSeg sg = M.rseg[q];
-      if (sg.idx != 0) continue;
-      const int k = sg.id;
-      double s = 0.0;
-      for (int p = Ar_ptr[k] + (int)threadIdx.x; p < Ar_ptr[k + 1]; p += FB) s += fabs(Ar_val[p]) * v[Ar_col[p]];
-      s = cond_block_sum(s, lsum);
-      if (threadIdx.x == 0) cond_row_tail(M, k, perm, s, a);
-    }
-  }
+  AbsProduct acc{v, a};
+  k_walk_saddle<1>(n, m, Kp, Ki, Kval, Ar_ptr, Ar_col, Ar_val, perm, M, acc);
 }
-// Generic mode: the two lists of k_residual_sym, one thread per row
 __global__ __launch_bounds__(FB) void k_cond_abs_sym(int N, const int* __restrict__ Kp, const int* __restrict__ Ki,
                                                      const double* __restrict__ Kval, const int* __restrict__ Tp,
                                                      const int* __restrict__ Ti, const int* __restrict__ Tsrc,
                                                      const double* __restrict__ v, double* __restrict__ a) {
-  for (int j = blockIdx.x * FB + threadIdx.x; j < N; j += gridDim.x * FB) {
-    double s = 0.0;
-    for (int e = Kp[j]; e < Kp[j + 1]; ++e) s += fabs(Kval[e]) * v[Ki[e]];  // column j: rows >= j
-    for (int p = Tp[j]; p < Tp[j + 1]; ++p)                                 // row j: columns < j
-      if (Ti[p] != j) s += fabs(Kval[Tsrc[p]]) * v[Ti[p]];
-    a[j] = s;
-  }
+  AbsProduct acc{v, a};
+  k_walk_generic<1>(N, Kp, Ki, Kval, Tp, Ti, Tsrc, acc);
 }
 // d = the diagonal of D in the caller's numbering: ones, then (saddle mode, a launch behind) the row scales
 __global__ __launch_bounds__(FB) void k_cond_ones(int N, double* __restrict__ d) {
@@ -139,7 +70,7 @@ __global__ __launch_bounds__(FB) void k_cond_row_scales(int m, const int* __rest
     if (i >= 0) d[i] = M.dscale[k];
   }
 }
-// max_i d_i a_i, NaN-propagating: a partial per workgroup, then one workgroup (k_block_maxabs's pattern)
+// max_i d_i a_i, NaN-propagating: a partial per workgroup, then one workgroup (k_block_maxabs_multi's pattern)
 __device__ __forceinline__ double cond_block_max(double v, double* sh) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = nanmax(v, __shfl_down(v, o, 64));

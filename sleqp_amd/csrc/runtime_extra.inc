@@ -3,7 +3,7 @@
 //
 // Every solve of the handle is refined on an fp64 residual: that drives the BACKWARD error to rounding level and
 // leaves a forward error of about cond(K) 2^-53.  Here the residual b - K z is accumulated as pairs of doubles
-// (dd_arith.h, k_residual_saddle_dd / k_residual_sym_dd) and rounded once: as long as the factor contracts
+// (dd_arith.h, k_residual_saddle_dd<1> / k_residual_sym_dd<1>) and rounded once: as long as the factor contracts
 // (||dz_k|| <= ||dz_{k-1}|| / 2) the iteration z += K^-1 (b - K z) then converges to the correctly rounded solution,
 // whatever cond(K) is, and the size of the last corrections measures the error that is left (LAPACK's xSYRFSX, MA57D).
 //   z = K^-1 b;  for k = 1, 2, ...:  r = b - K z (pairs);  dz = K^-1 r;  (||dz||, ||z||) per block;  the rule;  z += dz
@@ -63,18 +63,40 @@ static bool extra_rule_step(ExtraRule& R, const double* dn, const double* zn) {
   return true;
 }
 
-// res = b - K z in double-double; partials: the three block maxima of every workgroup (null: none)
-static void residual_dd_async(hipfact_handle* h, const double* b, const double* z, double* res, double* partials) {
+// the column slots of `mask` in the blocks B, Z and R (column slot q at b + q ldb, z + q ldz, res + q ldr)
+static DdCols dd_cols(const double* b, long long ldb, const double* z, long long ldz, double* res, long long ldr,
+                      unsigned int mask) {
+  DdCols C = {b, z, res, ldb, ldz, ldr, 0, {0}};
+  for (int j = 0; j < MR; ++j)
+    if ((mask >> j) & 1u) C.col[C.nc++] = j;
+  return C;
+}
+
+// R = B - K Z in double-double for the columns of C, NC (1, 4, 8 or 16) of them per walk over K; partials: the three
+// block maxima of every workgroup, those of column slot q at partials + q pstride (null: none)
+template <int NC>
+static void residual_dd_walks(hipfact_handle* h, const DdCols& C, double* partials, long long pstride) {
   const Plan& P = h->plan;
-  if (P.saddle) {
-    LAUNCH(PC_RESID, k_residual_saddle_dd, dim3(resid_blocks(P)), dim3(FB), 0, P.n, P.m, h->d_Kp.as<int>(),
-           h->d_Ki.as<int>(), h->d_Kval.as<double>(), h->d_Ar_ptr.as<int>(), h->d_Ar_col.as<int>(),
-           (masked_rows(h) ? h->d_Ar_full : h->d_Ar_val).as<double>(), h->d_perm.as<int>(), saddle_maps(h), b, z, res,
-           partials);
-  } else {
-    LAUNCH(PC_RESID, k_residual_sym_dd, dim3(resid_blocks(P)), dim3(FB), 0, P.N, h->d_Kp.as<int>(), h->d_Ki.as<int>(),
-           h->d_Kval.as<double>(), h->d_Tp.as<int>(), h->d_Ti.as<int>(), h->d_Tsrc.as<int>(), b, z, res, partials);
+  for (int c0 = 0; c0 < C.nc; c0 += NC) {
+    DdCols W = C;  // the walk's columns in front
+    W.nc = C.nc - c0;
+    for (int q = 0; q < W.nc; ++q) W.col[q] = C.col[c0 + q];
+    if (P.saddle) {
+      LAUNCH(PC_RESID, k_residual_saddle_dd<NC>, dim3(resid_blocks(P)), dim3(FB), 0, P.n, P.m, h->d_Kp.as<int>(),
+             h->d_Ki.as<int>(), h->d_Kval.as<double>(), h->d_Ar_ptr.as<int>(), h->d_Ar_col.as<int>(),
+             (masked_rows(h) ? h->d_Ar_full : h->d_Ar_val).as<double>(), h->d_perm.as<int>(), saddle_maps(h), W, partials,
+             pstride);
+    } else {
+      LAUNCH(PC_RESID, k_residual_sym_dd<NC>, dim3(resid_blocks(P)), dim3(FB), 0, P.N, h->d_Kp.as<int>(),
+             h->d_Ki.as<int>(), h->d_Kval.as<double>(), h->d_Tp.as<int>(), h->d_Ti.as<int>(), h->d_Tsrc.as<int>(), W,
+             partials, pstride);
+    }
   }
+}
+// res = b - K z in double-double: the one column slot 0
+static void residual_dd_async(hipfact_handle* h, const double* b, const double* z, double* res, double* partials) {
+  const long long N = h->N_ext;
+  residual_dd_walks<1>(h, dd_cols(b, N, z, N, res, N, 1u), partials, 0);
 }
 
 // res = b - K z in fp64, as every checked solve takes it, without a control block or block maxima
@@ -92,7 +114,7 @@ static void residual_fp64_async(hipfact_handle* h, const double* b, const double
   }
 }
 
-static const int g_maxabs_cap = 256;  // workgroups (= partial maxima) of k_block_maxabs
+static const int g_maxabs_cap = 256;  // workgroups (= partial maxima) per column of k_block_maxabs_multi
 
 // workspace: the vectors with the plan state, the small blocks with the handle; the handle stays usable when it fails
 static int extra_workspace(hipfact_handle* h) {
@@ -139,6 +161,7 @@ static int extra_loop(hipfact_handle* h, long solves_kept, hipfact_extra_info& o
   if (rc) return rc;
   const int split = P.saddle ? P.n : h->N_ext;
   const int nmax = nblocks((long long)N, g_maxabs_cap);
+  const DdCols one = dd_cols(b, (long long)N, z, (long long)N, r, (long long)N, 1u);  // the norms' column set: slot 0
   while (R.status < 0 && R.k < R.cap) {
     {
       Turn turn(h);
@@ -147,9 +170,10 @@ static int extra_loop(hipfact_handle* h, long solves_kept, hipfact_extra_info& o
     if ((rc = plain_solve(r, dz))) return rc;
     {
       Turn turn(h);
-      LAUNCH(PC_RESID, k_block_maxabs, dim3(nmax), dim3(FB), 0, split, (int)N, dz, z, h->d_xpart.as<double>());
-      LAUNCH(PC_RESID, k_block_maxabs_final, dim3(1), dim3(FB), 0, nmax, h->d_xpart.as<double>(),
-             static_cast<double*>(h->h_xout_dev));
+      LAUNCH(PC_RESID, k_block_maxabs_multi, dim3(nmax, 1), dim3(FB), 0, split, (int)N, dz, (long long)N, z, (long long)N,
+             one, h->d_xpart.as<double>());
+      LAUNCH(PC_RESID, k_block_maxabs_multi_final, dim3(1), dim3(FB), 0, nmax, one, h->d_xpart.as<double>(),
+             static_cast<double*>(h->h_xout_dev));  // (the four doubles of slot 0: the RefineCtl behind them is not touched)
     }
     HCHECK(h, hipGetLastError());
     if ((rc = check_info(h, Phase::solve, &switched))) return rc;  // the pass's synchronisation

@@ -4,7 +4,7 @@
 //
 // Per block of up to MR columns:
 //   B = a private copy of the caller's columns;  Z = K^-1 B (a plain blocked pass, multi_pass without a residual);
-//   for k = 1, 2, ...:  R = B - K Z in pairs, the open columns in ONE walk over K (kernels_saddle_dd_multi.inc);
+//   for k = 1, 2, ...:  R = B - K Z in pairs, the open columns in ONE walk over K (kernels_saddle_dd.inc);
 //                       dZ = K^-1 R (a plain blocked pass over the open columns, the others swept as zeros);
 //                       (||dz_j||, ||z_j||) per index block and column;  ONE synchronisation (check_info);
 //                       extra_rule_step per open column;  z_j += dz_j for the columns whose rule said so, one launch;
@@ -17,7 +17,7 @@
 // blocks Z and dZ: it touches nothing of the single solve and does not become "the last solve".  Plans with the
 // low-rank dense-column correction go column by column through solve_extra_device.
 
-// Columns of K per walk of the blocked double-double residual (the NC of k_residual_*_dd_multi: 4, 8 or 16; 16 columns
+// Columns of K per walk of the blocked double-double residual (the NC of k_residual_*_dd: 4, 8 or 16; 16 columns
 // are ceil(16 / NC) walks).  Registers, scratch and the measurement behind the choice: EXPERIMENTS.md, "Blocked
 // extra-precise solve".
 static const int g_dd_multi_nc = 8;
@@ -62,39 +62,14 @@ struct ExtraBlock {
   }
 };
 
-static DdCols dd_cols(const double* b, long long ldb, const double* z, long long ldz, double* res, long long ldr,
-                      unsigned int mask) {
-  DdCols C = {b, z, res, ldb, ldz, ldr, 0, {0}};
-  for (int j = 0; j < MR; ++j)
-    if ((mask >> j) & 1u) C.col[C.nc++] = j;
-  return C;
-}
-
-// R = B - K Z in pairs for the columns of C, nc_walk (4, 8 or 16) of them per walk over K; partials: the block maxima
-// of column slot q at partials + q pstride (null: none)
-template <int NC>
-static void residual_dd_multi_walks(hipfact_handle* h, const DdCols& C, double* partials, long long pstride) {
-  const Plan& P = h->plan;
-  for (int c0 = 0; c0 < C.nc; c0 += NC) {
-    if (P.saddle) {
-      LAUNCH(PC_RESID, k_residual_saddle_dd_multi<NC>, dim3(resid_blocks(P)), dim3(FB), 0, P.n, P.m, h->d_Kp.as<int>(),
-             h->d_Ki.as<int>(), h->d_Kval.as<double>(), h->d_Ar_ptr.as<int>(), h->d_Ar_col.as<int>(),
-             (masked_rows(h) ? h->d_Ar_full : h->d_Ar_val).as<double>(), h->d_perm.as<int>(), saddle_maps(h), C, c0,
-             partials, pstride);
-    } else {
-      LAUNCH(PC_RESID, k_residual_sym_dd_multi<NC>, dim3(resid_blocks(P)), dim3(FB), 0, P.N, h->d_Kp.as<int>(),
-             h->d_Ki.as<int>(), h->d_Kval.as<double>(), h->d_Tp.as<int>(), h->d_Ti.as<int>(), h->d_Tsrc.as<int>(), C, c0,
-             partials, pstride);
-    }
-  }
-}
+// R = B - K Z in pairs for the columns of C, nc_walk (4, 8 or 16) of them per walk over K (residual_dd_walks)
 static void residual_dd_multi_async(hipfact_handle* h, const DdCols& C, int nc_walk, double* partials, long long pstride) {
   if (nc_walk == 4)
-    residual_dd_multi_walks<4>(h, C, partials, pstride);
+    residual_dd_walks<4>(h, C, partials, pstride);
   else if (nc_walk == 16)
-    residual_dd_multi_walks<16>(h, C, partials, pstride);
+    residual_dd_walks<16>(h, C, partials, pstride);
   else
-    residual_dd_multi_walks<8>(h, C, partials, pstride);
+    residual_dd_walks<8>(h, C, partials, pstride);
 }
 
 // workspace: the blocked solve's, the blocks Z | dZ with the plan state, the small blocks with the handle; the handle

@@ -106,8 +106,9 @@ def _assert_accurate(name, Z, infos, fact):
 # ---- 1. the residual kernels, bit for bit --------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", ["par17_bounds", "par17_superset", "long", "generic"])
 def test_residual_bit_for_bit(fact, hip, name):
-    """every column of the blocked kernel against the single-column kernel on that column; nrhs 1, 5, 16, 17 in turn on
-    one factorisation, ld = N + 3"""
+    """every column of the 4, 8 and 16 columns-per-walk instances of the residual kernel against its one-column
+    instance (hipfact_residual_device) on that column - all of them one walk over K (kernels_k_walk.inc); nrhs 1, 5,
+    16, 17 in turn on one factorisation, ld = N + 3"""
     c = X.case(name)
     X.load_into(fact, c)
     assert fact.info("saddle") == (0.0 if name == "generic" else 1.0)
