@@ -699,8 +699,8 @@ int hipfact_get_info(const hipfact_handle* h, const char* name, double* value);
  * state to the host ("L", "SPf", "sitems", "y", "xhat", "ysol", "uvec", "dscale"; "mY": the m x 16 block of
  * the last pass of the blocked solve, pivot order; "res": the last residual of the single solve, caller's numbering;
  * "norms": the partial maxima (r, b, z per block, info "resid_blocks" blocks) its kernel left), or of one of the
- * active host plan's front arrays ("perm", "sn_c0", "sn_r", "sn_rowptr", "sn_rows", "sn_Loff", "late_cols", "sn_level", "dense_cols";
- * int32, except int64 for sn_rowptr and sn_Loff). */
+ * active host plan's front arrays ("perm", "sn_c0", "sn_r", "sn_rowptr", "sn_rows", "sn_Loff", "sn_Uoff", "late_cols", "sn_level",
+ * "dense_cols"; int32, except int64 for sn_rowptr, sn_Loff and sn_Uoff). */
 int hipfact_debug_copy(hipfact_handle* h, const char* name, void* out, size_t bytes);
 
 /* Host-only self-test of the worker pool behind the row dictionary's passes over K (no GPU needed): `callers` threads
@@ -727,6 +727,15 @@ int hipfact_debug_place_items(int nfronts, const int* counts, int classes, int* 
  * and, when tile_bounds is not NULL and nslice <= cap, writes the nslice + 1 tile bounds; HIPFACT_EINVAL for u < 0 or
  * a slice_rows the option "multi_slice_rows" would refuse.  The item lists of the sweeps are built from the same rule. */
 int hipfact_debug_multi_slices(int u, int slice_rows, int* tile_bounds /* cap + 1 values */, int cap);
+
+/* The Schur items of a front with `u` update rows, as a pure host function (no GPU needed; used by the tests): one per
+ * tile of the lower triangle of its update matrix, nt (nt + 1) / 2 with nt = ceil(u / edge).  leaf = 1: the tile edge
+ * (96) of the kernel that split levels of fronts without children run (environment HIPFACT_LEAF_SCHUR = 1 at
+ * hipfact_create, the default; 0: such levels keep the other kernel); leaf = 0: the edge (64) of the kernel of every
+ * other split level; a level of fronts without children with fewer than 256 items at the edge of 64 keeps that edge
+ * too.  HIPFACT_EINVAL for u < 0 or another `leaf`.  The item lists are built from the same rule; info
+ * "leaf_schur_levels" / "leaf_schur_items" count what the current plan launches at the edge of 96. */
+int hipfact_debug_schur_items(int u, int leaf);
 
 /* The stopping rule of hipfact_solve_device_extra as a pure host function (no GPU needed; used by the tests), applied
  * to a recorded sequence of norms: dn / zn hold npasses x nblocks values, pass by pass (nblocks 1 or 2, pass_cap >= 1,

@@ -205,6 +205,7 @@ static const OptionRow kOptions[] = {
     {nullptr, "HIPFACT_CHECK_LAUNCHES", FX_NONE, OPT_STORE(check_launches, v != 0.0), nullptr},
     {nullptr, "HIPFACT_SOL_SPLIT", FX_NONE, OPT_STORE(sol_split, v != 0.0), nullptr},
     {nullptr, "HIPFACT_IDX64", FX_NONE, OPT_STORE(idx64, v != 0.0), nullptr},
+    {nullptr, "HIPFACT_LEAF_SCHUR", FX_NONE, OPT_STORE(leaf_schur, v != 0.0), nullptr},
     {nullptr, "HIPFACT_XCD_CLASSES", FX_NONE, OPT_STORE(xcd_classes, std::max(1, std::min(XCD_CLASSES_MAX, (int)v))), nullptr},
     {nullptr, "HIPFACT_RESID_FROM_X", FX_NONE, OPT_STORE(resid_from_x, std::max(0, std::min(3, (int)v))), nullptr},
 };
@@ -260,6 +261,7 @@ int hipfact_debug_copy(hipfact_handle* h, const char* name, void* out, size_t by
   if (!strcmp(name, "sn_rowptr")) return host_copy(P.sn_rowptr);
   if (!strcmp(name, "sn_rows")) return host_copy(P.sn_rows);
   if (!strcmp(name, "sn_Loff")) return host_copy(P.sn_Loff);
+  if (!strcmp(name, "sn_Uoff")) return host_copy(P.sn_Uoff);
   if (!strcmp(name, "late_cols")) return host_copy(P.late_cols);
   if (!strcmp(name, "sn_level")) return host_copy(P.sn_level);
   if (!strcmp(name, "dense_cols")) return host_copy(P.dense_cols);
@@ -325,6 +327,13 @@ int hipfact_debug_place_items(int nfronts, const int* counts, int classes, int* 
     lost[i] = l[i];
   }
   return HIPFACT_OK;
+}
+
+// the Schur items of a front with u update rows (leaf_schur.h) as a pure host function: leaf = 1 at the tile edge of
+// k_leaf_schur, 0 at that of k_front_schur
+int hipfact_debug_schur_items(int u, int leaf) {
+  if (u < 0 || leaf < 0 || leaf > 1) return HIPFACT_EINVAL;
+  return schur_items(u, leaf ? LEAF_EDGE : 64);
 }
 
 // the row slices of the blocked solve (multi_slices.h) as a pure host function: what a front with u update rows becomes
@@ -519,6 +528,14 @@ int hipfact_get_info(const hipfact_handle* h, const char* name, double* value) {
   // the mode of the first residual of a checked solve on this plan, and the residual launches queued in either mode
   INFO("resid_blocks", resid_blocks(P)) INFO("resid_from_x", resid_from_x(h)) INFO("resid_queued_from_x", h->resid_queued_from_x) INFO("resid_queued_full", h->resid_queued_full)
   INFO("xcd_classes", h->xcd_classes) INFO("dealt_multi_item_fronts", h->dealt_multi) INFO("long_prod_segments", h->n_lprod)
+  if (!strcmp(name, "leaf_schur_levels") || !strcmp(name, "leaf_schur_items")) {
+    int levels;
+    long long items;
+    leaf_schur_counts(h, levels, items);
+    *value = !strcmp(name, "leaf_schur_levels") ? (double)levels : (double)items;
+    return HIPFACT_OK;
+  }
+  INFO("leaf_schur", h->leaf_schur)
   INFO("long_col_segments", h->n_cseg) INFO("idx32", h->idx32) INFO("prod_packed", h->prod_packed)
   INFO("active_bounds", h->maps_on ? h->n_bounds : 0)
   // (hipfact_refactor_device takes the caller's values as the structure's own, entry by entry)

@@ -48,6 +48,7 @@
 #include "kernel_types.h"
 #include "kernels_decl.h"
 #include "xcd_place.h"
+#include "leaf_schur.h"
 #include "multi_slices.h"
 #include "refine_cadence.h"
 #include "condest_rule.h"

@@ -28,6 +28,7 @@
 
 #include "device_types.h"
 #include "kernel_types.h"
+#include "leaf_schur.h"
 
 namespace hipfact {
 #include "kernels_common.inc"

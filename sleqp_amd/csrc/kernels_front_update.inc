@@ -460,6 +460,139 @@ __global__ __launch_bounds__(FB, 3) void k_front_schur(const FrontItem* __restri
                                nullptr, PullMore{more, U, inv, rel});
 }
 
+// ---- phase D of a split level whose fronts have no children (level 0 of a bushy tree): one (32 NB) x (32 NB) tile
+// (I, J) of U_s = -L21 D L21^T.  Nothing of the pull path is left, the tile is assigned.  The four waves stay 2 x 2, a
+// wave owns NB x NB blocks of 16 x 16 - per group of four pivots 2 NB operands from LDS feed NB^2 matrix instructions
+// (dev_schur_tile: 4 feed 4) - and a level of fronts with ~176 update rows has half the items of the 64-row tiles.
+// The strips are staged KCH pivots at a time and double-buffered in registers as in k_front_schur_pair: chunk n + 1 is
+// in flight while chunk n goes through LDS and the matrix cores.  A diagonal tile requests its rows once and writes
+// both strips from them.  The pivots are read from c.dd (LDS, wp doubles, zero from w on: k_leaf_schur).
+// Same bits as dev_schur_tile<.., assign>: every accumulator starts at +0.0 and takes one MFMA per aligned group of
+// four pivots in ascending order over all of w (KCH is a multiple of 4), a short last group padded with zero operands;
+// the operands are L21[j, k] * d_k, rounded once, and L21[i, k]; the entry stored is 0.0 - acc.
+// A 16 x 16 block wholly at or beyond u, or wholly above the diagonal, gets no matrix instruction and no store (bm).
+// LDS: dd[wp] | SI[KCH][LS] | SJ[KCH][LS], LS = 32 NB + 16 (leaf_schur.h).
+template <int NB, int KCH>
+__device__ __forceinline__ void dev_leaf_schur_tile(const FrontCtx& c, int I, int J) {
+  constexpr int E = 32 * NB, HB = 16 * NB, LS = E + 16;
+  constexpr int NV = E * KCH / FB;  // strip entries per thread and chunk
+  static_assert(E * KCH % FB == 0 && KCH % 4 == 0, "a chunk is a whole number of entries per thread and of pivot groups");
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int li = lane & 15, lk = lane >> 4;
+  const int w = c.w, r = c.r, u = c.u;
+  double* SI = c.A;             // [k][rows of I]
+  double* SJ = c.A + KCH * LS;  // [k][rows of J] * d_k
+  const bool diag = I == J;
+  const int wi = wave & 1, wj = wave >> 1;
+  const int i0 = E * I + HB * wi, j0 = E * J + HB * wj;  // first row and column of the wave's blocks
+  unsigned bm = 0;  // block (x, y): columns j0 + 16 x .., rows i0 + 16 y ..
+#pragma unroll
+  for (int x = 0; x < NB; ++x)
+#pragma unroll
+    for (int y = 0; y < NB; ++y)
+      if (i0 + 16 * y < u && j0 + 16 * x < u && i0 + 16 * y + 15 >= j0 + 16 * x) bm |= 1u << (NB * x + y);
+  d4_t acc[NB][NB];
+#pragma unroll
+  for (int x = 0; x < NB; ++x)
+#pragma unroll
+    for (int y = 0; y < NB; ++y) acc[x][y] = (d4_t){0.0, 0.0, 0.0, 0.0};
+  // Entries t and t + NH of this thread in every chunk share their row of the strip and lie KH pivots apart: one
+  // 32-bit offset serves both, behind two uniform bases (global) or with a constant in the instruction (LDS)
+  constexpr int NH = NV / 2, KH = FB * NH / E;
+  static_assert(NV % 2 == 0 && FB * NH % E == 0 && 2 * KH == KCH, "the two halves of a thread's entries share their rows");
+  int ek[NH], loff[NH];
+  unsigned goff[NH];
+  bool iok[NH], jok[NH];
+#pragma unroll
+  for (int t = 0; t < NH; ++t) {
+    const int e = tid + FB * t, k = e / E, row = e - E * k;
+    ek[t] = k;
+    goff[t] = (unsigned)(row + k * r);
+    loff[t] = k * LS + row;
+    iok[t] = E * I + row < u;
+    jok[t] = E * J + row < u;
+  }
+  const double* __restrict__ pI = c.P + w + E * I;
+  const double* __restrict__ pJ = c.P + w + E * J;
+  auto request = [&](int n, double (&vi)[NV], double (&vj)[NV]) {
+    const int kcn = min(KCH, w - n * KCH);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const double* __restrict__ qI = pI + (long long)(n * KCH + KH * h) * r;
+      const double* __restrict__ qJ = pJ + (long long)(n * KCH + KH * h) * r;
+#pragma unroll
+      for (int t = 0; t < NH; ++t) {
+        vi[t + NH * h] = (iok[t] && ek[t] + KH * h < kcn) ? qI[goff[t]] : 0.0;
+        if (!diag) vj[t + NH * h] = (jok[t] && ek[t] + KH * h < kcn) ? qJ[goff[t]] : 0.0;
+      }
+    }
+  };
+  auto chunk = [&](int n, const double (&vi)[NV], const double (&vj)[NV]) {
+    const int kc0 = n * KCH, kcn = min(KCH, w - kc0);
+    __syncthreads();  // the previous chunk / tile has finished reading the strips (first chunk: the pivots are in LDS)
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int t = 0; t < NH; ++t) {  // (pivots from kcn on: zero entries times dd = 0.0, the padding of the last group)
+        SI[loff[t] + KH * h * LS] = vi[t + NH * h];
+        SJ[loff[t] + KH * h * LS] = (diag ? vi[t + NH * h] : vj[t + NH * h]) * c.dd[kc0 + ek[t] + KH * h];
+      }
+    __syncthreads();
+    if (bm) {
+      const int ng = (kcn + 3) >> 2;
+      for (int g = 0; g < ng; ++g) {
+        const int ko = (4 * g + lk) * LS + li;
+        double a[NB], b[NB];
+#pragma unroll
+        for (int x = 0; x < NB; ++x) a[x] = SJ[ko + HB * wj + 16 * x];
+#pragma unroll
+        for (int y = 0; y < NB; ++y) b[y] = SI[ko + HB * wi + 16 * y];
+#pragma unroll
+        for (int x = 0; x < NB; ++x)
+#pragma unroll
+          for (int y = 0; y < NB; ++y)
+            if (bm & (1u << (NB * x + y))) acc[x][y] = MFMA_F64(a[x], b[y], acc[x][y]);
+      }
+    }
+  };
+  {
+    double ai[NV], aj[NV], bi[NV], bj[NV];
+    const int nc = (w + KCH - 1) / KCH;
+    request(0, ai, aj);
+    for (int n = 0; n < nc; n += 2) {
+      if (n + 1 < nc) request(n + 1, bi, bj);
+      chunk(n, ai, aj);
+      if (n + 2 < nc) request(n + 2, ai, aj);
+      if (n + 1 < nc) chunk(n + 1, bi, bj);
+    }
+  }
+  // acc[x][y][q] = update of U(i = i0 + 16 y + li, j = j0 + 16 x + lk + 4 q)
+#pragma unroll
+  for (int x = 0; x < NB; ++x)
+#pragma unroll
+    for (int y = 0; y < NB; ++y)
+      if (bm & (1u << (NB * x + y))) {
+        const int i = i0 + 16 * y + li;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int j = j0 + 16 * x + lk + 4 * q;
+          if (i < u && j < u && i >= j) c.Us[i + (long long)j * u] = 0.0 - acc[x][y][q];
+        }
+      }
+}
+
+// part = (I << 16) | J in tiles of LEAF_EDGE rows
+__global__ __launch_bounds__(FB, 3) void k_leaf_schur(const FrontItem* __restrict__ items, double* __restrict__ L,
+                                                       double* __restrict__ U) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const FrontItem& S = items[blockIdx.x];
+  const FrontCtx c = make_ctx(S, L, U, lds);
+  // the pivots of the front go through LDS once
+  for (int t = threadIdx.x; t < c.wp; t += FB) c.dd[t] = (t < c.w) ? c.P[t + (long long)t * c.r] : 0.0;
+  dev_leaf_schur_tile<LEAF_NB, LEAF_KCH>(c, S.part >> 16, S.part & 0xffff);
+}
+
 
 // ---- dense chains, two fronts per trailing update.  b is the second front of a pair (a = its only child, g = a's only
 // child, rows nested exactly): tile (I, J) of U_b = U_g (shifted by w_a + w_b) - L21_a D_a L21_a^T (rows shifted by

@@ -433,11 +433,18 @@ static int upload_plan(hipfact_handle* h) {
           li.nD = (int)(nt * (nt + 1) / 2);
         }
       }
+      // A level whose fronts have no children (level 0 of a bushy tree): tiles of LEAF_EDGE rows for k_leaf_schur
+      // (if it has enough of the 64-row tiles to give every CU one: LEAF_MIN_TILES)
+      long long tiles64 = 0;
+      for (int s : order) tiles64 += schur_items(P.sn_r[s] - (P.sn_c0[s + 1] - P.sn_c0[s]), 64);
+      li.leaf = mch == 0 && !li.compactD && h->leaf_schur && tiles64 >= LEAF_MIN_TILES;
+      if (li.leaf) li.lds_schur = leaf_schur_lds(wp);
+      const int edge = li.leaf ? LEAF_EDGE : 64;
       for (int s : order) {
         if (li.compactD) break;
         const int u = P.sn_r[s] - (P.sn_c0[s + 1] - P.sn_c0[s]);
-        const int nt = (u + 63) / 64;
-        per_front.push_back(nt * (nt + 1) / 2);
+        const int nt = schur_tile_rows(u, edge);
+        per_front.push_back(schur_items(u, edge));
         for (int I = 0; I < nt; ++I)
           for (int J = 0; J <= I; ++J) {
             plain.push_back(item(s, (I << 16) | J));

@@ -130,13 +130,27 @@ static void place_front_end(hipfact_handle* h) {
   const Plan& P = h->plan;
   h->rs_grid = place_rows(P.m, P.Ar_ptr.data(), arena_fill_bytes(P), h->xcd_classes, h->rs_place);
 }
+// levels of the current plan whose Schur update is a launch of k_leaf_schur (those below the dataflow launch), and
+// their items
+static inline void leaf_schur_counts(const hipfact_handle* h, int& levels, long long& items) {
+  levels = 0;
+  items = 0;
+  const int below = dataflow_factor(h) ? std::min(h->ftop_level, h->plan.nlevels) : h->plan.nlevels;
+  for (int l = 0; l < below && l < (int)h->levels.size(); ++l)
+    if (h->levels[l].split && h->levels[l].leaf && h->levels[l].nD > 0) {
+      ++levels;
+      items += h->levels[l].nD;
+    }
+}
 // the Schur items of a level whose pivot blocks and panels are done (CH: a chain level)
 template <bool CH>
 static void launch_schur(hipfact_handle* h, const LevelInfo& li, int pull) {
   h->prof.next_fl = li.schur_flops;
   if (li.nD <= 0) return;
   const FrontItem* fit = h->d_fitems.as<FrontItem>() + li.itD;
-  if (li.pair == 2)
+  if (li.leaf)
+    LAUNCH(PC_FACTOR_D, k_leaf_schur, dim3(li.nD), dim3(FB), li.lds_schur, fit, h->d_L.as<double>(), h->d_U.as<double>());
+  else if (li.pair == 2)
     LAUNCH(PC_FACTOR_D, k_front_schur_pair, dim3(li.nD), dim3(FB), li.lds_schur, fit, h->d_L.as<double>(),
            h->d_U.as<double>(), li.pd);
   else

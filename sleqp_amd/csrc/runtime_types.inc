@@ -79,6 +79,7 @@ struct LevelInfo {
   int pair = 0;            // dense chain, two fronts per trailing update: 1 = first front of a pair (partial update), 2 = second
   PairDesc pd;             // pair == 2: the first front's panel and the grandchild's update matrix
   double schur_flops_full = 0.0, pair_flops_done = 0.0;
+  bool leaf = false;  // the level's fronts have no children: its Schur items are tiles of LEAF_EDGE rows for k_leaf_schur (leaf_schur.h)
   bool compactD = false;  // the level's Schur workgroups share ONE item (single front) and take their tile from the block index
   double schur_flops = 0.0;  // fp64 flops of the level's Schur updates (structural: u (u + 1) w per front)
   // single-front level of a dense chain below the dataflow launch: its pivot and panel items as one small dataflow
@@ -389,6 +390,7 @@ struct hipfact_handle : PlanState, SingleSolveMemo {
   int resid_from_x = 3;
   double* x_res_out = nullptr;  // set around the first pass of a checked solve (solve_enqueue): where the x update leaves it
   long resid_queued_from_x = 0, resid_queued_full = 0;  // saddle residual launches queued (or captured) in either mode
+  bool leaf_schur = true;     // HIPFACT_LEAF_SCHUR: split levels of fronts without children run their Schur update on tiles of LEAF_EDGE rows (k_leaf_schur; 0: the 64-row tiles of k_front_schur)
   int xcd_classes = 8;        // HIPFACT_XCD_CLASSES (1-16): classes the rows of k_row_scale and the items of the per-level panel / Schur launches are dealt to (1: plain order)
   int factor_top_max = 160;   // levels with at most this many fronts join the single-launch top-of-tree factorisation (0: off)
   int factor_top_levels = 1 << 20;  // at most this many levels in the single-launch top-of-tree factorisation (tests)
