@@ -355,6 +355,92 @@ typedef struct hipfact_cond_info {
 int hipfact_condition_estimate(hipfact_handle* h, int equilibrated, hipfact_cond_info* info /* nullable */,
                                double* d_witness /* nullable, device, N doubles */);
 
+/* ---- null space of a rank-deficient K and minimum-norm least-squares solves ------------------------------------
+ * A working set with dependent rows is factored with every pivot of A A^T shifted by static_pivot_delta
+ * (hipfact_last_warning).  In the equilibrated space that factor is the exact inverse of M^ = K^ - delta E, K^ = D K D,
+ * E the 0 / 1 diagonal of the rows the shift acts on (the multiplier rows, but for the multipliers of active bounds
+ * where the plan eliminates them): a plain blocked pass D^-1 K^-1 D^-1 (E X) is a step of inverse iteration on the
+ * pencil (K^, E) and multiplies every vector of null(K^) by exactly -1 / delta, whatever rows it has weight on.
+ * hipfact_nullspace returns an orthonormal (2-norm) basis Z of null(K) in the caller's numbering - which combinations
+ * of rows are dependent -, for the matrix residuals are taken against, inactive rows of a superset plan left out.
+ * Column j is written at d_Z + j ld for j < dim; the doubles between N and ld and the columns from dim on are never
+ * written.  The rule (sleqp_amd/csrc/nullspace_rule.h), with a block of t = min(16, multiplier rows) columns:
+ *   no shift is active (also: generic mode): REGULAR, no pass.
+ *   X[i][j] = s(i, j) of hipfact_condition_estimate for multiplier rows i >= n and j < t, 0 elsewhere (null(K) lies in
+ *   {x = 0}).  Then for k = 1 .. 4:
+ *     1. Y = D^-1 K^-1 D^-1 (E X): ONE plain blocked pass between exact scalings (no refinement, no verdict; the row
+ *        slices of "multi_slice_rows").  A plan state with the low-rank dense-column correction (dense_mode 2 with
+ *        dense columns) takes the block's t columns through plain single solves instead, counted by
+ *        "multi_single_cols": hipfact_set_matrix and hipfact_assemble_kkt factor a rank-deficient working set again
+ *        without the treatment before the shift ("dense_fallbacks"), but a stalled solve behind
+ *        hipfact_refactor_device shifts the plan as it stands.
+ *     2. every column scaled to max-abs 1, then classical Gram-Schmidt column by column with three projection passes,
+ *        coefficients and lengths on the device; a column whose remainder behind the first projection is not above
+ *        2^-40 of its length in front of it is dead: zeroed and left out of what follows.
+ *     3. T = Q^T (K^ Q) with K^ Q = D (K (D Q)) by the walk over K, symmetrised on the host, T = V diag(theta) V^T by
+ *        cyclic Jacobi; Q <- Q V, the columns by |theta| ascending.
+ *     4. rho_j = ||K^ q_j||_inf / (||K^||_1 ||q_j||_inf) and orth = max |Q^T Q - I|, measured on the rotated block.  A
+ *        vector is null with rho <= 2^-36 and separated with rho >= 2^-26.  The verdict falls in the first iteration
+ *        k >= 2 in which every live column is one or the other, the null ones in front, and orth <= 2^-40; else X = Q.
+ *   No verdict behind the 4th iteration: UNRESOLVED, dim 0.  With dim > 0 the x halves of the null columns are set to
+ *   exactly 0 and the columns orthonormalised and measured again (the bounds must still hold, else UNRESOLVED); then
+ *   Z = D Q_null, orthonormalised once more, orth measured on Z as well.
+ * 2^-36 lies above what rounding alone produces in a computed null vector (c N 2^-53, N <= 1.5e5) and 2^-26 is the order of
+ * the shift: a direction of K^ whose eigenvalue lies below the shift cannot be told from a null direction by the shifted
+ * factor - such a K is UNRESOLVED.  The thresholds are constants of the rule.
+ * The call BLOCKS, with the contract of hipfact_condition_estimate: on entry it does what hipfact_check does;
+ * HIPFACT_ESTATE before a factorisation; HIPFACT_EINVAL for ld < N with a non-NULL d_Z; it does not become "the last
+ * solve" - hipfact_solution* still return the earlier single solve, and a single solve issued afterwards gives the bits
+ * it would have given without this call.  A failed workspace allocation returns
+ * HIPFACT_ENOMEM and leaves the handle usable.  The same handle state gives the same bits on every call: every sum has a
+ * fixed order.  The result is kept per factorisation and shift: a second call costs no pass; a new factorisation or a
+ * change of the shift voids it.  Cost: iterations x (one plain blocked pass + two walks over K + 100 small launches of
+ * the orthonormalisation + two host synchronisations), 2 iterations on every system tried, plus three measurements of the
+ * final block (EXPERIMENTS.md, "Null space and deflated solves").
+ * Info: "null_calls" runs that asked for passes, "null_blocks" passes they asked for, "null_dim" / "null_status" of the
+ * current factorisation (-1: not computed), "deflated_solves". */
+enum { HIPFACT_NULL_REGULAR = 0,    /* no static-pivot shift is active: K is regular as factored; no pass is run */
+       HIPFACT_NULL_FOUND = 1,      /* dim in 1..15, certified: every other Ritz vector of the block is separated */
+       HIPFACT_NULL_NONE = 2,       /* a shift is active but no vector of the block is null (dim 0) */
+       HIPFACT_NULL_BLOCK_FULL = 3, /* all columns of the block are null: dim >= 16, or >= the number of multipliers;
+                                       Z holds what was found, not certified complete */
+       HIPFACT_NULL_UNRESOLVED = 4  /* after the last iteration some Ritz vector is neither null nor separated, or the
+                                       block is not orthonormal to the rule's bound */ };
+typedef struct hipfact_null_info {
+  int dim, status, iterations, blocks;  /* blocks: plain blocked passes asked for */
+  double max_null_rho;   /* largest rho among the accepted vectors (0 with dim 0) */
+  double min_other_rho;  /* smallest rho among the rest (+inf when none) */
+  double orth;           /* max |Q^T Q - I| of the final block */
+} hipfact_null_info;
+int hipfact_nullspace(hipfact_handle* h, hipfact_null_info* info /* nullable */, double* d_Z /* nullable, device */,
+                      long long ld /* >= N */);
+
+/* The deflated solve: z = K^+ b, the minimum-norm least-squares solution of K z = b.  K is symmetric, so range(K) is the
+ * orthogonal complement of null(K): this is the loop of hipfact_solve_device_extra (the same rule, info and double-double
+ * residual) with three projections by the basis Z of hipfact_nullspace - b~ = b - Z (Z^T b) once, r <- r - Z (Z^T r)
+ * behind every residual, z <- z - Z (Z^T z) behind the first solve and behind every update.  The final residual is taken
+ * against b~ and judged as the single solve's: b~ is consistent, so a right-hand side outside the range of K is
+ * HIPFACT_OK.  *defect = ||Z Z^T b||_inf / ||b||_inf, the part of b the solution does not answer (0 for b = 0).  The null
+ * space is computed on first use.  Status REGULAR or NONE: the plain extra-precise solve, defect 0.  BLOCK_FULL or
+ * UNRESOLVED: HIPFACT_ESINGULAR with a message that names the status.  Z^T v is up to 15 dots with fixed-order partials,
+ * the update the next launch.  Otherwise the contract of hipfact_solve_device_extra holds word for word (blocking,
+ * overlap, "not the last solve", NaN / Inf right-hand sides; its "extra_*" counters count these solves too).
+ * hipfact_solve_deflated: the same for host vectors.
+ * Option "deflate_singular" (hipfact_set_option; the feature's own, kept out of the table below; readable through
+ * hipfact_get_info): 0 (default) nothing changes anywhere.  1: a single solve that ends with the out-of-range verdict on
+ * a statically pivoted factor - at the blocking points of hipfact_check, hipfact_solution, hipfact_solution_view,
+ * hipfact_solve_dense, hipfact_solve_sparse that would return HIPFACT_ESINGULAR for it - is redone through the deflated
+ * solve from the preserved right-hand side into the same solution vector: it becomes the last solution, the call
+ * returns HIPFACT_OK, and hipfact_last_warning says that the minimum-norm least-squares solution was returned, with its
+ * defect.  A right-hand side that was not preserved (an in-place device solve without a kept copy) leaves the error
+ * standing (the solution vector as the refused solve left it), and so does a null space that is not FOUND.  "last_omega"
+ * and "last_iters" keep describing the refused solve.  Anything else is HIPFACT_EINVAL.  The Krylov and LSQR loops and
+ * the columns of a blocked solve are not touched: the rescue applies inside hipfact_check and hipfact_solution* only. */
+int hipfact_solve_device_deflated(hipfact_handle* h, const double* d_rhs, double* d_sol,
+                                  hipfact_extra_info* info /* nullable */, double* defect /* nullable, host */);
+int hipfact_solve_deflated(hipfact_handle* h, const double* rhs, double* sol, hipfact_extra_info* info /* nullable */,
+                           double* defect /* nullable */);
+
 /* Blocks until the queued work has finished and reports what the asynchronous
  * entry points above could not: a singular / rank-deficient factorisation
  * (HIPFACT_ESINGULAR), a solve whose iterative refinement stalled far above its
@@ -765,6 +851,17 @@ int hipfact_debug_condest_dense(int N, const double* A, long long ld, hipfact_co
  * h[ind_best], the history indices in front of the best unused index, the number of unused candidates and 16 of them.
  * HIPFACT_EINVAL when the records end before the rule does (N > 16 needs up to 5). */
 int hipfact_debug_condest_recorded(int N, int nrecords, const double* records, hipfact_cond_info* info);
+/* The rule of hipfact_nullspace (sleqp_amd/csrc/nullspace_rule.h) with dense products, no GPU needed; used by the
+ * tests.  Khat: the equilibrated K^ (N x N, column-major, ld >= N) with n0 variables in front of the multiplier rows;
+ * Minv: the inverse of K^ - delta diag(0, I), same layout and ld - it stands in for the blocked pass.  D = I: Z (N x 16,
+ * leading dimension N; the first dim columns are written) is a basis of null(K^).  Every sum in row order.
+ * HIPFACT_EINVAL for N <= 0, n0 outside [0, N], ld < N or NULL matrices. */
+int hipfact_debug_nullspace_dense(int N, int n0, const double* Khat, const double* Minv, long long ld,
+                                  hipfact_null_info* info /* nullable */, double* Z /* N x 16, nullable */);
+/* The cyclic Jacobi routine of that rule on a symmetric t x t matrix A (row-major, t <= 16; symmetrised first):
+ * theta[c] and column c of V (row-major t x t) are the eigenpairs, by |theta| ascending.  Returns the sweeps taken, or
+ * HIPFACT_EINVAL for t outside [1, 16] or a NULL array. */
+int hipfact_debug_nullspace_jacobi(int t, const double* A, double* theta, double* V);
 /* The refinement cadence of the single solve as a pure host function (no GPU needed; used by the tests): how many
  * correction passes the solve graphs carry, which solves take a residual, and which leave their verdict to the next tree
  * launch.  A script of events runs through the transitions the runtime calls, on one plan of one fresh handle.

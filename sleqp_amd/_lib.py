@@ -29,6 +29,8 @@ SYMBOLS = [
     "hipfact_solve_dense", "hipfact_solution", "hipfact_solution_view", "hipfact_condition", "hipfact_refactor_device",
     "hipfact_solve_device", "hipfact_solve_device_multi", "hipfact_solve_multi",
     "hipfact_condition_estimate", "hipfact_debug_condest_dense", "hipfact_debug_condest_recorded",
+    "hipfact_nullspace", "hipfact_solve_device_deflated", "hipfact_solve_deflated", "hipfact_debug_nullspace_dense",
+    "hipfact_debug_nullspace_jacobi",
     "hipfact_solve_device_extra", "hipfact_solve_extra", "hipfact_residual_device", "hipfact_debug_extra_rule", "hipfact_debug_dd_residual",
     "hipfact_solve_device_multi_extra", "hipfact_solve_multi_extra", "hipfact_residual_device_multi", "hipfact_debug_multi_extra_schedule",
     "hipfact_solution_device", "hipfact_synchronize", "hipfact_check", "hipfact_stream",
@@ -93,6 +95,12 @@ def load() -> C.CDLL:
         lib.hipfact_condition_estimate.argtypes = [vp, ci, vp, vp]
         lib.hipfact_debug_condest_dense.argtypes = [ci, vp, C.c_longlong, vp, vp, vp, ci]
         lib.hipfact_debug_condest_recorded.argtypes = [ci, ci, vp, vp]
+    if hasattr(lib, "hipfact_nullspace"):
+        lib.hipfact_nullspace.argtypes = [vp, vp, vp, C.c_longlong]
+        lib.hipfact_solve_device_deflated.argtypes = [vp, vp, vp, vp, C.POINTER(cd)]
+        lib.hipfact_solve_deflated.argtypes = [vp, vp, vp, vp, C.POINTER(cd)]
+        lib.hipfact_debug_nullspace_dense.argtypes = [ci, ci, vp, vp, C.c_longlong, vp, vp]
+        lib.hipfact_debug_nullspace_jacobi.argtypes = [ci, vp, vp, vp]
     lib.hipfact_solution_device.argtypes = [vp, C.POINTER(vp)]
     lib.hipfact_synchronize.argtypes = [vp]
     lib.hipfact_check.argtypes = [vp]

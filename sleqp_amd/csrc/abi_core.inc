@@ -467,6 +467,7 @@ int hipfact_solve_device(hipfact_handle* h, const double* d_rhs, double* d_sol) 
 static int solution_range(hipfact_handle* h, double* out, const double** view, int begin, int end, const char* who) {
   int rc = enter(h);
   if (rc) return rc;
+  const RescueScope rescue(h);  // (option "deflate_singular": a refused solve may be rescued here)
   if (view) *view = nullptr;
   if (!h->solved && h->N_ext > 0) {
     h->error = std::string(who) + ": no solve has been performed";
@@ -564,6 +565,7 @@ int hipfact_check(hipfact_handle* h) {
   int rc = enter(h);
   if (rc) return rc;
   if (!h->have_plan) return HIPFACT_OK;
+  const RescueScope rescue(h);  // (option "deflate_singular": a refused solve may be rescued here)
   if ((rc = finish_solve(h))) return rc;
   const bool was_solve = h->solved && h->last_b && h->last_z;
   bool switched = false;

@@ -229,6 +229,11 @@ int hipfact_set_option(hipfact_handle* h, const char* name, double value) {
     const int rc = condest_set_option(h, name, value, known);
     if (known) return rc;
   }
+  {  // ... and the rescue of an out-of-range single solve (runtime_nullspace.inc)
+    bool known = false;
+    const int rc = nullspace_set_option(h, name, value, known);
+    if (known) return rc;
+  }
   for (const OptionRow& row : kOptions) {
     if (!row.name || strcmp(name, row.name)) continue;
     const int changed = row.set(h, value);
@@ -503,6 +508,9 @@ int hipfact_get_info(const hipfact_handle* h, const char* name, double* value) {
   INFO("multi_passes", h->multi_passes) INFO("multi_single_cols", h->multi_single_cols) INFO("multi_failed_col", h->multi_failed_col)
   INFO("multi_sliced_fronts", h->mitems_for < 0 ? 0 : h->n_mcut) INFO("multi_slice_items", h->mitems_for < 0 ? 0 : h->n_mslices) INFO("multi_slice_rows", h->multi_slice_rows)
   INFO("cond_estimates", h->cond_estimates) INFO("cond_blocks", h->cond_blocks) INFO("cond_last", h->cond_last) INFO("condition_estimate", h->condition_estimate)
+  INFO("null_calls", h->null_calls) INFO("null_blocks", h->null_blocks) INFO("deflated_solves", h->deflated_solves) INFO("deflate_singular", h->deflate_singular)
+  INFO("null_dim", (h->null_for_factor == h->num_factor && h->null_for_delta == h->reg_delta) ? h->null_res.dim : -1)
+  INFO("null_status", (h->null_for_factor == h->num_factor && h->null_for_delta == h->reg_delta) ? h->null_res.status : -1)
   INFO("extra_solves", h->extra_solves) INFO("extra_passes", h->extra_passes) INFO("extra_last_status", h->extra_last_status)
   INFO("extra_multi_solves", h->extra_multi_solves) INFO("extra_multi_cols", h->extra_multi_cols) INFO("extra_multi_passes", h->extra_multi_passes)
   INFO("num_solve", h->num_solve) INFO("num_refined", h->solve_cad.num_refined) INFO("refine_adaptive", h->refine_adaptive)

@@ -5,7 +5,7 @@
 // state.  All numerics run on the device; there is no CPU fallback: without a
 // usable GPU hipfact_create fails with HIPFACT_EDEVICE.
 //
-// The host translation unit (the kernels are compiled separately: kernels_factor.hip / kernels_solve.hip / kernels_extra.hip, declared in the
+// The host translation unit (the kernels are compiled separately: kernels_factor.hip / kernels_solve.hip / kernels_extra.hip / kernels_nullspace.hip, declared in the
 // generated kernels_decl.h), split by role:
 //   runtime_types.inc   buffers, plan state, the handle          abi_core.inc         create .. solution (SleqpFact)
 //   runtime_plan.inc    upload of a plan, work items             abi_working_set.inc  superset plans, assemble_kkt
@@ -16,6 +16,7 @@
 //   runtime_extra.inc   extra-precise solve (dd_arith.h)         abi_extra.inc        hipfact_solve[_device]_extra, _residual_device
 //   runtime_multi_extra.inc blocked extra-precise solve         abi_multi_extra.inc  hipfact_solve[_device]_multi_extra, _residual_device_multi
 //   runtime_condest.inc 1-norm condition estimate (condest_rule.h) abi_condest.inc      hipfact_condition_estimate, _debug_condest_*
+//   runtime_nullspace.inc null space of a rank-deficient K, deflated solve (nullspace_rule.h) abi_nullspace.inc hipfact_nullspace, hipfact_solve[_device]_deflated
 //   refine_cadence.h    refinement cadence of the single solve: passes in the graph, residual checks, deferred verdicts
 //                       (pure host rules, like xcd_place.h and multi_slices.h)
 #include <hip/hip_runtime.h>
@@ -52,6 +53,7 @@
 #include "multi_slices.h"
 #include "refine_cadence.h"
 #include "condest_rule.h"
+#include "nullspace_rule.h"
 #include "dd_arith.h"
 
 #include "runtime_types.inc"
@@ -61,6 +63,7 @@
 #include "runtime_extra.inc"
 #include "runtime_multi_extra.inc"
 #include "runtime_condest.inc"
+#include "runtime_nullspace.inc"
 
 extern "C" {
 #include "abi_core.inc"
@@ -68,6 +71,7 @@ extern "C" {
 #include "abi_extra.inc"
 #include "abi_multi_extra.inc"
 #include "abi_condest.inc"
+#include "abi_nullspace.inc"
 #include "abi_working_set.inc"
 #include "abi_krylov.inc"
 #include "abi_options.inc"

@@ -136,9 +136,20 @@ static int extra_workspace(hipfact_handle* h) {
   return HIPFACT_OK;
 }
 
+// The projections of the deflated solve (runtime_nullspace.inc): v <- v - Z (Z^T v) for the orthonormal basis Z of
+// null(K), dim columns of N_ext doubles; pmax (nullable, device): max |Z Z^T v| and max |v| in front of the update
+struct Deflation {
+  int dim;
+  const double* Z;
+};
+static void deflate_async(hipfact_handle* h, const Deflation& F, double* v, double* pmax);
+
 // The loop on the handle's own vectors; b has been copied into the workspace.  Returns HIPFACT_EINTERNAL with
 // `switched` set when a dataflow wait ran out and the handle has moved to the per-level launches.
-static int extra_loop(hipfact_handle* h, long solves_kept, hipfact_extra_info& out, RefineCtl& final_ctl, bool& switched) {
+// defl (the deflated solve; null: none): b is the deflated right-hand side; every residual is projected behind its
+// walk and z behind the first solve and behind every update, so that what leaves is orthogonal to null(K).
+static int extra_loop(hipfact_handle* h, long solves_kept, hipfact_extra_info& out, RefineCtl& final_ctl, bool& switched,
+                      const Deflation* defl = nullptr) {
   const size_t N = (size_t)h->N_ext;
   const Plan& P = h->plan;
   double* const b = h->d_xvec.as<double>();
@@ -159,6 +170,10 @@ static int extra_loop(hipfact_handle* h, long solves_kept, hipfact_extra_info& o
   R.cap = h->refine_max;
   int rc = plain_solve(b, z);
   if (rc) return rc;
+  if (defl) {
+    Turn turn(h);
+    deflate_async(h, *defl, z, nullptr);
+  }
   const int split = P.saddle ? P.n : h->N_ext;
   const int nmax = nblocks((long long)N, g_maxabs_cap);
   const DdCols one = dd_cols(b, (long long)N, z, (long long)N, r, (long long)N, 1u);  // the norms' column set: slot 0
@@ -166,6 +181,7 @@ static int extra_loop(hipfact_handle* h, long solves_kept, hipfact_extra_info& o
     {
       Turn turn(h);
       residual_dd_async(h, b, z, r, nullptr);
+      if (defl) deflate_async(h, *defl, r, nullptr);
     }
     if ((rc = plain_solve(r, dz))) return rc;
     {
@@ -181,6 +197,7 @@ static int extra_loop(hipfact_handle* h, long solves_kept, hipfact_extra_info& o
     if (extra_rule_step(R, dn, zn)) {
       Turn turn(h);
       LAUNCH(PC_AXPY, k_axpy, dim3(nblocks((long long)N)), dim3(FB), 0, (long long)N, 1.0, dz, z, nullptr);
+      if (defl) deflate_async(h, *defl, z, nullptr);
     }
   }
   if (R.status < 0) R.status = HIPFACT_EXTRA_PASS_LIMIT;  // (refine_max = 0: the plain solve, unjudged)
@@ -204,7 +221,10 @@ static int extra_loop(hipfact_handle* h, long solves_kept, hipfact_extra_info& o
   return HIPFACT_OK;
 }
 
-static int solve_extra_device(hipfact_handle* h, const double* d_rhs, double* d_sol, hipfact_extra_info* info) {
+// defl / defect (the deflated solve; null: the plain one): the right-hand side is deflated in the workspace,
+// *defect = ||Z Z^T b||_inf / ||b||_inf (0 for b = 0)
+static int solve_extra_device(hipfact_handle* h, const double* d_rhs, double* d_sol, hipfact_extra_info* info,
+                              const Deflation* defl = nullptr, double* defect = nullptr) {
   const size_t N = (size_t)h->N_ext;
   int rc = extra_workspace(h);
   if (rc) return rc;
@@ -220,7 +240,11 @@ static int solve_extra_device(hipfact_handle* h, const double* d_rhs, double* d_
              ? HIPFACT_OK
              : HIPFACT_EDEVICE;
     if (rc == HIPFACT_OK) rc = hipMemsetAsync(h->d_xctl.p, 0, sizeof(RefineCtl), h->stream) == hipSuccess ? HIPFACT_OK : HIPFACT_EDEVICE;
-    if (rc == HIPFACT_OK) rc = extra_loop(h, keep.factor.solves_this_factor, out, c, switched);
+    if (rc == HIPFACT_OK && defl) {
+      Turn turn(h);
+      deflate_async(h, *defl, h->d_xvec.as<double>(), static_cast<double*>(h->h_nout_dev));
+    }
+    if (rc == HIPFACT_OK) rc = extra_loop(h, keep.factor.solves_this_factor, out, c, switched, defl);
     if (!(rc == HIPFACT_EINTERNAL && switched && attempt == 0)) break;
     h->error.clear();  // (the per-level launches from here on: the same call once more)
   }
@@ -232,6 +256,10 @@ static int solve_extra_device(hipfact_handle* h, const double* d_rhs, double* d_
   keep.put_back(h);
   if (rc == HIPFACT_EDEVICE && h->error.empty()) h->error = "hipfact_solve_device_extra: device error";
   if (rc) return rc;
+  if (defl && defect) {  // (the pair in front of the pinned block: written by the projection of b, read behind the loop's synchronisations)
+    const double* pm = h->h_nout.as<double>();
+    *defect = pm[1] == 0.0 ? 0.0 : pm[0] / pm[1];
+  }
   h->extra_solves++;
   h->extra_passes += out.passes;
   h->extra_last_status = out.status;

@@ -913,6 +913,14 @@ static bool vtable_can_retry(const hipfact_handle* h);
 static int vtable_retry_exact(hipfact_handle* h);
 static bool static_pivot_applies(const hipfact_handle* h);
 static int static_pivot_retry(hipfact_handle* h, int rc);
+static int deflated_rescue(hipfact_handle* h, int rc);  // (runtime_nullspace.inc: option "deflate_singular")
+struct RescueScope {  // the entry points at which a refused single solve may be rescued
+  hipfact_handle* h;
+  explicit RescueScope(hipfact_handle* h_) : h(h_) { ++h->rescue_scope; }
+  ~RescueScope() { --h->rescue_scope; }
+  RescueScope(const RescueScope&) = delete;
+  RescueScope& operator=(const RescueScope&) = delete;
+};
 
 // The verdict on a refinement that has ended, for the single solve (finish_solve) and for every column of the blocked
 // one (multi_block).  accepted includes a non-finite solve (status 2): that one is the caller's case.  The two failures
@@ -999,6 +1007,10 @@ static int finish_solve(hipfact_handle* h, bool* continued = nullptr, bool synce
   }
   if (v == Verdict::accepted) return HIPFACT_OK;
   set_verdict_error(h, v, c);
+  // (option "deflate_singular", off by default: the minimum-norm least-squares solution instead of the error)
+  // only at the blocking points of hipfact_check and hipfact_solution*: the Krylov and LSQR loops and the columns of a
+  // blocked solve come through here too and keep their error
+  if (v == Verdict::out_of_range && h->deflate_singular && h->rescue_scope > 0) return deflated_rescue(h, HIPFACT_ESINGULAR);
   return HIPFACT_ESINGULAR;
 }
 

@@ -261,6 +261,10 @@ struct PlanState : FactorMemo {
   // of D as doubles (d_cblk); two generations of sign words (d_cwords); the `used` bytes (d_cused).  They live with the
   // plan because the single-solve route of a dense_mode = 2 plan captures graphs on the blocks' columns.
   DevBuf d_cblk, d_cwords, d_cused;
+  // null space (runtime_nullspace.inc), N_ext each: a third N x 16 block, a vector of zeros and the mask of the shifted rows (d_nblk; the other two
+  // blocks and the diagonal of D are the condition estimate's), the basis Z of the current factorisation, up to 15
+  // columns (d_nullZ).  Allocated by the first such call of the state.
+  DevBuf d_nblk, d_nullZ;
 
   PlanState() = default;
   PlanState(PlanState&&) = default;
@@ -506,6 +510,20 @@ struct hipfact_handle : PlanState, SingleSolveMemo {
   long cond_estimates = 0, cond_blocks = 0;
   double cond_last = 0.0;
   std::vector<int> cond_history;  // the index history of the last estimate, -1 behind it (hipfact_debug_copy "cond_history")
+  // null space and deflated solves (runtime_nullspace.inc): the partials of its sums and maxima and the lengths of the
+  // orthonormalisation, the pinned block the host reads behind a synchronisation; the result of the factorisation
+  // number null_for_factor with the shift null_for_delta (the cache: another factorisation or another shift voids it);
+  // the option "deflate_singular"; counters of hipfact_get_info (the host entry point stages in d_xhost)
+  DevBuf d_npart;
+  PinBuf h_nout;
+  void* h_nout_dev = nullptr;
+  long null_for_factor = -1;
+  double null_for_delta = 0.0;
+  hipfact::NullResult null_res;
+  int deflate_singular = 0;
+  bool in_deflated = false;  // (a deflated solve is running: its plain solves are not rescued themselves)
+  int rescue_scope = 0;      // > 0 inside hipfact_check and hipfact_solution*: the only places the rescue applies (RescueScope)
+  long null_calls = 0, null_blocks = 0, deflated_solves = 0;
 };
 
 // The refinement cadence of the handle (refine_cadence.h): its four parts, the option values it reads, and what the

@@ -195,6 +195,50 @@ class HipFact:
             out["witness"] = wit[:self.N].cpu().numpy()
         return out
 
+    def nullspace(self, want_basis: bool = False) -> dict:
+        """hipfact_nullspace: an orthonormal basis of null(K) of a rank-deficient working set from the statically
+        pivoted factor; blocks.  Returns the hipfact_null_info as a dict (dim, status, iterations, blocks, max_null_rho,
+        min_other_rho, orth) with "status_name" and, on request, "Z" (N x dim, the caller's numbering)."""
+        info = NullInfo()
+        if not want_basis:
+            self._check(self._lib.hipfact_nullspace(self._h, C.byref(info), None, max(self.N, 1)))
+            return info.as_dict()
+        import torch
+
+        ld = max(self.N, 1)
+        Z = torch.empty((16, ld), dtype=torch.float64, device=f"cuda:{int(self.info('device'))}")
+        self._check(self._lib.hipfact_nullspace(self._h, C.byref(info), C.c_void_p(Z.data_ptr()), ld))
+        out = info.as_dict()
+        out["Z"] = np.ascontiguousarray(Z[:info.dim, :self.N].cpu().numpy().T)
+        return out
+
+    def solve_device_deflated(self, d_rhs_ptr: int, d_sol_ptr: int, raise_singular: bool = True) -> dict:
+        """hipfact_solve_device_deflated: z = K^+ b, the minimum-norm least-squares solution, for device vectors;
+        blocks.  Returns the hipfact_extra_info as a dict (solve_device_extra) with "defect" = ||Z Z^T b|| / ||b||."""
+        info = ExtraInfo()
+        defect = C.c_double(0.0)
+        rc = self._lib.hipfact_solve_device_deflated(self._h, C.c_void_p(d_rhs_ptr), C.c_void_p(d_sol_ptr), C.byref(info),
+                                                     C.byref(defect))
+        if rc != 0 and not (rc == -3 and not raise_singular):
+            self._check(rc)
+        out = info.as_dict(rc)
+        out["defect"] = defect.value
+        return out
+
+    def solve_deflated(self, b, raise_singular: bool = True):
+        """hipfact_solve_deflated: (z, info) with z = K^+ b for a host vector; info as in solve_device_deflated."""
+        rhs = np.ascontiguousarray(b, dtype=np.float64)
+        assert rhs.size == self.N
+        sol = np.zeros_like(rhs)
+        info = ExtraInfo()
+        defect = C.c_double(0.0)
+        rc = self._lib.hipfact_solve_deflated(self._h, _ptr(rhs), _ptr(sol), C.byref(info), C.byref(defect))
+        if rc != 0 and not (rc == -3 and not raise_singular):
+            self._check(rc)
+        out = info.as_dict(rc)
+        out["defect"] = defect.value
+        return sol, out
+
     def residual_device(self, d_b_ptr: int, d_z_ptr: int, d_res_ptr: int, extended: bool = True):
         """hipfact_residual_device: res = b - K z on the handle's stream (extended: double-double accumulation)."""
         self._check(self._lib.hipfact_residual_device(self._h, C.c_void_p(d_b_ptr), C.c_void_p(d_z_ptr),
@@ -376,6 +420,52 @@ def condest_dense(A) -> dict:
     out["history"] = [int(i) for i in hist if i >= 0]
     out["witness"] = wit
     return out
+
+
+class NullInfo(C.Structure):
+    """hipfact_null_info (include/hipfact.h)"""
+    _fields_ = [("dim", C.c_int), ("status", C.c_int), ("iterations", C.c_int), ("blocks", C.c_int),
+                ("max_null_rho", C.c_double), ("min_other_rho", C.c_double), ("orth", C.c_double)]
+
+    def as_dict(self) -> dict:
+        out = {k: getattr(self, k) for k, _ in self._fields_}
+        out["status_name"] = NULL_STATUS[self.status] if 0 <= self.status < len(NULL_STATUS) else str(self.status)
+        return out
+
+
+NULL_STATUS = ["REGULAR", "FOUND", "NONE", "BLOCK_FULL", "UNRESOLVED"]
+
+
+def nullspace_dense(Khat, Minv, n0: int) -> dict:
+    """hipfact_debug_nullspace_dense: the rule of hipfact_nullspace with dense products (Khat: the equilibrated K^ with
+    n0 variables in front; Minv: the inverse of K^ - delta diag(0, I), which stands in for the blocked pass), on the host
+    (no GPU).  Returns the info as a dict with "Z" (N x dim)."""
+    Khat = np.asfortranarray(Khat, dtype=np.float64)
+    Minv = np.asfortranarray(Minv, dtype=np.float64)
+    assert Khat.ndim == 2 and Khat.shape[0] == Khat.shape[1] and Minv.shape == Khat.shape, (Khat.shape, Minv.shape)
+    N = Khat.shape[0]
+    info = NullInfo()
+    Z = np.zeros((N, 16), order="F")
+    rc = _lib.load().hipfact_debug_nullspace_dense(N, int(n0), _ptr(Khat), _ptr(Minv), N, C.byref(info), _ptr(Z))
+    if rc != 0:
+        raise HipfactError(rc, "hipfact_debug_nullspace_dense")
+    out = info.as_dict()
+    out["Z"] = np.ascontiguousarray(Z[:, :info.dim])
+    return out
+
+
+def nullspace_jacobi(T):
+    """hipfact_debug_nullspace_jacobi: (theta, V, sweeps) of a symmetric t x t matrix, t <= 16, by the cyclic Jacobi
+    routine of the rule, the eigenvalues by |theta| ascending (no GPU)."""
+    T = np.ascontiguousarray(T, dtype=np.float64)
+    assert T.ndim == 2 and T.shape[0] == T.shape[1], T.shape
+    t = T.shape[0]
+    theta = np.empty(t)
+    V = np.empty((t, t))
+    rc = _lib.load().hipfact_debug_nullspace_jacobi(t, _ptr(T), _ptr(theta), _ptr(V))
+    if rc < 0:
+        raise HipfactError(rc, "hipfact_debug_nullspace_jacobi")
+    return theta, V, rc
 
 
 class TrExtra(C.Structure):
