@@ -441,6 +441,79 @@ int hipfact_solve_device_deflated(hipfact_handle* h, const double* d_rhs, double
 int hipfact_solve_deflated(hipfact_handle* h, const double* rhs, double* sol, hipfact_extra_info* info /* nullable */,
                            double* defect /* nullable */);
 
+/* ---- selected inverse: the entries of K^-1 on the pattern of the factor ------------------------------------------
+ * M = L D L^T is the matrix the engine factors, in pivot order: K in generic mode, the equilibrated D S D (with the
+ * late variables of a dense_mode 1 plan) in saddle mode.  hipfact_selected_inverse forms Z = M^-1 on exactly the
+ * pattern of L + L^T by Takahashi's equations, in ONE top-down sweep over the front tree: with X = inv(L11), d and L21
+ * of a front and W = L21 X,  Z_UF = -Z_UU W,  Z_FF = X^T diag(1 / d) X - W^T Z_UF,  where Z_UU - the entries of Z at
+ * the front's update rows - is gathered from the parent.  Dense fp64 products on the matrix cores, four launches per
+ * level, no workgroup waits for another one, every sum in a fixed order: the same factorisation gives
+ * the same bits on every call.  Z is stored like the factor (hipfact_debug_copy "selinv_Z" has the layout of "L": an
+ * r x w column-major panel per front, the full symmetric Z_FF on top, Z_UF below).
+ * All four calls are BLOCKING, with the contract of hipfact_condition_estimate: on entry they do what hipfact_check
+ * does; HIPFACT_ESTATE before a factorisation; none of them becomes "the last solve" - hipfact_solution* still return
+ * the earlier single solve, and a single solve issued afterwards gives the bits it would have given without the call.
+ * With an active static-pivot shift K has no inverse: every call returns HIPFACT_ESINGULAR with a message that points
+ * to hipfact_nullspace.  The result is kept per factorisation: a second call runs no launch (info key "selinv_runs"
+ * counts the sweeps), a new factorisation voids it.
+ * Workspace, allocated by the first call of a plan state and kept with it: Z and W, as large as the factor each
+ * ("L_bytes"), and one u x u block per front (the sum of u^2 doubles; no reuse) - info key "selinv_bytes".  A failed
+ * allocation returns HIPFACT_ENOMEM, releases the workspace and leaves the handle usable.
+ *
+ * hipfact_inverse_diagonal_device: d_out[q] = (K^-1)_ii for i = d_idx[q] in the caller's numbering (d_idx NULL: every
+ * i in order, nidx == N); forms Z on first use.  An index outside [0, N) is HIPFACT_EINVAL (nothing is written), as
+ * are a NULL output and a negative count; a zero count returns HIPFACT_OK.  hipfact_inverse_diagonal: the same for
+ * host arrays.
+ * WHAT THE TREE SERVES (status HIPFACT_SELINV_TREE).  Generic mode: the diagonal entry of Z.  Saddle mode, with
+ * Z = D Z^ D (the row scales D are powers of two: applied exactly), a_k = column k of the working-set rows and the
+ * sums over the pairs of entries of that column in a fixed order:
+ *     free ordinary variable k             1 - a_k^T Z a_k
+ *     variable fixed by an active bound    0
+ *     working-set row r                    -Z_rr
+ *     late (dense) variable of a dense_mode 1 plan    -Z_ii
+ *     unit row of the active bound on k    -1 - a_k^T Z a_k
+ * (the handle's structure keeps the columns of active bounds whole, so every pair of such a sum is an entry of it; on
+ * the crafted and plain saddle cases of the tests no index kind needs the fallback).  Scaling the Jacobian by 2^k
+ * changes the entries at the working-set rows by exactly 2^-2k and leaves the others bitwise unchanged.
+ * THE FALLBACK makes the call total: an index whose sum needs an entry the structure does not hold is flagged by the
+ * extraction kernel and taken from component i of K^-1 e_i, a column of the checked blocked solve's internal path, 16
+ * columns per pass, in place, with the options in force (status HIPFACT_SELINV_MIXED; the bits of such a value are
+ * those of hipfact_solve_multi applied to e_i).  Whole plan states go that way (status HIPFACT_SELINV_COLUMNS) when
+ * they carry the low-rank dense-column correction (dense_mode 2 with dense columns), when they are superset plans with
+ * structure rows outside the current working set, and under selinv_route = 1.  A column that makes the blocked solve
+ * return HIPFACT_ESINGULAR makes this call return it.
+ * hipfact_inverse_entries_device: d_out[q] = (K^-1)_ij at (d_row[q], d_col[q]) for the pairs the selected inverse
+ * holds directly - generic mode: (i, j) in the structure of L + L^T; saddle mode: i and j both working-set rows or
+ * late variables with the pair in the structure, value -s_i s_j d_i d_j Z^_ij with s = -1 for a late variable (the sign
+ * of -J M^-1 J).  (i, j) and (j, i) give the same bits.  Every other pair (an index outside [0, N) included) gets a
+ * quiet NaN and is counted in *outside.  This call has no fallback.
+ * Options (hipfact_set_option; the feature's own, kept out of the table below; readable through hipfact_get_info;
+ * anything else is HIPFACT_EINVAL):
+ *   selinv_route         0 (default), 1: every index goes through the fallback columns (a measurement and test aid)
+ *   selinv_fallback_max  -1 or >= 0, default 4096: above this many fallback values the diagonal call returns
+ *                        HIPFACT_ESTATE with the count in the message instead of spending seconds silently; -1: no limit
+ *   selinv_fake_absent   test hook, default 0: > 0 makes the saddle-mode extraction report every request slot q with
+ *                        q % value == 0 as not served, so that the per-index fallback can be exercised
+ * Info keys: "selinv_runs" sweeps actually run, "selinv_served" requested values served by the selected inverse,
+ * "selinv_fallback_cols" requested values that went through fallback columns, "selinv_bytes" workspace size. */
+enum { HIPFACT_SELINV_TREE = 0,      /* every requested value came from the selected inverse */
+       HIPFACT_SELINV_MIXED = 1,     /* some came from unit-vector columns of the blocked solve */
+       HIPFACT_SELINV_COLUMNS = 2 }; /* all of them did (plan kind not served, or selinv_route = 1) */
+typedef struct hipfact_selinv_info {
+  int status;
+  long long served, fallback;   /* requested values by source */
+  int fallback_blocks;          /* blocked passes the fallback asked for */
+  double omega;                 /* largest backward error over the fallback columns, 0 without */
+} hipfact_selinv_info;
+
+int hipfact_selected_inverse(hipfact_handle* h);   /* forms and keeps Z for the current factorisation */
+int hipfact_inverse_diagonal_device(hipfact_handle* h, long long nidx, const int* d_idx /* nullable: all N */,
+                                    double* d_out, hipfact_selinv_info* info /* nullable */);
+int hipfact_inverse_diagonal(hipfact_handle* h, long long nidx, const int* idx /* nullable */, double* out,
+                             hipfact_selinv_info* info /* nullable */);
+int hipfact_inverse_entries_device(hipfact_handle* h, long long nent, const int* d_row, const int* d_col,
+                                   double* d_out, long long* outside /* host, nullable */);
+
 /* Blocks until the queued work has finished and reports what the asynchronous
  * entry points above could not: a singular / rank-deficient factorisation
  * (HIPFACT_ESINGULAR), a solve whose iterative refinement stalled far above its
@@ -908,6 +981,19 @@ const char* hipfact_plan_error(const hipfact_plan* plan);
 int hipfact_plan_array(const hipfact_plan* plan, const char* name, const void** data, int64_t* len,
                        int* elem_size);
 int hipfact_plan_scalar(const hipfact_plan* plan, const char* name, double* value);
+
+/* The selected inverse on the host (sleqp_amd/csrc/selinv_host.h: plain C++ fp64, every sum in index order), from what
+ * hipfact_plan_create produces.  hipfact_debug_selinv_host: L is a factor arena in the device layout (L_size doubles: per
+ * front an r x w column-major panel at sn_Loff, inv(L11) strictly lower with the pivots on the diagonal, L21 below); Z
+ * gets Z = (L D L^T)^-1 on the pattern of L + L^T in the same layout, the full symmetric Z_FF on top of every panel.
+ * HIPFACT_ESINGULAR on a zero or non-finite pivot.  hipfact_debug_selinv_lookup: off[q] = the offset in that arena of
+ * the entry at pivot positions (pi[q], pj[q]) - the front of the smaller position, then a binary search in its sorted
+ * rows - or -1 for a pair outside the structure; symmetric pairs give the same offset.  The same routine runs in the
+ * device's extraction kernels.  hipfact_debug_copy "selinv_Z_host" runs the executor on a handle's own plan and the
+ * device's factor bits. */
+int hipfact_debug_selinv_host(const hipfact_plan* plan, const double* L, double* Z);
+int hipfact_debug_selinv_lookup(const hipfact_plan* plan, long long npairs, const int* pi, const int* pj,
+                                long long* off /* -1: absent */);
 
 #ifdef __cplusplus
 }

@@ -31,6 +31,8 @@ SYMBOLS = [
     "hipfact_condition_estimate", "hipfact_debug_condest_dense", "hipfact_debug_condest_recorded",
     "hipfact_nullspace", "hipfact_solve_device_deflated", "hipfact_solve_deflated", "hipfact_debug_nullspace_dense",
     "hipfact_debug_nullspace_jacobi",
+    "hipfact_selected_inverse", "hipfact_inverse_diagonal_device", "hipfact_inverse_diagonal", "hipfact_inverse_entries_device",
+    "hipfact_debug_selinv_host", "hipfact_debug_selinv_lookup",
     "hipfact_solve_device_extra", "hipfact_solve_extra", "hipfact_residual_device", "hipfact_debug_extra_rule", "hipfact_debug_dd_residual",
     "hipfact_solve_device_multi_extra", "hipfact_solve_multi_extra", "hipfact_residual_device_multi", "hipfact_debug_multi_extra_schedule",
     "hipfact_solution_device", "hipfact_synchronize", "hipfact_check", "hipfact_stream",
@@ -101,6 +103,14 @@ def load() -> C.CDLL:
         lib.hipfact_solve_deflated.argtypes = [vp, vp, vp, vp, C.POINTER(cd)]
         lib.hipfact_debug_nullspace_dense.argtypes = [ci, ci, vp, vp, C.c_longlong, vp, vp]
         lib.hipfact_debug_nullspace_jacobi.argtypes = [ci, vp, vp, vp]
+    if hasattr(lib, "hipfact_selected_inverse"):
+        ll = C.c_longlong
+        lib.hipfact_selected_inverse.argtypes = [vp]
+        lib.hipfact_inverse_diagonal_device.argtypes = [vp, ll, vp, vp, vp]
+        lib.hipfact_inverse_diagonal.argtypes = [vp, ll, vp, vp, vp]
+        lib.hipfact_inverse_entries_device.argtypes = [vp, ll, vp, vp, vp, C.POINTER(ll)]
+        lib.hipfact_debug_selinv_host.argtypes = [vp, vp, vp]
+        lib.hipfact_debug_selinv_lookup.argtypes = [vp, ll, vp, vp, vp]
     lib.hipfact_solution_device.argtypes = [vp, C.POINTER(vp)]
     lib.hipfact_synchronize.argtypes = [vp]
     lib.hipfact_check.argtypes = [vp]

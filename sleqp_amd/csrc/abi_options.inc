@@ -234,6 +234,11 @@ int hipfact_set_option(hipfact_handle* h, const char* name, double value) {
     const int rc = nullspace_set_option(h, name, value, known);
     if (known) return rc;
   }
+  {  // ... and the selected inverse (runtime_selinv.inc)
+    bool known = false;
+    const int rc = selinv_set_option(h, name, value, known);
+    if (known) return rc;
+  }
   for (const OptionRow& row : kOptions) {
     if (!row.name || strcmp(name, row.name)) continue;
     const int changed = row.set(h, value);
@@ -271,8 +276,11 @@ int hipfact_debug_copy(hipfact_handle* h, const char* name, void* out, size_t by
   if (!strcmp(name, "sn_level")) return host_copy(P.sn_level);
   if (!strcmp(name, "dense_cols")) return host_copy(P.dense_cols);
   if (!strcmp(name, "cond_history")) return host_copy(h->cond_history);  // index history of the last condition estimate
+  // the host executor of the selected inverse (selinv_host.h) on the handle's own plan and the device's factor bits
+  if (!strcmp(name, "selinv_Z_host")) return selinv_host_on_device_factor(h, static_cast<double*>(out), bytes);
   const DevBuf* b = nullptr;
   if (!strcmp(name, "L")) b = &h->d_L;
+  else if (!strcmp(name, "selinv_Z")) b = (h->selinv_ws && h->selinv_for_factor == h->num_factor) ? &h->d_selZ : nullptr;  // Z of the current factorisation, the layout of "L"
   else if (!strcmp(name, "U")) b = &h->d_U;
   else if (!strcmp(name, "SPf")) b = &h->d_SPf;
   else if (!strcmp(name, "sitems")) b = &h->d_sitems;
@@ -509,6 +517,9 @@ int hipfact_get_info(const hipfact_handle* h, const char* name, double* value) {
   INFO("multi_sliced_fronts", h->mitems_for < 0 ? 0 : h->n_mcut) INFO("multi_slice_items", h->mitems_for < 0 ? 0 : h->n_mslices) INFO("multi_slice_rows", h->multi_slice_rows)
   INFO("cond_estimates", h->cond_estimates) INFO("cond_blocks", h->cond_blocks) INFO("cond_last", h->cond_last) INFO("condition_estimate", h->condition_estimate)
   INFO("null_calls", h->null_calls) INFO("null_blocks", h->null_blocks) INFO("deflated_solves", h->deflated_solves) INFO("deflate_singular", h->deflate_singular)
+  INFO("selinv_runs", h->selinv_runs) INFO("selinv_served", h->selinv_served) INFO("selinv_fallback_cols", h->selinv_fallback_cols)
+  INFO("selinv_bytes", h->selinv_bytes) INFO("selinv_route", h->selinv_route) INFO("selinv_fallback_max", h->selinv_fallback_max)
+  INFO("selinv_cached", (h->selinv_ws && h->selinv_for_factor == h->num_factor) ? 1 : 0)
   INFO("null_dim", (h->null_for_factor == h->num_factor && h->null_for_delta == h->reg_delta) ? h->null_res.dim : -1)
   INFO("null_status", (h->null_for_factor == h->num_factor && h->null_for_delta == h->reg_delta) ? h->null_res.status : -1)
   INFO("extra_solves", h->extra_solves) INFO("extra_passes", h->extra_passes) INFO("extra_last_status", h->extra_last_status)

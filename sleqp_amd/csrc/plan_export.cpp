@@ -6,6 +6,7 @@
 
 #include "../../include/hipfact.h"
 #include "plan.h"
+#include "selinv_host.h"
 
 struct hipfact_plan {
   hipfact::Plan plan;
@@ -73,6 +74,31 @@ int hipfact_plan_scalar(const hipfact_plan* plan, const char* name, double* valu
   SC(t_total) SC(N_ext) SC(n_bounds)
 #undef SC
   return HIPFACT_EINVAL;
+}
+
+// ---- the selected inverse on the host (selinv_host.h): the front recurrence and the lookup, from the plan alone
+
+static hipfact::SelinvTree selinv_tree(const hipfact::Plan& P) {
+  return hipfact::SelinvTree{P.nsuper,       P.sn_c0.data(),     P.sn_r.data(),    P.sn_parent.data(), P.sn_level.data(),
+                             P.rel.data(),   P.sn_rowptr.data(), P.sn_Loff.data(), P.rel_ptr.data(),   P.sn_rows.data()};
+}
+
+int hipfact_debug_selinv_host(const hipfact_plan* plan, const double* L, double* Z) {
+  if (!plan || !L || !Z) return HIPFACT_EINVAL;
+  try {
+    return hipfact::selinv_host(selinv_tree(plan->plan), L, Z) ? HIPFACT_OK : HIPFACT_ESINGULAR;
+  } catch (const std::bad_alloc&) {
+    return HIPFACT_ENOMEM;
+  }
+}
+
+int hipfact_debug_selinv_lookup(const hipfact_plan* plan, long long npairs, const int* pi, const int* pj, long long* off) {
+  if (!plan || npairs < 0 || (npairs > 0 && (!pi || !pj || !off))) return HIPFACT_EINVAL;
+  const hipfact::Plan& P = plan->plan;
+  for (long long q = 0; q < npairs; ++q)
+    off[q] = hipfact::selinv_offset(P.nsuper, P.sn_c0.data(), P.sn_r.data(), P.sn_rowptr.data(), P.sn_rows.data(),
+                                    P.sn_Loff.data(), pi[q], pj[q]);
+  return HIPFACT_OK;
 }
 
 }  // extern "C"

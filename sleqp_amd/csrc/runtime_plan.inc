@@ -263,6 +263,9 @@ static int upload_plan(hipfact_handle* h) {
   h->levels.assign(P.nlevels, LevelInfo());
   h->dealt_multi = 0;
   h->mitems_for = -1;  // (the blocked solve's item lists: rebuilt by its next call)
+  h->selinv_ws = false;  // (the selected inverse's offsets and maps likewise; no result of another plan survives)
+  h->selinv_for_factor = -1;
+  h->selinv_bytes = 0;
   size_t max_lds = 0;
   std::vector<int> items;
   std::vector<FrontItem> fitems;

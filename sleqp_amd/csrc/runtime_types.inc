@@ -90,10 +90,10 @@ struct LevelInfo {
 };
 
 // kernel classes for the event-timed profiling mode (option "profile")
-enum ProfClass { PC_MEMSET = 0, PC_MVALS, PC_GATHER, PC_FACTOR, PC_FACTOR_A, PC_FACTOR_B, PC_FACTOR_C, PC_FACTOR_D, PC_FACTOR_T, PC_FWD, PC_BWD, PC_RHS, PC_XUPD, PC_RESID, PC_AXPY, PC_PERM, PC_SPANEL, PC_TREE, PC_COUNT };
+enum ProfClass { PC_MEMSET = 0, PC_MVALS, PC_GATHER, PC_FACTOR, PC_FACTOR_A, PC_FACTOR_B, PC_FACTOR_C, PC_FACTOR_D, PC_FACTOR_T, PC_FWD, PC_BWD, PC_RHS, PC_XUPD, PC_RESID, PC_AXPY, PC_PERM, PC_SPANEL, PC_TREE, PC_SELINV, PC_COUNT };
 static const char* const kProfNames[PC_COUNT] = {"memset", "mvals", "gather", "factor", "factorA", "factorB", "factorC",
                                                  "factorD", "factorT", "fwd", "bwd", "rhs", "xupd", "resid", "axpy", "perm",
-                                                 "spanel", "tree"};
+                                                 "spanel", "tree", "selinv"};
 
 struct Prof {
   bool on = false;
@@ -265,6 +265,14 @@ struct PlanState : FactorMemo {
   // blocks and the diagonal of D are the condition estimate's), the basis Z of the current factorisation, up to 15
   // columns (d_nullZ).  Allocated by the first such call of the state.
   DevBuf d_nblk, d_nullZ;
+  // selected inverse (runtime_selinv.inc): the Z panels and W = L21 X in the layout of d_L, the Z_UU blocks (sum of u^2
+  // doubles, no reuse), their offsets, the tree's arrays for the lookup and iperm; a 16-column block of the fallback.
+  // Allocated by the first such call of the state (selinv_ws); Z belongs to the factorisation number selinv_for_factor
+  // of the handle (-1: none; another factorisation voids it without anybody having to say so).
+  DevBuf d_selZ, d_selW, d_selG, d_selmeta, d_selblk;
+  bool selinv_ws = false;
+  long selinv_for_factor = -1;
+  size_t selinv_bytes = 0;
 
   PlanState() = default;
   PlanState(PlanState&&) = default;
@@ -524,6 +532,15 @@ struct hipfact_handle : PlanState, SingleSolveMemo {
   bool in_deflated = false;  // (a deflated solve is running: its plain solves are not rescued themselves)
   int rescue_scope = 0;      // > 0 inside hipfact_check and hipfact_solution*: the only places the rescue applies (RescueScope)
   long null_calls = 0, null_blocks = 0, deflated_solves = 0;
+  // selected inverse (runtime_selinv.inc): the options "selinv_route" and "selinv_fallback_max", a flag word and the
+  // partial counts of the extraction kernels, the pinned words the host reads; counters of hipfact_get_info
+  int selinv_route = 0;
+  int selinv_fake_absent = 0;  // test hook: the saddle-mode diagonal treats every request slot q with q % this == 0 as not served by the tree
+  long long selinv_fallback_max = 4096;
+  DevBuf d_selpart, d_selkind, d_selneed;  // ... the kinds of the caller's positions (saddle mode), the flags of the indices the tree cannot serve
+  PinBuf h_selout;
+  long selinv_runs = 0;
+  long long selinv_served = 0, selinv_fallback_cols = 0;
 };
 
 // The refinement cadence of the handle (refine_cadence.h): its four parts, the option values it reads, and what the

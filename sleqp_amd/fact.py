@@ -212,6 +212,57 @@ class HipFact:
         out["Z"] = np.ascontiguousarray(Z[:info.dim, :self.N].cpu().numpy().T)
         return out
 
+    def selected_inverse(self, want_z: bool = True):
+        """hipfact_selected_inverse: forms Z = M^-1 on the pattern of the factor for the current factorisation (kept
+        until the next one); blocks.  Returns the Z arena in the layout of the factor arena "L" (hipfact_debug_copy
+        "selinv_Z"): per front an r x w column-major panel, the full symmetric Z_FF on top and Z_UF below; want_z =
+        False leaves it on the device."""
+        self._check(self._lib.hipfact_selected_inverse(self._h))
+        if not want_z:
+            return None
+        Z = np.empty(int(self.info("L_bytes")) // 8)
+        self._check(self._lib.hipfact_debug_copy(self._h, b"selinv_Z", _ptr(Z), Z.nbytes))
+        return Z
+
+    def inverse_diagonal(self, idx=None, want_info: bool = False):
+        """hipfact_inverse_diagonal: (K^-1)_ii at the indices idx (None: all N) in the caller's numbering; blocks.
+        With want_info also the hipfact_selinv_info as a dict (status, served, fallback, fallback_blocks, omega)."""
+        info = SelinvInfo()
+        if idx is None:
+            n, ip = self.N, None
+        else:
+            idx = np.ascontiguousarray(idx, dtype=np.int32)
+            n, ip = idx.size, _ptr(idx)
+        out = np.empty(n, dtype=np.float64)
+        self._check(self._lib.hipfact_inverse_diagonal(self._h, n, ip, _ptr(out), C.byref(info)))
+        return (out, info.as_dict()) if want_info else out
+
+    def inverse_entries(self, rows, cols, want_outside: bool = False):
+        """hipfact_inverse_entries_device: (K^-1)_ij at the pairs (rows, cols) the selected inverse holds directly; a
+        quiet NaN for every other pair; blocks.  With want_outside also the number of such pairs."""
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        cols = np.ascontiguousarray(cols, dtype=np.int32)
+        assert rows.shape == cols.shape and rows.ndim == 1
+        n = rows.size
+        out = np.empty(n, dtype=np.float64)
+        outside = C.c_longlong(0)
+        hip = C.CDLL("libamdhip64.so")
+        buf = C.c_void_p()  # values | rows | cols
+        if hip.hipMalloc(C.byref(buf), C.c_size_t(max(16 * n, 16))) != 0:
+            raise MemoryError("hipMalloc")
+        try:
+            d_o, d_r, d_c = buf.value, buf.value + 8 * n, buf.value + 12 * n
+            for dst, a in ((d_r, rows), (d_c, cols)):
+                if n and hip.hipMemcpy(C.c_void_p(dst), _ptr(a), C.c_size_t(a.nbytes), 1) != 0:
+                    raise RuntimeError("hipMemcpy")
+            self._check(self._lib.hipfact_inverse_entries_device(self._h, n, C.c_void_p(d_r), C.c_void_p(d_c),
+                                                                 C.c_void_p(d_o), C.byref(outside)))
+            if n and hip.hipMemcpy(_ptr(out), C.c_void_p(d_o), C.c_size_t(out.nbytes), 2) != 0:
+                raise RuntimeError("hipMemcpy")
+        finally:
+            hip.hipFree(buf)
+        return (out, int(outside.value)) if want_outside else out
+
     def solve_device_deflated(self, d_rhs_ptr: int, d_sol_ptr: int, raise_singular: bool = True) -> dict:
         """hipfact_solve_device_deflated: z = K^+ b, the minimum-norm least-squares solution, for device vectors;
         blocks.  Returns the hipfact_extra_info as a dict (solve_device_extra) with "defect" = ||Z Z^T b|| / ||b||."""
@@ -434,6 +485,20 @@ class NullInfo(C.Structure):
 
 
 NULL_STATUS = ["REGULAR", "FOUND", "NONE", "BLOCK_FULL", "UNRESOLVED"]
+
+
+class SelinvInfo(C.Structure):
+    """hipfact_selinv_info (include/hipfact.h)"""
+    _fields_ = [("status", C.c_int), ("served", C.c_longlong), ("fallback", C.c_longlong), ("fallback_blocks", C.c_int),
+                ("omega", C.c_double)]
+
+    def as_dict(self) -> dict:
+        out = {k: getattr(self, k) for k, _ in self._fields_}
+        out["status_name"] = SELINV_STATUS[self.status] if 0 <= self.status < len(SELINV_STATUS) else str(self.status)
+        return out
+
+
+SELINV_STATUS = ["TREE", "MIXED", "COLUMNS"]
 
 
 def nullspace_dense(Khat, Minv, n0: int) -> dict:
