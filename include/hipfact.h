@@ -441,6 +441,59 @@ int hipfact_solve_device_deflated(hipfact_handle* h, const double* d_rhs, double
 int hipfact_solve_deflated(hipfact_handle* h, const double* rhs, double* sol, hipfact_extra_info* info /* nullable */,
                            double* defect /* nullable */);
 
+/* ---- GMRES solve: Krylov refinement on the statically pivoted factor ---------------------------------------------
+ * A statically pivoted factor is the exact inverse of K^ - delta E, and every solve on it is repaired by stationary
+ * refinement against the caller's K.  That iteration has the propagation matrix I - K_d^-1 K with the eigenvalues
+ * delta / (sigma^2 + delta) over the singular values sigma of the equilibrated A^.  An exactly dependent row (sigma = 0)
+ * is the null space's and the deflated solve's case.  A row that is only NEARLY dependent (sigma^2 <~ delta, that is
+ * cond(A^) >~ 3e3) contracts by 0.5 ... 0.99 per pass: hipfact_solve_device_extra ends STALLED, hipfact_nullspace
+ * answers UNRESOLVED - and the plain solve fails silently, because the residual along such a direction is sigma^2 x the
+ * error: the backward error looks fine while the multipliers are wrong.  K K_d^-1, however, has every eigenvalue at
+ * sigma^2 / (sigma^2 + delta) ~ 1 but for one outlier per such direction and a 0 per exact null direction (of index 1:
+ * a consistent system is safe), so a Krylov method needs about (#outliers + 2) steps.
+ * The rule (sleqp_amd/csrc/gmres_rule.h): restarted, right-preconditioned GMRES with these constants, none an option -
+ * restart length 16, inner tolerance 2^-30, target 2^-51, cycle cap = refine_max.
+ *   z = 0;  cycle c = 1, 2, ...:
+ *     r = b - K z in double-double, rounded once; beta_c = ||r||_2 (caller's numbering; the inactive rows of a superset
+ *         plan hold zeros); omega_c = the backward error as "last_omega" defines it
+ *     NONFINITE if either is not finite; CONVERGED if omega_c <= 2^-51 or beta_c = 0 (b = 0: zero cycles, z = 0);
+ *     STALLED if c >= 3 and beta_c > beta_{c-1} / 2 (z is kept, no accuracy claim); CYCLE_LIMIT if c > cap
+ *     v_1 = r / beta_c; for j = 1 .. 16: u_j = K_d^-1 v_j (ONE plain single solve); w = K u_j (fp64 walk over K);
+ *         classical Gram-Schmidt against v_1 .. v_j, exactly two passes, the coefficients added; h_{j+1,j} = ||w||_2;
+ *         v_{j+1} = w / h_{j+1,j}; Givens update of the Hessenberg column; est = |g_{j+1}|;
+ *         leave when est <= 2^-30 beta_c, or h_{j+1,j} <= 2^-44 (||w||_2 in front of the projections), or j = 16
+ *     y by back-substitution; dz = sum y_j u_j; z += dz
+ * The target is the rounding level on purpose: omega ~ 1e-12 is reached after the first cycle with the multipliers still
+ * wrong; it falls to ~ 1e-18 only when the outlier directions are resolved, and can be measured that low only because
+ * the restart residual is double-double.  More outliers than the basis holds end STALLED.
+ * info: status (below), cycles run, Arnoldi steps (= plain solves) over all cycles, null_status (HIPFACT_NULL_*; -1 with
+ * deflate = 0), the final omega, beta_rel = the last beta over the first, dz_rel[q] = ||dz||_inf / ||z||_inf of the last
+ * update over the variables (q = 0) and the multipliers (q = 1; generic mode: one block, dz_rel[1] = 0).
+ * deflate = 1: the null space is computed on first use.  FOUND: the three projections of the deflated solve - b once,
+ * every restart residual, z behind every update - and the minimum-norm solution leaves.  Any other status: the loop
+ * runs unprojected and null_status says which; x is unique for a consistent system, the multipliers are one solution.
+ * deflate = 0: the null space is never touched.
+ * Contract, word for word that of hipfact_solve_device_extra: the call blocks; on entry it does what hipfact_check
+ * does; d_sol may be d_rhs (no other overlap); it is not "the last solve" - hipfact_solution*, "last_omega" and the
+ * refinement cadence keep describing the single solve in front of it, and a single solve issued afterwards gives the
+ * bits it would have given without the call; the same handle state gives the same bits on every call.
+ * HIPFACT_ESTATE before a factorisation, HIPFACT_EINVAL for NULL vectors or deflate outside {0, 1}, HIPFACT_ENOMEM when
+ * the workspace ((2 x 17 + 4) vectors of N doubles, kept with the plan state) cannot be had - the handle stays usable.
+ * Returns HIPFACT_OK with the status in info, whatever it is (a NaN / Inf right-hand side is NONFINITE and the caller's
+ * case); the final omega is additionally judged as the single solve's (above "fail_omega": HIPFACT_ESINGULAR, message
+ * in hipfact_last_error; the solution reached is still handed out).  Plans with the low-rank dense-column correction
+ * work unchanged: every K_d^-1 is the single path's.  One host synchronisation per Arnoldi step and one per cycle.
+ * hipfact_get_info: "gmres_solves", "gmres_cycles", "gmres_steps" (cumulative), "gmres_last_status".
+ * hipfact_solve_gmres: the same for host vectors. */
+enum { HIPFACT_GMRES_CONVERGED = 0, HIPFACT_GMRES_STALLED = 1, HIPFACT_GMRES_CYCLE_LIMIT = 2, HIPFACT_GMRES_NONFINITE = 3 };
+typedef struct hipfact_gmres_info {
+  int status, cycles, steps, null_status;
+  double omega, beta_rel, dz_rel[2];
+} hipfact_gmres_info;
+int hipfact_solve_device_gmres(hipfact_handle* h, const double* d_rhs, double* d_sol, int deflate,
+                               hipfact_gmres_info* info /* nullable */);
+int hipfact_solve_gmres(hipfact_handle* h, const double* rhs, double* sol, int deflate, hipfact_gmres_info* info /* nullable */);
+
 /* ---- selected inverse: the entries of K^-1 on the pattern of the factor ------------------------------------------
  * M = L D L^T is the matrix the engine factors, in pivot order: K in generic mode, the equilibrated D S D (with the
  * late variables of a dense_mode 1 plan) in saddle mode.  hipfact_selected_inverse forms Z = M^-1 on exactly the
@@ -935,6 +988,21 @@ int hipfact_debug_nullspace_dense(int N, int n0, const double* Khat, const doubl
  * theta[c] and column c of V (row-major t x t) are the eigenpairs, by |theta| ascending.  Returns the sweeps taken, or
  * HIPFACT_EINVAL for t outside [1, 16] or a NULL array. */
 int hipfact_debug_nullspace_jacobi(int t, const double* A, double* theta, double* V);
+/* The rule of hipfact_solve_device_gmres (sleqp_amd/csrc/gmres_rule.h) with dense products, no GPU needed; used by
+ * the tests.  K and Minv (it stands in for the plain solve on the statically pivoted factor), both N x N, column-major
+ * with ld >= N, in ONE space: no equilibration here, omega = ||r||_inf / (||z||_inf + ||b||_inf); the restart residual
+ * in long double; cycle cap 10 (the default refine_max); n0: the rows in front of the second block of dz_rel (n0 = N:
+ * one block).  Every sum in index order.  HIPFACT_EINVAL for N <= 0, n0 outside [0, N], ld < N or a NULL array. */
+int hipfact_debug_gmres_dense(int N, int n0, const double* K, const double* Minv, long long ld, const double* b, double* z,
+                              hipfact_gmres_info* info /* nullable */);
+/* ... and the Arnoldi steps of its first ncycles cycles in cycle_steps (nullable; 0 behind the cycles run). */
+int hipfact_debug_gmres_dense_steps(int N, int n0, const double* K, const double* Minv, long long ld, const double* b,
+                                    double* z, hipfact_gmres_info* info /* nullable */, int* cycle_steps, int ncycles);
+/* The small recurrences of that rule on a (k + 1) x k upper Hessenberg matrix H (column-major, leading dimension
+ * k + 1, k <= 16; non-negative subdiagonal): the Givens rotations column by column and the back-substitution.
+ * y (k values) minimises ||beta e_1 - H y||_2; *est = |g_{k+1}|, the norm of that residual.  HIPFACT_EINVAL for k
+ * outside [1, 16] or a NULL array. */
+int hipfact_debug_gmres_hessenberg(int k, const double* H, double beta, double* y, double* est);
 /* The refinement cadence of the single solve as a pure host function (no GPU needed; used by the tests): how many
  * correction passes the solve graphs carry, which solves take a residual, and which leave their verdict to the next tree
  * launch.  A script of events runs through the transitions the runtime calls, on one plan of one fresh handle.

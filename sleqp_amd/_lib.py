@@ -31,6 +31,8 @@ SYMBOLS = [
     "hipfact_condition_estimate", "hipfact_debug_condest_dense", "hipfact_debug_condest_recorded",
     "hipfact_nullspace", "hipfact_solve_device_deflated", "hipfact_solve_deflated", "hipfact_debug_nullspace_dense",
     "hipfact_debug_nullspace_jacobi",
+    "hipfact_solve_device_gmres", "hipfact_solve_gmres", "hipfact_debug_gmres_dense", "hipfact_debug_gmres_dense_steps",
+    "hipfact_debug_gmres_hessenberg",
     "hipfact_selected_inverse", "hipfact_inverse_diagonal_device", "hipfact_inverse_diagonal", "hipfact_inverse_entries_device",
     "hipfact_debug_selinv_host", "hipfact_debug_selinv_lookup",
     "hipfact_solve_device_extra", "hipfact_solve_extra", "hipfact_residual_device", "hipfact_debug_extra_rule", "hipfact_debug_dd_residual",
@@ -103,6 +105,13 @@ def load() -> C.CDLL:
         lib.hipfact_solve_deflated.argtypes = [vp, vp, vp, vp, C.POINTER(cd)]
         lib.hipfact_debug_nullspace_dense.argtypes = [ci, ci, vp, vp, C.c_longlong, vp, vp]
         lib.hipfact_debug_nullspace_jacobi.argtypes = [ci, vp, vp, vp]
+    if hasattr(lib, "hipfact_solve_device_gmres"):
+        ll = C.c_longlong
+        lib.hipfact_solve_device_gmres.argtypes = [vp, vp, vp, ci, vp]
+        lib.hipfact_solve_gmres.argtypes = [vp, vp, vp, ci, vp]
+        lib.hipfact_debug_gmres_dense.argtypes = [ci, ci, vp, vp, ll, vp, vp, vp]
+        lib.hipfact_debug_gmres_dense_steps.argtypes = [ci, ci, vp, vp, ll, vp, vp, vp, vp, ci]
+        lib.hipfact_debug_gmres_hessenberg.argtypes = [ci, vp, cd, vp, C.POINTER(cd)]
     if hasattr(lib, "hipfact_selected_inverse"):
         ll = C.c_longlong
         lib.hipfact_selected_inverse.argtypes = [vp]

@@ -522,6 +522,7 @@ int hipfact_get_info(const hipfact_handle* h, const char* name, double* value) {
   INFO("selinv_cached", (h->selinv_ws && h->selinv_for_factor == h->num_factor) ? 1 : 0)
   INFO("null_dim", (h->null_for_factor == h->num_factor && h->null_for_delta == h->reg_delta) ? h->null_res.dim : -1)
   INFO("null_status", (h->null_for_factor == h->num_factor && h->null_for_delta == h->reg_delta) ? h->null_res.status : -1)
+  INFO("gmres_solves", h->gmres_solves) INFO("gmres_cycles", h->gmres_cycles) INFO("gmres_steps", h->gmres_steps) INFO("gmres_last_status", h->gmres_last_status)
   INFO("extra_solves", h->extra_solves) INFO("extra_passes", h->extra_passes) INFO("extra_last_status", h->extra_last_status)
   INFO("extra_multi_solves", h->extra_multi_solves) INFO("extra_multi_cols", h->extra_multi_cols) INFO("extra_multi_passes", h->extra_multi_passes)
   INFO("num_solve", h->num_solve) INFO("num_refined", h->solve_cad.num_refined) INFO("refine_adaptive", h->refine_adaptive)

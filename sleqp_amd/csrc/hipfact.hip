@@ -5,7 +5,7 @@
 // state.  All numerics run on the device; there is no CPU fallback: without a
 // usable GPU hipfact_create fails with HIPFACT_EDEVICE.
 //
-// The host translation unit (the kernels are compiled separately: kernels_factor.hip / kernels_solve.hip / kernels_extra.hip / kernels_nullspace.hip / kernels_selinv.hip, declared in the
+// The host translation unit (the kernels are compiled separately: kernels_factor.hip / kernels_solve.hip / kernels_extra.hip / kernels_nullspace.hip / kernels_selinv.hip / kernels_gmres.hip, declared in the
 // generated kernels_decl.h), split by role:
 //   runtime_types.inc   buffers, plan state, the handle          abi_core.inc         create .. solution (SleqpFact)
 //   runtime_plan.inc    upload of a plan, work items             abi_working_set.inc  superset plans, assemble_kkt
@@ -18,6 +18,7 @@
 //   runtime_condest.inc 1-norm condition estimate (condest_rule.h) abi_condest.inc      hipfact_condition_estimate, _debug_condest_*
 //   runtime_nullspace.inc null space of a rank-deficient K, deflated solve (nullspace_rule.h) abi_nullspace.inc hipfact_nullspace, hipfact_solve[_device]_deflated
 //   runtime_selinv.inc  selected inverse: K^-1 on the pattern of the factor (selinv_host.h) abi_selinv.inc hipfact_selected_inverse, hipfact_inverse_diagonal[_device], hipfact_inverse_entries_device
+//   runtime_gmres.inc   GMRES(16) on the statically pivoted factor (gmres_rule.h) abi_gmres.inc hipfact_solve[_device]_gmres, _debug_gmres_dense
 //   refine_cadence.h    refinement cadence of the single solve: passes in the graph, residual checks, deferred verdicts
 //                       (pure host rules, like xcd_place.h and multi_slices.h)
 #include <hip/hip_runtime.h>
@@ -55,6 +56,7 @@
 #include "refine_cadence.h"
 #include "condest_rule.h"
 #include "nullspace_rule.h"
+#include "gmres_rule.h"
 #include "selinv_types.h"
 #include "selinv_host.h"
 #include "dd_arith.h"
@@ -68,6 +70,7 @@
 #include "runtime_condest.inc"
 #include "runtime_nullspace.inc"
 #include "runtime_selinv.inc"
+#include "runtime_gmres.inc"
 
 extern "C" {
 #include "abi_core.inc"
@@ -77,6 +80,7 @@ extern "C" {
 #include "abi_condest.inc"
 #include "abi_nullspace.inc"
 #include "abi_selinv.inc"
+#include "abi_gmres.inc"
 #include "abi_working_set.inc"
 #include "abi_krylov.inc"
 #include "abi_options.inc"

@@ -265,6 +265,10 @@ struct PlanState : FactorMemo {
   // blocks and the diagonal of D are the condition estimate's), the basis Z of the current factorisation, up to 15
   // columns (d_nullZ).  Allocated by the first such call of the state.
   DevBuf d_nblk, d_nullZ;
+  // GMRES solve (runtime_gmres.inc), N_ext each: b | z | r (the right-hand side slot of a step's solve) | a vector of
+  // zeros | the solution slot of a step's solve | the basis V, 17 columns | U, 16 columns.  They live with the plan
+  // because its solve graphs hold two of the addresses.  Allocated by the first such call of the state.
+  DevBuf d_gvec;
   // selected inverse (runtime_selinv.inc): the Z panels and W = L21 X in the layout of d_L, the Z_UU blocks (sum of u^2
   // doubles, no reuse), their offsets, the tree's arrays for the lookup and iperm; a 16-column block of the fallback.
   // Allocated by the first such call of the state (selinv_ws); Z belongs to the factorisation number selinv_for_factor
@@ -532,6 +536,14 @@ struct hipfact_handle : PlanState, SingleSolveMemo {
   bool in_deflated = false;  // (a deflated solve is running: its plain solves are not rescued themselves)
   int rescue_scope = 0;      // > 0 inside hipfact_check and hipfact_solution*: the only places the rescue applies (RescueScope)
   long null_calls = 0, null_blocks = 0, deflated_solves = 0;
+  // GMRES solve (runtime_gmres.inc): the small state of the cycle in flight (GmresDev), the partials of its sums and
+  // maxima, the pinned block the host reads behind a synchronisation; counters of hipfact_get_info (control block and
+  // partial maxima of the restart residual are the extra-precise solve's, the host entry point stages in d_xhost)
+  DevBuf d_gdev, d_gpart;
+  PinBuf h_gout;
+  void* h_gout_dev = nullptr;
+  long gmres_solves = 0, gmres_cycles = 0, gmres_steps = 0;
+  int gmres_last_status = 0;
   // selected inverse (runtime_selinv.inc): the options "selinv_route" and "selinv_fallback_max", a flag word and the
   // partial counts of the extraction kernels, the pinned words the host reads; counters of hipfact_get_info
   int selinv_route = 0;

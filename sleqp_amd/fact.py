@@ -290,6 +290,30 @@ class HipFact:
         out["defect"] = defect.value
         return sol, out
 
+    def solve_device_gmres(self, d_rhs_ptr: int, d_sol_ptr: int, deflate: int = 0, raise_singular: bool = True) -> dict:
+        """hipfact_solve_device_gmres: K z = b for device vectors by restarted GMRES(16) preconditioned with the
+        statically pivoted factor; blocks.  Returns the hipfact_gmres_info as a dict (status, cycles, steps, null_status,
+        omega, beta_rel, dz_rel) with the return code under "rc"; raise_singular = False hands HIPFACT_ESINGULAR back
+        there instead of raising."""
+        info = GmresInfo()
+        rc = self._lib.hipfact_solve_device_gmres(self._h, C.c_void_p(d_rhs_ptr), C.c_void_p(d_sol_ptr), int(deflate),
+                                                  C.byref(info))
+        if rc != 0 and not (rc == -3 and not raise_singular):
+            self._check(rc)
+        return info.as_dict(rc)
+
+    def solve_gmres(self, b, deflate: int = 0, raise_singular: bool = True):
+        """hipfact_solve_gmres: (z, info) with K z = b for a host vector; the solve for a statically pivoted factor whose
+        multipliers matter (nearly dependent rows); info as in solve_device_gmres."""
+        rhs = np.ascontiguousarray(b, dtype=np.float64)
+        assert rhs.size == self.N
+        sol = np.zeros_like(rhs)
+        info = GmresInfo()
+        rc = self._lib.hipfact_solve_gmres(self._h, _ptr(rhs), _ptr(sol), int(deflate), C.byref(info))
+        if rc != 0 and not (rc == -3 and not raise_singular):
+            self._check(rc)
+        return sol, info.as_dict(rc)
+
     def residual_device(self, d_b_ptr: int, d_z_ptr: int, d_res_ptr: int, extended: bool = True):
         """hipfact_residual_device: res = b - K z on the handle's stream (extended: double-double accumulation)."""
         self._check(self._lib.hipfact_residual_device(self._h, C.c_void_p(d_b_ptr), C.c_void_p(d_z_ptr),
@@ -485,6 +509,56 @@ class NullInfo(C.Structure):
 
 
 NULL_STATUS = ["REGULAR", "FOUND", "NONE", "BLOCK_FULL", "UNRESOLVED"]
+
+
+class GmresInfo(C.Structure):
+    """hipfact_gmres_info (include/hipfact.h)"""
+    _fields_ = [("status", C.c_int), ("cycles", C.c_int), ("steps", C.c_int), ("null_status", C.c_int),
+                ("omega", C.c_double), ("beta_rel", C.c_double), ("dz_rel", C.c_double * 2)]
+
+    def as_dict(self, rc: int = 0) -> dict:
+        return {"rc": rc, "status": self.status, "cycles": self.cycles, "steps": self.steps, "null_status": self.null_status,
+                "omega": self.omega, "beta_rel": self.beta_rel, "dz_rel": (self.dz_rel[0], self.dz_rel[1]),
+                "status_name": GMRES_STATUS[self.status] if 0 <= self.status < len(GMRES_STATUS) else str(self.status)}
+
+
+GMRES_STATUS = ["CONVERGED", "STALLED", "CYCLE_LIMIT", "NONFINITE"]
+
+
+def gmres_dense(K, Minv, b, n0: int):
+    """hipfact_debug_gmres_dense_steps: the rule of hipfact_solve_device_gmres with dense products (K and Minv, which
+    stands in for the plain solve on the statically pivoted factor, in one space; n0 rows in front of the second block),
+    on the host (no GPU).  Returns (z, info) with the steps of every cycle under "cycle_steps"."""
+    K = np.asfortranarray(K, dtype=np.float64)
+    Minv = np.asfortranarray(Minv, dtype=np.float64)
+    assert K.ndim == 2 and K.shape[0] == K.shape[1] and Minv.shape == K.shape, (K.shape, Minv.shape)
+    N = K.shape[0]
+    rhs = np.ascontiguousarray(b, dtype=np.float64)
+    assert rhs.size == N
+    z = np.zeros(N)
+    info = GmresInfo()
+    steps = np.zeros(16, dtype=np.int32)
+    rc = _lib.load().hipfact_debug_gmres_dense_steps(N, int(n0), _ptr(K), _ptr(Minv), N, _ptr(rhs), _ptr(z), C.byref(info),
+                                                     _ptr(steps), steps.size)
+    if rc != 0:
+        raise HipfactError(rc, "hipfact_debug_gmres_dense")
+    out = info.as_dict(rc)
+    out["cycle_steps"] = [int(k) for k in steps[:info.cycles]]
+    return z, out
+
+
+def gmres_hessenberg(H, beta: float):
+    """hipfact_debug_gmres_hessenberg: (y, est) of the (k + 1) x k upper Hessenberg least-squares problem
+    min ||beta e_1 - H y|| by the Givens recurrences of the rule (no GPU)."""
+    H = np.asfortranarray(H, dtype=np.float64)
+    k = H.shape[1]
+    assert H.shape == (k + 1, k), H.shape
+    y = np.empty(k)
+    est = C.c_double(0.0)
+    rc = _lib.load().hipfact_debug_gmres_hessenberg(k, _ptr(H), float(beta), _ptr(y), C.byref(est))
+    if rc != 0:
+        raise HipfactError(rc, "hipfact_debug_gmres_hessenberg")
+    return y, est.value
 
 
 class SelinvInfo(C.Structure):
