@@ -494,6 +494,72 @@ int hipfact_solve_device_gmres(hipfact_handle* h, const double* d_rhs, double* d
                                hipfact_gmres_info* info /* nullable */);
 int hipfact_solve_gmres(hipfact_handle* h, const double* rhs, double* sol, int deflate, hipfact_gmres_info* info /* nullable */);
 
+/* ---- bordered solve: a few more rows and columns on the factor of K ----------------------------------------------
+ *   M = [ K   B ] [z]   [f]        B: N x k, sparse, 1 <= k <= 64;   C: k x k symmetric (NULL: 0)
+ *       [ B^T C ] [w] = [g]
+ * solved with the factor of K as it stands, by block elimination with the k x k Schur complement S_c = C - B^T K^-1 B
+ * and refinement on residuals of the whole of M.  This is the Schur-complement update of active-set methods: a border
+ * column [a; 0] with C = 0 ADDS the constraint a^T x = gamma to the working set (w is its multiplier); a border column
+ * e_{n+i} DROPS row i (it forces y_i = 0, and w = g_i - a_i x comes back as the dropped row's slack); a general B or C
+ * covers a few dense coupling rows or a -delta softening of some constraints, which the [I A^T; A 0] detector refuses.
+ * hipfact_border_set: B is host CSC in the caller's numbering (rows in [0, N), strictly increasing within a column,
+ * finite values), C column-major.  Y = K^-1 B by the blocked solve (ceil(k / 16) blocks, refined to its usual target),
+ * G = B^T Y on the device, S_c = C - (G + G^T) / 2 and its LU with partial pivoting on the host; rcond =
+ * 1 / (||S_c||_1 ||S_c^-1||_1) from the explicit inverse.  info->status: HIPFACT_BORDER_READY; _SHIFTED when a
+ * static-pivot shift is active once Y is formed (a rank-deficient K is out of scope); _SINGULAR when a pivot is zero or
+ * not finite, Y is not finite, or rcond <= N 2^-52 (dimension x eps, the numerical-rank tolerance for the N-term sums
+ * behind S_c).  SHIFTED and SINGULAR return HIPFACT_ESINGULAR, fill info and keep NO border (an earlier one is gone
+ * too).  On READY Y, B, C, the LU and the pivots stay on the device with the plan state: (k + 4) x ld doubles,
+ * ld = N rounded up to even, plus B twice.  hipfact_border_clear drops the border ("border_k" = -1).
+ * hipfact_solve_device_bordered: d_rhs = [f; g] and d_sol = [z; w], N + k doubles each; d_sol may be d_rhs, any other
+ * overlap is HIPFACT_EINVAL.  The rule (sleqp_amd/csrc/border_rule.h), with E(r_f, r_g):
+ *       z0 = K^-1 r_f (ONE plain single solve);  t = r_g - B^T z0;  w = S_c^-1 t;  z = z0 - Y w
+ *   u = E(f, g);  pass p = 1, 2, ...:
+ *     r_f = (f - B w) - K z in double-double (f - B w in fp64 first), r_g = g - B^T z - C w
+ *     omega = max(omega_K, omega_g): omega_K the backward error of the K rows as "last_omega" defines it,
+ *             omega_g = ||r_g||_inf / (||u||_inf + ||g||_inf)
+ *     NONFINITE if either is not finite; CONVERGED if omega <= 2^-51 (the GMRES rule's target) or r = 0;
+ *     PASS_LIMIT if p reaches refine_max; du = E(r_f, r_g);
+ *     STALLED if p >= 2 and ||du_p||_inf > ||du_{p-1}||_inf / 2 - the correction is not applied; else u += du
+ * (whether a correction is applied is decided on the device, so that a pass has ONE host synchronisation; STALLED is
+ * reported behind one more residual, that of the unchanged u).  info: status, k, passes = residuals taken, the final
+ * omega, dn_rel = ||du||_inf / ||u||_inf of the last correction looked at (0: none), rcond of the set.
+ * Returns HIPFACT_OK with the status in info, whatever it is (a NaN / Inf right-hand side is NONFINITE and the caller's
+ * case); the final omega is additionally judged as the single solve's (above "fail_omega": HIPFACT_ESINGULAR, the
+ * solution reached is still written).
+ * Contract: both calls block; on entry they do what hipfact_check does; neither is "the last solve" - hipfact_solution*,
+ * "last_omega" and the refinement cadence keep describing the single solve in front, and a single solve issued
+ * afterwards gives the bits it would have given without the call; the same handle state gives the same bits on every
+ * call.  HIPFACT_EINVAL: k < 1, k > 64, an index out of range, unsorted or repeated rows, a non-finite value, a NULL
+ * array, a C that is not symmetric bit for bit.  HIPFACT_ESTATE: before a factorisation; a solve without a border; a
+ * solve after ANY later factorisation or a change of the static-pivot shift (the border is keyed on the factorisation
+ * count and the shift, as the null space is: set it again).  HIPFACT_ENOMEM when the workspace cannot be had - the
+ * handle stays usable for everything else.  No option of its own: "refine_max" and "fail_omega" apply.
+ * When it pays (scripts/border_probe.py, profiles/border_probe.txt; change + first solve, border against
+ * hipfact_assemble_kkt of the new working set + one hipfact_solve_device): on the headline workload nowhere - 1.129
+ * against 1.010 ms at k = 1, 1.811 against 1.003 ms at k = 16, 5.775 against 0.995 ms at k = 64, and 0.38 - 0.48 ms per
+ * further solve against 0.107 ms - because a superset plan re-assembles a changed working set in 0.90 ms; on a plan whose
+ * factorisation costs ten solves or more (grid3d_g37: 5.2 ms) from k = 1 up to one block of 16 columns - 4.155 against
+ * 5.666 ms at k = 1, 4.733 against 5.664 ms at k = 16, ahead for the first 14 and 8 solves behind the change - and not
+ * at k = 64 (17.463 against 5.684 ms).  A general B or C has no assembled counterpart at any cost.
+ * hipfact_get_info: "border_k" (-1: none), "border_sets", "border_solves", "border_passes" (cumulative),
+ * "border_last_status", "border_rcond".  hipfact_solve_bordered: the same for host vectors. */
+enum { HIPFACT_BORDER_READY = 0, HIPFACT_BORDER_SINGULAR = 1, HIPFACT_BORDER_SHIFTED = 2 };
+enum { HIPFACT_BORDER_CONVERGED = 0, HIPFACT_BORDER_STALLED = 1, HIPFACT_BORDER_PASS_LIMIT = 2, HIPFACT_BORDER_NONFINITE = 3 };
+typedef struct hipfact_border_info {
+  int status;     /* set: HIPFACT_BORDER_READY / _SINGULAR / _SHIFTED;  solve: CONVERGED / STALLED / PASS_LIMIT / NONFINITE */
+  int k, passes;  /* border columns; residuals taken by the solve */
+  double omega;   /* backward error of the returned [z; w] (above) */
+  double dn_rel;  /* ||du||_inf / ||u||_inf of the last correction looked at (0: none) */
+  double rcond;   /* 1 / (||S_c||_1 ||S_c^-1||_1) of the k x k Schur complement */
+} hipfact_border_info;
+int hipfact_border_set(hipfact_handle* h, int k, const int* colptr, const int* rowidx, const double* vals,
+                       const double* C /* k x k column-major, nullable = 0 */, hipfact_border_info* info /* nullable */);
+int hipfact_border_clear(hipfact_handle* h);
+int hipfact_solve_device_bordered(hipfact_handle* h, const double* d_rhs /* N + k: [f; g] */,
+                                  double* d_sol /* N + k: [z; w] */, hipfact_border_info* info /* nullable */);
+int hipfact_solve_bordered(hipfact_handle* h, const double* rhs, double* sol, hipfact_border_info* info /* nullable */);
+
 /* ---- selected inverse: the entries of K^-1 on the pattern of the factor ------------------------------------------
  * M = L D L^T is the matrix the engine factors, in pivot order: K in generic mode, the equilibrated D S D (with the
  * late variables of a dense_mode 1 plan) in saddle mode.  hipfact_selected_inverse forms Z = M^-1 on exactly the
@@ -1003,6 +1069,25 @@ int hipfact_debug_gmres_dense_steps(int N, int n0, const double* K, const double
  * y (k values) minimises ||beta e_1 - H y||_2; *est = |g_{k+1}|, the norm of that residual.  HIPFACT_EINVAL for k
  * outside [1, 16] or a NULL array. */
 int hipfact_debug_gmres_hessenberg(int k, const double* H, double beta, double* y, double* est);
+/* The k x k LU of hipfact_border_set (sleqp_amd/csrc/border_rule.h), no GPU needed; used by the tests.  S: k x k
+ * column-major; LU receives P S = L U (unit L below the diagonal), piv[j] the row exchanged with row j at step j,
+ * *rcond = 1 / (||S||_1 ||S^-1||_1) from the explicit inverse (0 behind a zero or non-finite pivot).  Returns
+ * HIPFACT_BORDER_READY or HIPFACT_BORDER_SINGULAR (such a pivot, or rcond <= N 2^-52), or HIPFACT_EINVAL for k outside
+ * [1, 64], N < 1 or a NULL array. */
+int hipfact_debug_border_lu(int k, long long N, const double* S, double* LU, int* piv, double* rcond);
+/* The rule of hipfact_border_set + hipfact_solve_device_bordered with dense products, no GPU needed; used by the
+ * tests.  K and Kinv (it stands in for the solves on the factor), N x N column-major with ld >= N; B dense N x k
+ * (leading dimension N); C k x k or NULL; c = [f; g] and u = [z; w], N + k values; residuals in long double over the
+ * whole of M, omega = ||r||_inf / (||u||_inf + ||c||_inf) (no equilibration here); pass cap `cap`.  A border that is
+ * not READY returns HIPFACT_ESINGULAR with the set's status in info.  HIPFACT_EINVAL for N < 1, k outside [1, 64],
+ * ld < N, cap < 1 or a NULL array (C apart). */
+int hipfact_debug_border_dense(int N, int k, const double* K, const double* Kinv, long long ld, const double* B,
+                               const double* C /* nullable */, const double* c, double* u, int cap,
+                               hipfact_border_info* info /* nullable */);
+/* The driver of that rule on a recorded sequence: pass p has the backward error omega[p - 1], the correction formed in
+ * it the norm dn[p - 1] (a refused correction repeats the omega in front of it).  *status, *passes as in
+ * hipfact_border_info.  HIPFACT_EINVAL when the n records end before the rule does, for cap < 1 or a NULL array. */
+int hipfact_debug_border_recorded(int n, const double* omega, const double* dn, int cap, int* status, int* passes);
 /* The refinement cadence of the single solve as a pure host function (no GPU needed; used by the tests): how many
  * correction passes the solve graphs carry, which solves take a residual, and which leave their verdict to the next tree
  * launch.  A script of events runs through the transitions the runtime calls, on one plan of one fresh handle.

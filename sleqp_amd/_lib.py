@@ -33,6 +33,8 @@ SYMBOLS = [
     "hipfact_debug_nullspace_jacobi",
     "hipfact_solve_device_gmres", "hipfact_solve_gmres", "hipfact_debug_gmres_dense", "hipfact_debug_gmres_dense_steps",
     "hipfact_debug_gmres_hessenberg",
+    "hipfact_border_set", "hipfact_border_clear", "hipfact_solve_device_bordered", "hipfact_solve_bordered",
+    "hipfact_debug_border_lu", "hipfact_debug_border_dense", "hipfact_debug_border_recorded",
     "hipfact_selected_inverse", "hipfact_inverse_diagonal_device", "hipfact_inverse_diagonal", "hipfact_inverse_entries_device",
     "hipfact_debug_selinv_host", "hipfact_debug_selinv_lookup",
     "hipfact_solve_device_extra", "hipfact_solve_extra", "hipfact_residual_device", "hipfact_debug_extra_rule", "hipfact_debug_dd_residual",
@@ -112,6 +114,15 @@ def load() -> C.CDLL:
         lib.hipfact_debug_gmres_dense.argtypes = [ci, ci, vp, vp, ll, vp, vp, vp]
         lib.hipfact_debug_gmres_dense_steps.argtypes = [ci, ci, vp, vp, ll, vp, vp, vp, vp, ci]
         lib.hipfact_debug_gmres_hessenberg.argtypes = [ci, vp, cd, vp, C.POINTER(cd)]
+    if hasattr(lib, "hipfact_border_set"):
+        ll = C.c_longlong
+        lib.hipfact_border_set.argtypes = [vp, ci, vp, vp, vp, vp, vp]
+        lib.hipfact_border_clear.argtypes = [vp]
+        lib.hipfact_solve_device_bordered.argtypes = [vp, vp, vp, vp]
+        lib.hipfact_solve_bordered.argtypes = [vp, vp, vp, vp]
+        lib.hipfact_debug_border_lu.argtypes = [ci, ll, vp, vp, vp, C.POINTER(cd)]
+        lib.hipfact_debug_border_dense.argtypes = [ci, ci, vp, vp, ll, vp, vp, vp, vp, ci, vp]
+        lib.hipfact_debug_border_recorded.argtypes = [ci, vp, vp, ci, C.POINTER(ci), C.POINTER(ci)]
     if hasattr(lib, "hipfact_selected_inverse"):
         ll = C.c_longlong
         lib.hipfact_selected_inverse.argtypes = [vp]

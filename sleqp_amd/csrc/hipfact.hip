@@ -5,7 +5,7 @@
 // state.  All numerics run on the device; there is no CPU fallback: without a
 // usable GPU hipfact_create fails with HIPFACT_EDEVICE.
 //
-// The host translation unit (the kernels are compiled separately: kernels_factor.hip / kernels_solve.hip / kernels_extra.hip / kernels_nullspace.hip / kernels_selinv.hip / kernels_gmres.hip, declared in the
+// The host translation unit (the kernels are compiled separately: kernels_factor.hip / kernels_solve.hip / kernels_extra.hip / kernels_nullspace.hip / kernels_selinv.hip / kernels_gmres.hip / kernels_border.hip, declared in the
 // generated kernels_decl.h), split by role:
 //   runtime_types.inc   buffers, plan state, the handle          abi_core.inc         create .. solution (SleqpFact)
 //   runtime_plan.inc    upload of a plan, work items             abi_working_set.inc  superset plans, assemble_kkt
@@ -19,6 +19,7 @@
 //   runtime_nullspace.inc null space of a rank-deficient K, deflated solve (nullspace_rule.h) abi_nullspace.inc hipfact_nullspace, hipfact_solve[_device]_deflated
 //   runtime_selinv.inc  selected inverse: K^-1 on the pattern of the factor (selinv_host.h) abi_selinv.inc hipfact_selected_inverse, hipfact_inverse_diagonal[_device], hipfact_inverse_entries_device
 //   runtime_gmres.inc   GMRES(16) on the statically pivoted factor (gmres_rule.h) abi_gmres.inc hipfact_solve[_device]_gmres, _debug_gmres_dense
+//   runtime_border.inc  bordered solve [K B; B^T C] on the factor of K (border_rule.h) abi_border.inc hipfact_border_set / _clear, hipfact_solve[_device]_bordered, _debug_border_*
 //   refine_cadence.h    refinement cadence of the single solve: passes in the graph, residual checks, deferred verdicts
 //                       (pure host rules, like xcd_place.h and multi_slices.h)
 #include <hip/hip_runtime.h>
@@ -57,6 +58,7 @@
 #include "condest_rule.h"
 #include "nullspace_rule.h"
 #include "gmres_rule.h"
+#include "border_rule.h"
 #include "selinv_types.h"
 #include "selinv_host.h"
 #include "dd_arith.h"
@@ -71,6 +73,7 @@
 #include "runtime_nullspace.inc"
 #include "runtime_selinv.inc"
 #include "runtime_gmres.inc"
+#include "runtime_border.inc"
 
 extern "C" {
 #include "abi_core.inc"
@@ -81,6 +84,7 @@ extern "C" {
 #include "abi_nullspace.inc"
 #include "abi_selinv.inc"
 #include "abi_gmres.inc"
+#include "abi_border.inc"
 #include "abi_working_set.inc"
 #include "abi_krylov.inc"
 #include "abi_options.inc"

@@ -269,6 +269,11 @@ struct PlanState : FactorMemo {
   // zeros | the solution slot of a step's solve | the basis V, 17 columns | U, 16 columns.  They live with the plan
   // because its solve graphs hold two of the addresses.  Allocated by the first such call of the state.
   DevBuf d_gvec;
+  // bordered solve (runtime_border.inc): Y = K^-1 B (N_ext x k, even leading dimension) and the vectors f | z | r | dz
+  // behind it, (k + 4) ld doubles (d_bvec); B as CSC and as CSR, C, the LU of the Schur complement and its pivots in one
+  // block (d_bmat).  They live with the plan because its solve graphs hold two of the addresses.  Allocated by
+  // hipfact_border_set.
+  DevBuf d_bvec, d_bmat;
   // selected inverse (runtime_selinv.inc): the Z panels and W = L21 X in the layout of d_L, the Z_UU blocks (sum of u^2
   // doubles, no reuse), their offsets, the tree's arrays for the lookup and iperm; a 16-column block of the fallback.
   // Allocated by the first such call of the state (selinv_ws); Z belongs to the factorisation number selinv_for_factor
@@ -544,6 +549,19 @@ struct hipfact_handle : PlanState, SingleSolveMemo {
   void* h_gout_dev = nullptr;
   long gmres_solves = 0, gmres_cycles = 0, gmres_steps = 0;
   int gmres_last_status = 0;
+  // bordered solve (runtime_border.inc): the small vectors of the k border rows, partial maxima, G and the control block
+  // (d_bsmall), the pinned block the host reads behind a synchronisation; the border that is set (border_k columns, -1:
+  // none) belongs to the factorisation number border_for_factor with the shift border_for_delta (another factorisation
+  // or another shift voids it); counters of hipfact_get_info
+  DevBuf d_bsmall;
+  PinBuf h_bout;
+  void* h_bout_dev = nullptr;
+  BorderMatLayout border_layout;
+  int border_k = -1, border_has_C = 0;
+  long border_for_factor = -1;
+  double border_for_delta = 0.0, border_rcond = 0.0;
+  long border_sets = 0, border_solves = 0, border_passes = 0;
+  int border_last_status = 0;
   // selected inverse (runtime_selinv.inc): the options "selinv_route" and "selinv_fallback_max", a flag word and the
   // partial counts of the extraction kernels, the pinned words the host reads; counters of hipfact_get_info
   int selinv_route = 0;

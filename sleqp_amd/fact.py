@@ -314,6 +314,55 @@ class HipFact:
             self._check(rc)
         return sol, info.as_dict(rc)
 
+    def border_set(self, B, Cmat=None, raise_singular: bool = True) -> dict:
+        """hipfact_border_set: borders the factored K with the columns of B (N x k, anything scipy.sparse.csc_matrix
+        takes, 1 <= k <= 64) and the symmetric k x k block Cmat (None: zero) - the matrix [K B; B^T C] of solve_bordered.
+        Returns the hipfact_border_info as a dict (status READY / SINGULAR / SHIFTED, k, rcond) with the return code
+        under "rc"; raise_singular = False hands HIPFACT_ESINGULAR back there instead of raising."""
+        import scipy.sparse as sp
+
+        B = sp.csc_matrix(B, dtype=np.float64)
+        B.sort_indices()
+        assert B.shape[0] == self.N, (B.shape, self.N)
+        k = B.shape[1]
+        cp = np.ascontiguousarray(B.indptr, dtype=np.int32)
+        ri = np.ascontiguousarray(B.indices, dtype=np.int32) if B.nnz else np.zeros(1, dtype=np.int32)
+        cv = np.ascontiguousarray(B.data, dtype=np.float64) if B.nnz else np.zeros(1)
+        Cm = None if Cmat is None else np.asfortranarray(Cmat, dtype=np.float64)
+        assert Cm is None or Cm.shape == (k, k), (Cm.shape, k)
+        info = BorderInfo()
+        rc = self._lib.hipfact_border_set(self._h, k, _ptr(cp), _ptr(ri), _ptr(cv), _ptr(Cm), C.byref(info))
+        if rc != 0 and not (rc == -3 and not raise_singular):
+            self._check(rc)
+        return info.as_dict(rc, BORDER_SET_STATUS)
+
+    def border_clear(self):
+        """hipfact_border_clear: drops the border ("border_k" = -1)"""
+        self._check(self._lib.hipfact_border_clear(self._h))
+
+    def solve_device_bordered(self, d_rhs_ptr: int, d_sol_ptr: int, raise_singular: bool = True) -> dict:
+        """hipfact_solve_device_bordered: [K B; B^T C] [z; w] = [f; g] for device vectors of N + k doubles on the factor
+        of K and the border of border_set; blocks.  Returns the hipfact_border_info as a dict (status, k, passes, omega,
+        dn_rel, rcond) with the return code under "rc"."""
+        info = BorderInfo()
+        rc = self._lib.hipfact_solve_device_bordered(self._h, C.c_void_p(d_rhs_ptr), C.c_void_p(d_sol_ptr), C.byref(info))
+        if rc != 0 and not (rc == -3 and not raise_singular):
+            self._check(rc)
+        return info.as_dict(rc, BORDER_STATUS)
+
+    def solve_bordered(self, c, raise_singular: bool = True):
+        """hipfact_solve_bordered: (u, info) with [K B; B^T C] u = c for a host vector c = [f; g] of N + k values; info
+        as in solve_device_bordered."""
+        k = int(self.info("border_k"))
+        rhs = np.ascontiguousarray(c, dtype=np.float64)
+        assert k < 1 or rhs.size == self.N + k, (rhs.size, self.N, k)
+        sol = np.zeros_like(rhs)
+        info = BorderInfo()
+        rc = self._lib.hipfact_solve_bordered(self._h, _ptr(rhs), _ptr(sol), C.byref(info))
+        if rc != 0 and not (rc == -3 and not raise_singular):
+            self._check(rc)
+        return sol, info.as_dict(rc, BORDER_STATUS)
+
     def residual_device(self, d_b_ptr: int, d_z_ptr: int, d_res_ptr: int, extended: bool = True):
         """hipfact_residual_device: res = b - K z on the handle's stream (extended: double-double accumulation)."""
         self._check(self._lib.hipfact_residual_device(self._h, C.c_void_p(d_b_ptr), C.c_void_p(d_z_ptr),
@@ -559,6 +608,68 @@ def gmres_hessenberg(H, beta: float):
     if rc != 0:
         raise HipfactError(rc, "hipfact_debug_gmres_hessenberg")
     return y, est.value
+
+
+class BorderInfo(C.Structure):
+    """hipfact_border_info (include/hipfact.h)"""
+    _fields_ = [("status", C.c_int), ("k", C.c_int), ("passes", C.c_int), ("omega", C.c_double), ("dn_rel", C.c_double),
+                ("rcond", C.c_double)]
+
+    def as_dict(self, rc: int = 0, names=()) -> dict:
+        return {"rc": rc, "status": self.status, "k": self.k, "passes": self.passes, "omega": self.omega,
+                "dn_rel": self.dn_rel, "rcond": self.rcond,
+                "status_name": names[self.status] if 0 <= self.status < len(names) else str(self.status)}
+
+
+BORDER_SET_STATUS = ["READY", "SINGULAR", "SHIFTED"]
+BORDER_STATUS = ["CONVERGED", "STALLED", "PASS_LIMIT", "NONFINITE"]
+
+
+def border_lu(S, N: int):
+    """hipfact_debug_border_lu: (status, LU, piv, rcond) of the k x k matrix S by the LU of hipfact_border_set (no GPU)"""
+    S = np.asfortranarray(S, dtype=np.float64)
+    k = S.shape[0]
+    assert S.shape == (k, k), S.shape
+    LU = np.zeros((k, k), order="F")
+    piv = np.zeros(k, dtype=np.int32)
+    rcond = C.c_double(0.0)
+    st = _lib.load().hipfact_debug_border_lu(k, int(N), _ptr(S), _ptr(LU), _ptr(piv), C.byref(rcond))
+    if st < 0:
+        raise HipfactError(st, "hipfact_debug_border_lu")
+    return st, LU, piv, rcond.value
+
+
+def border_dense(K, Kinv, B, Cmat, c, cap: int = 10):
+    """hipfact_debug_border_dense: the rule of border_set + solve_bordered with dense products (Kinv stands in for the
+    solves on the factor), on the host (no GPU).  Returns (u, info); a border that is not READY gives rc -3 and the
+    set's status."""
+    K = np.asfortranarray(K, dtype=np.float64)
+    Kinv = np.asfortranarray(Kinv, dtype=np.float64)
+    B = np.asfortranarray(B, dtype=np.float64)
+    N, k = B.shape
+    assert K.shape == (N, N) and Kinv.shape == (N, N), (K.shape, Kinv.shape, B.shape)
+    Cm = None if Cmat is None else np.asfortranarray(Cmat, dtype=np.float64)
+    rhs = np.ascontiguousarray(c, dtype=np.float64)
+    assert rhs.size == N + k
+    u = np.zeros(N + k)
+    info = BorderInfo()
+    rc = _lib.load().hipfact_debug_border_dense(N, k, _ptr(K), _ptr(Kinv), N, _ptr(B), _ptr(Cm), _ptr(rhs), _ptr(u), int(cap),
+                                                C.byref(info))
+    if rc not in (0, -3):
+        raise HipfactError(rc, "hipfact_debug_border_dense")
+    return u, info.as_dict(rc, BORDER_STATUS if rc == 0 else BORDER_SET_STATUS)
+
+
+def border_recorded(omega, dn, cap: int = 10):
+    """hipfact_debug_border_recorded: (status, passes) of the rule's driver on a recorded sequence (no GPU)"""
+    om = np.ascontiguousarray(omega, dtype=np.float64)
+    d = np.ascontiguousarray(dn, dtype=np.float64)
+    assert om.size == d.size
+    st, ps = C.c_int(-1), C.c_int(0)
+    rc = _lib.load().hipfact_debug_border_recorded(om.size, _ptr(om), _ptr(d), int(cap), C.byref(st), C.byref(ps))
+    if rc != 0:
+        raise HipfactError(rc, "hipfact_debug_border_recorded")
+    return st.value, ps.value
 
 
 class SelinvInfo(C.Structure):
