@@ -726,6 +726,29 @@ int hipfact_spmat_mult_device(hipfact_spmat* M, int trans, const double* d_x, do
 int hipfact_steihaug_solve(hipfact_handle* h, hipfact_spmat* hess, const double* gradient, double trust_radius,
                            double rel_tol, int max_iter, double* newton_step, double* tr_dual, int* iterations);
 
+/* What the loops leave on the handle (hipfact_steihaug_solve, hipfact_tr_solve*, hipfact_lsqr_solve).  The result of a
+ * loop depends on its arguments, the factorisation and the options only, once a single solve of the factorisation has
+ * been judged (before that the loops keep the host in every iteration).  Its projections are single solves of the
+ * handle in every respect but one: they run in the loop's own vectors, so hipfact_solution* still return the single
+ * solve in front of the loop.  Unlike the blocked, extra-precise, GMRES, bordered and selected-inverse calls they ARE
+ * counted: "num_solve" advances by the number of projections, they count towards "top_block_after", and they stand in
+ * the check cadence of the single solve ("refine_check_every", "refine_check_backoff") - by one of two routes:
+ *   (a) A CADENCE projection is queued and judged exactly as hipfact_solve_device queues and judges a solve: it advances
+ *       the interval by one solve, takes a residual where the interval says so, and only then moves "num_checked" (by
+ *       one), "num_passes" (by the passes it applied) and "last_omega" / "last_iters" (to its verdict).  These are:
+ *       every projection of hipfact_lsqr_solve; the first projection of a trust-region loop; every projection of a
+ *       trust-region loop that keeps the host in every iteration (no explicit Hessian, a factorisation not yet
+ *       judged, or one whose solves carry a correction pass, as on a statically pivoted factor); and in
+ *       hipfact_tr_solve* the projections of the iterations behind the device-controlled phase.
+ *   (b) A projection of the device-controlled phase takes no residual and does not stand in the cadence: it moves
+ *       "num_solve" and nothing else.  The last of them is verified with one residual when the phase ends.  That
+ *       residual is no check of the cadence either: it moves none of the keys above.  Should it fail, the
+ *       factorisation's judgement is withdrawn and the call starts over by route (a); only that run is counted.
+ * "kappa_est" is the factorisation's and does not move.  So "num_solve", "num_checked", "num_passes", "last_omega" and
+ * "last_iters" behind a loop are those of a handle that has made the same COUNTED calls (hipfact_solve,
+ * hipfact_solve_device, the loops) in the same order since the factorisation, bit for bit: the calls that are not
+ * counted change nothing in between, wherever they stand. */
+
 /* ---- matrix-free Hessian, Lanczos (the reference's default EQP solver) ---- */
 
 /* product = H direction for host n-vectors; returns 0 on success.  The SLEQP

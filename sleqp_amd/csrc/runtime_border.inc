@@ -242,7 +242,9 @@ struct BorderDeviceExec {
   int first() {
     {
       Turn turn(h);
-      HCHECK(h, hipMemsetAsync(h->d_xctl.p, 0, sizeof(RefineCtl), h->stream));
+      // (d_xctl, shared with the extra-precise and the GMRES solve, needs no clearing, here as there: every verdict of
+      // these loops is a FIRST one, which writes the whole block and takes nothing from it but seq, a count that only
+      // the single solve's own block is ever asked for - on a fresh handle it counts on from whatever the allocation held)
       HCHECK(h, hipMemcpyAsync(r, f, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
       LAUNCH(PC_RESID, k_border_norm, dim3(1), dim3(64), 0, (int)BORDER_NORM_G, 0, 0, (const double*)nullptr, k, g, ctl, &pin_dev->B);
     }

@@ -239,7 +239,7 @@ static int solve_extra_device(hipfact_handle* h, const double* d_rhs, double* d_
     rc = hipMemcpyAsync(h->d_xvec.p, d_rhs, N * sizeof(double), hipMemcpyDeviceToDevice, h->stream) == hipSuccess
              ? HIPFACT_OK
              : HIPFACT_EDEVICE;
-    if (rc == HIPFACT_OK) rc = hipMemsetAsync(h->d_xctl.p, 0, sizeof(RefineCtl), h->stream) == hipSuccess ? HIPFACT_OK : HIPFACT_EDEVICE;
+    // (d_xctl is not cleared: the verdicts of extra_loop are all first ones, see BorderDeviceExec::first)
     if (rc == HIPFACT_OK && defl) {
       Turn turn(h);
       deflate_async(h, *defl, h->d_xvec.as<double>(), static_cast<double*>(h->h_nout_dev));

@@ -112,7 +112,7 @@ struct GmresDeviceExec {
     Turn turn(h);
     HCHECK(h, hipMemsetAsync(z, 0, (size_t)N * sizeof(double), h->stream));
     HCHECK(h, hipMemsetAsync(zeros, 0, (size_t)N * sizeof(double), h->stream));
-    HCHECK(h, hipMemsetAsync(h->d_xctl.p, 0, sizeof(RefineCtl), h->stream));
+    // (d_xctl is not cleared: the verdicts of residual() are all first ones, see BorderDeviceExec::first)
     if (defl) deflate_async(h, *defl, b, nullptr);
     return HIPFACT_OK;
   }
