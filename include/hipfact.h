@@ -1038,6 +1038,18 @@ int hipfact_debug_multi_slices(int u, int slice_rows, int* tile_bounds /* cap + 
  * "leaf_schur_levels" / "leaf_schur_items" count what the current plan launches at the edge of 96. */
 int hipfact_debug_schur_items(int u, int leaf);
 
+/* The two host rules of the sparse products (hipfact_spmat_mult_*), as pure host functions (no GPU needed; used by the
+ * tests).  row_blocks: the row blocks the streaming product walks over the rows of a CSR pattern (ptr: nrows + 1
+ * ascending offsets): consecutive rows with at most 2044 entries and at most 4096 rows together, a longer row is a
+ * block of its own.  Returns the number of blocks and, when first_rows is not NULL and that number is <= cap, writes
+ * the first row of every block and nrows behind them (number + 1 values); HIPFACT_EINVAL for nrows < 0, NULL or
+ * descending ptr.  lanes: the lanes per row (1, 4, 16 or 64) of the lanes-per-row product for a matrix with
+ * avg_per_row entries per row (symmetric product: 2 nnz / n).  hipfact_spmat_create and hipfact_spmat_mult_device use
+ * the same rules; info "spmv_last_lanes" is the lanes per row of the last product of the handle (0: it streamed, -1:
+ * none yet), "spmv_stream_runs" the number of streamed products. */
+int hipfact_debug_spmat_row_blocks(int nrows, const int* ptr, int* first_rows /* cap + 1 values */, int cap);
+int hipfact_debug_spmv_lanes(double avg_per_row);
+
 /* The stopping rule of hipfact_solve_device_extra as a pure host function (no GPU needed; used by the tests), applied
  * to a recorded sequence of norms: dn / zn hold npasses x nblocks values, pass by pass (nblocks 1 or 2, pass_cap >= 1,
  * else HIPFACT_EINVAL).  Returns the number of passes it looked at (it stops where the solve would); *status is

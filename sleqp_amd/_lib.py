@@ -44,6 +44,7 @@ SYMBOLS = [
     "hipfact_spmat_mult_vec", "hipfact_spmat_mult_vec_trans", "hipfact_spmat_mult_vec_sym",
     "hipfact_spmat_mult_device", "hipfact_steihaug_solve", "hipfact_tr_solve", "hipfact_tr_solve_ex", "hipfact_lsqr_solve", "hipfact_tridiag_tr", "hipfact_set_option", "hipfact_get_info", "hipfact_debug_copy", "hipfact_debug_pool_selftest",
     "hipfact_debug_place_rows", "hipfact_debug_place_items", "hipfact_debug_multi_slices", "hipfact_debug_schur_items", "hipfact_debug_refine_cadence", "hipfact_plan_create",
+    "hipfact_debug_spmat_row_blocks", "hipfact_debug_spmv_lanes",
     "hipfact_plan_free", "hipfact_plan_error", "hipfact_plan_array", "hipfact_plan_scalar",
 ]
 
@@ -158,6 +159,9 @@ def load() -> C.CDLL:
         lib.hipfact_debug_place_items.argtypes = [ci, vp, ci, vp, vp]
     if hasattr(lib, "hipfact_debug_multi_slices"):
         lib.hipfact_debug_multi_slices.argtypes = [ci, ci, vp, ci]
+    if hasattr(lib, "hipfact_debug_spmat_row_blocks"):
+        lib.hipfact_debug_spmat_row_blocks.argtypes = [ci, vp, vp, ci]
+        lib.hipfact_debug_spmv_lanes.argtypes = [cd]
     if hasattr(lib, "hipfact_debug_schur_items"):
         lib.hipfact_debug_schur_items.argtypes = [ci, ci]
     if hasattr(lib, "hipfact_debug_refine_cadence"):

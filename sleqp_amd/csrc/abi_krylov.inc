@@ -16,6 +16,20 @@ static std::vector<int> spmat_row_blocks(int nrows, const int* ptr) {
   return rb;
 }
 
+// the two host rules of the products as pure host functions (no device, no handle): the row blocks k_spmv_stream walks
+// and the lanes per row of k_spmv_csr
+int hipfact_debug_spmat_row_blocks(int nrows, const int* ptr, int* first_rows, int cap) {
+  if (nrows < 0 || !ptr) return HIPFACT_EINVAL;
+  for (int r = 0; r < nrows; ++r)
+    if (ptr[r + 1] < ptr[r]) return HIPFACT_EINVAL;
+  const std::vector<int> rb = spmat_row_blocks(nrows, ptr);
+  const int nblk = (int)rb.size() - 1;
+  if (first_rows && nblk <= cap)
+    for (int b = 0; b <= nblk; ++b) first_rows[b] = rb[b];
+  return nblk;
+}
+int hipfact_debug_spmv_lanes(double avg_per_row) { return spmv_lanes(avg_per_row); }
+
 int hipfact_spmat_create(hipfact_handle* h, int num_rows, int num_cols, const int* colptr, const int* rowidx,
                          const double* vals, hipfact_spmat** out) {
   int rc = enter(h);
@@ -146,10 +160,14 @@ int hipfact_spmat_mult_device(hipfact_spmat* M, int trans, const double* d_x, do
     hipLaunchKernelGGL(k_spmv_stream, dim3(std::min(nb, 256 * 16)), dim3(SPMV_T), 0, st, nb,
                        trans == 1 ? M->rb.as<int>() : M->trb.as<int>(), ptr, idx, val, M->nnz, d_x, d_y);
     HCHECK(h, hipGetLastError());
+    h->spmv_last_lanes = 0;
+    ++h->spmv_stream_runs;
     return HIPFACT_OK;
   }
-  launch_spmv(st, spmv_lanes(avg), nrows, ptr, idx, val, ptr2, idx2, val2, d_x, d_y);
+  const int L = spmv_lanes(avg);
+  launch_spmv(st, L, nrows, ptr, idx, val, ptr2, idx2, val2, d_x, d_y);
   HCHECK(h, hipGetLastError());
+  h->spmv_last_lanes = L;
   return HIPFACT_OK;
 }
 

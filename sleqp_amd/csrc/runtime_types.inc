@@ -334,6 +334,8 @@ struct hipfact_handle : PlanState, SingleSolveMemo {
   bool assemble_superset = true;  // hipfact_assemble_kkt analyses a superset structure of J instead of K itself
   bool spmv_stream = true;        // y = M x / M^T x as one stream through LDS (k_spmv_stream) from spmv_stream_min entries on
   long long spmv_stream_min = 4 << 20;  // (a matrix of a few MB lives in the Infinity Cache: there the lanes-per-row kernel is as fast, 5.5 vs 6.2 us at 10^6 entries)
+  int spmv_last_lanes = -1;       // what the last hipfact_spmat_mult_device launched: lanes per row of k_spmv_csr, 0 = k_spmv_stream (-1: no product yet)
+  long long spmv_stream_runs = 0; // products of this handle that went through k_spmv_stream
   bool exact_pattern = false;     // hipfact_set_matrix analyses the pattern of K itself, unit rows of active bounds included (no working-set maps: what hipfact_reduced_matrix needs)
   bool superset_vtable = true;    // hipfact_set_matrix recognises the rows of an augmented K and reuses superset plans (vtable_superset.inc)
   std::unique_ptr<VirtualJ> vj{new VirtualJ};

@@ -450,6 +450,39 @@ def test_assembly_bit_exact(fact):
         N, kc, kr, kd = oracle.fill_aug_jac(n, m, J.indptr, J.indices, J.data, vi, ci)
         assert K.num_cols == N
         assert np.array_equal(K.cols, kc) and np.array_equal(K.rows, kr) and np.array_equal(K.data, kd)
+    # the chunk edges of the single-block scan (k_asm_scan: chunks of 1024 columns, then the |W| + 1 trailing column
+    # pointers in strides of 1024): n one short of a chunk, a chunk, one more, two chunks, one more - with a random
+    # working set, an empty one (N = n: only kp[n] lies behind the scan), every bound active (|W| = n = 1025: the
+    # trailing loop takes a second pass), every row active with |W| = 1100, and a Jacobian with empty columns
+    for n, m, bounds, rows, empty_cols in [(1023, 400, "some", "some", False), (1024, 400, "none", "none", False),
+                                           (1025, 400, "all", "none", False), (2048, 1100, "none", "all", False),
+                                           (2049, 600, "some", "some", True)]:
+        J = synth.uniform_jacobian(n, m, 4, 3)
+        if empty_cols:
+            J = sp.lil_matrix(J)
+            gone = np.unique(np.concatenate([[0, n - 1], np.arange(3, n, 7), np.arange(1500, 1540)]))
+            J[:, gone] = 0.0
+            J = sp.csc_matrix(J)
+            J.eliminate_zeros()
+            J.sort_indices()
+            assert np.all(np.diff(J.indptr)[gone] == 0) and J.shape == (m, n)
+        # (with empty columns the bounds sit on those: the unit rows stay independent of the thinned rows of J)
+        av = {"some": np.sort(rng.choice(gone if empty_cols else n, n // 10, replace=False)), "none": np.zeros(0, int),
+              "all": np.arange(n)}[bounds]
+        vi = np.full(n, -1, dtype=np.int32)
+        vi[av] = np.arange(av.size)
+        held = np.flatnonzero(np.diff(sp.csr_matrix(J).indptr) > 0)  # (an active row keeps at least one entry)
+        ac = {"some": np.sort(rng.choice(held, (2 * held.size) // 3, replace=False)), "none": np.zeros(0, int),
+              "all": np.arange(m)}[rows]
+        assert rows != "all" or held.size == m
+        ci = np.full(m, -1, dtype=np.int32)
+        ci[ac] = av.size + np.arange(ac.size)
+        W = av.size + ac.size
+        assert {"none": W == 0, "all": W >= 1025, "some": W > 0}[bounds if rows == "none" else rows]
+        K = fact.assemble_kkt(SleqpMat.from_scipy(J), vi, ci, W)
+        N, kc, kr, kd = oracle.fill_aug_jac(n, m, J.indptr, J.indices, J.data, vi, ci)
+        assert K.num_cols == N == n + W
+        assert np.array_equal(K.cols, kc) and np.array_equal(K.rows, kr) and np.array_equal(K.data, kd)
 
 
 def _ws(n, m, rng, row_frac, bound_frac):
