@@ -802,6 +802,63 @@ int hipfact_tr_solve_ex(hipfact_handle* h, int method, hipfact_spmat* hess, hipf
                         const double* gradient, double trust_radius, double rel_tol, int max_iter, double* newton_step,
                         double* tr_dual, int* iterations, hipfact_tr_extra* extra);
 
+/* ---- the Hessian as a device operator: H0 + J_r' J_r + shift I ------------ */
+
+/* The Hessian of the trust-region loops as a sum of device-resident parts,
+ *     H = sym(H0) + J_r' J_r + shift I.
+ * Least-squares problems (SLEQP_FUNC_TYPE_LSQ) are the case it is made for: their Hessian product is
+ * lsq_func_hess_product (lsq.c:211-263), H d = J_r' (J_r d) + lm_factor d, flagged SLEQP_FUNC_HESS_PSD (lsq.c:362-365),
+ * so TR_SOLVER = AUTO runs the CG solver on it (newton.c:97-109): the default EQP path of every LSQ problem.  J_r' J_r is
+ * never formed (one residual that touches every variable makes it a dense n x n matrix); J_r is the `jac` of
+ * hipfact_lsqr_op, resident in both orientations.  The same operator gives Levenberg-Marquardt and proximal shifts on an
+ * explicit Hessian (H0 + shift I) and augmented-Lagrangian curvature (H0 + J' J) without uploading a matrix again.
+ *   hess    H0: lower triangle, n x n, on this handle, or NULL
+ *   gn_jac  J_r: r x n, on this handle, r >= 0, or NULL; adds J_r' J_r
+ *   shift   adds shift I; any finite value (a negative one makes H indefinite: GLTR, negative-curvature exits)
+ *   prod    the matrix-free product of hipfact_tr_solve; only alone (hess and gn_jac NULL, shift 0), with `user`
+ * A product is two launches: t = J_r x (the product of hipfact_spmat_mult_device into an r-vector of the handle, allocated
+ * on first use and grown on demand; a J_r with a row of more than 512 entries per lane of that product - one residual
+ * that touches every variable - goes through its streaming kernel whatever its size, which sums such a row with a whole
+ * workgroup), then per row i of n one running sum per lane in a fixed order: the row of sym(H0)
+ * as the loops of hipfact_tr_solve_ex walk it, then the row of J_r' (the matrix's column arrays) against t, then the sum
+ * over the row's lanes, then shift x_i, fused.  Lanes per row (1 / 4 / 16 / 64) from the entries per row of that sweep,
+ * (2 nnz(H0) + nnz(J_r)) / n, by the rule of the products.  The same handle state gives the same bits on every call; the
+ * host-driven loops, the device-controlled loops and hipfact_hess_op_apply_device form the product of one vector with
+ * the same bits. */
+typedef struct hipfact_hess_op
+{
+  hipfact_spmat* hess;
+  hipfact_spmat* gn_jac;
+  double shift;
+  hipfact_hess_prod_fn prod;
+  void* user;
+} hipfact_hess_op;
+
+/* hipfact_tr_solve_ex on the operator above: its contract in everything else - the time limit, the Rayleigh bounds,
+ * tr_dual, the zero step of Steihaug at the iteration cap, the counted projections and the cadence rules.  The
+ * device-controlled loops run under the conditions of hipfact_tr_solve_ex whenever the operator has no `prod`; with a
+ * Gauss-Newton term or a shift an iteration is four launches instead of three (t = J_r g in front of the product).  An
+ * operator that is `hess` and nothing else launches the kernels of hipfact_tr_solve_ex: its result is bit-identical.
+ * HIPFACT_EINVAL for a NULL op, an op with nothing in it, `prod` beside anything else, a matrix of another handle, a
+ * non-finite shift - and, behind HIPFACT_ESTATE before a factorisation, a hess that is not n x n or gn_jac->cols != n.
+ * HIPFACT_ENOMEM when the r-vector cannot be had; the handle stays usable.  Info "hess_op_solves": calls that passed
+ * the operator's checks; "hess_op_products": products formed under this call and hipfact_hess_op_apply_device, on
+ * either loop (a device-controlled loop counts the products in front of its stop).
+ * When it pays (scripts/hess_op_probe.py, profiles/hess_op_probe.txt: n = 1e5, m = 5e4, J_r 2e5 x 1e5 with 5 entries per
+ * row, fresh processes): always against the callback route - 0.119 ms per CG and 0.116 ms per GLTR iteration against 1.99
+ * and 2.02 with the two products formed by scipy on the host (17 x), 0.250 / 0.245 against 1.91 / 1.88 when one residual
+ * touches every variable (7.6 x).  Against an explicitly assembled tril(J_r' J_r + shift I), where that matrix can be
+ * had at all (2.1e6 entries for this J_r; 60 GB with the dense residual), the operator is no slower: 0.119 against 0.127
+ * ms per CG iteration - the fourth launch costs less than the second matrix's longer rows.  */
+int hipfact_tr_solve_op(hipfact_handle* h, int method, const hipfact_hess_op* op, const double* gradient,
+                        double trust_radius, double rel_tol, int max_iter, double* newton_step, double* tr_dual,
+                        int* iterations, hipfact_tr_extra* extra);
+
+/* d_y = H d_x for device vectors of n doubles that do not overlap (n: the variables of the factorised saddle matrix),
+ * queued on the handle's stream like hipfact_spmat_mult_device; with `prod` the callback runs on staged host copies.
+ * Return codes as above. */
+int hipfact_hess_op_apply_device(hipfact_handle* h, const hipfact_hess_op* op, const double* d_x, double* d_y);
+
 /* ---- Gauss-Newton LSQR (least-squares problems, TR_SOLVER = LSQR) ------- */
 
 /* Residual Jacobian J_r (r x n) as a product on host vectors: trans = 0: out (r) = J_r in (n); trans = 1: out (n) =

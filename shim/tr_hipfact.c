@@ -10,7 +10,10 @@
  * by default the product is computed by the problem's own callback on the host, with one n-vector
  * crossing PCIe in each direction per iteration (trlib_solver.c:542-602 does the same product per
  * iteration, plus the projection's two crossings that stay on the device here).  Callers that can
- * provide the Hessian as an explicit matrix (sleqp_hipfact_tr_set_hessian) avoid that as well.
+ * provide the Hessian as an explicit matrix (sleqp_hipfact_tr_set_hessian) avoid that as well, and so do
+ * least-squares problems (SLEQP_FUNC_TYPE_LSQ), whose Hessian product is J_r' (J_r d) + lm_factor d
+ * (lsq_func_hess_product, lsq.c:211-263): with the residual Jacobian resident in HBM
+ * (sleqp_hipfact_tr_set_gauss_newton) the product is a device operator, hipfact_tr_solve_op.
  *
  * The projection comes from the factorisation inside the hipfact handle of the augmented Jacobian
  * (aug_jac_hipfact.c); the solver holds its own reference to that handle (sleqp_hipfact_tr_bind) —
@@ -39,6 +42,12 @@ struct SleqpHipfactTR
   hipfact_spmat* hessian; /* explicit Hessian, optional */
   int hess_nnz;
   uint64_t hess_pattern_hash;
+
+  hipfact_spmat* lsq_jac; /* residual Jacobian J_r of the Gauss-Newton Hessian, optional */
+  int lsq_nnz;
+  int lsq_rows;
+  uint64_t lsq_pattern_hash;
+  double lm_factor;
 
   int method; /* HIPFACT_TR_GLTR / HIPFACT_TR_STEIHAUG */
   int max_iter;
@@ -87,6 +96,11 @@ hipfact_tr_free(void** star)
   if (solver->hessian)
   {
     hipfact_spmat_free(&solver->hessian);
+  }
+
+  if (solver->lsq_jac)
+  {
+    hipfact_spmat_free(&solver->lsq_jac);
   }
 
   hipfact_free(&solver->handle); /* our reference */
@@ -177,19 +191,45 @@ tr_callback_solve(SleqpAugJac* jacobian,
   int iterations = 0;
   /* time_limit: seconds or SLEQP_NONE (-1), tr/tr_solver.c:18-21,47 - the same convention as hipfact_tr_extra */
   hipfact_tr_extra extra = {.time_limit = time_limit, .timed_out = 0, .min_rayleigh = 1., .max_rayleigh = 1.};
-  const int status       = hipfact_tr_solve_ex(solver->handle,
-                                         solver->method,
-                                         solver->hessian,
-                                         solver->hessian ? NULL : hess_prod_callback,
-                                         solver,
-                                         solver->dense_gradient,
-                                         trust_radius,
-                                         solver->rel_tol,
-                                         solver->max_iter,
-                                         solver->dense_step,
-                                         tr_dual,
-                                         &iterations,
-                                         &extra);
+  int status;
+
+  if (solver->lsq_jac)
+  {
+    /* lsq_func_hess_product (lsq.c:211-263) as a device operator, on top of the explicit Hessian if one is set */
+    const hipfact_hess_op op = {.hess   = solver->hessian,
+                                .gn_jac = solver->lsq_jac,
+                                .shift  = solver->lm_factor,
+                                .prod   = NULL,
+                                .user   = NULL};
+
+    status = hipfact_tr_solve_op(solver->handle,
+                                 solver->method,
+                                 &op,
+                                 solver->dense_gradient,
+                                 trust_radius,
+                                 solver->rel_tol,
+                                 solver->max_iter,
+                                 solver->dense_step,
+                                 tr_dual,
+                                 &iterations,
+                                 &extra);
+  }
+  else
+  {
+    status = hipfact_tr_solve_ex(solver->handle,
+                                 solver->method,
+                                 solver->hessian,
+                                 solver->hessian ? NULL : hess_prod_callback,
+                                 solver,
+                                 solver->dense_gradient,
+                                 trust_radius,
+                                 solver->rel_tol,
+                                 solver->max_iter,
+                                 solver->dense_step,
+                                 tr_dual,
+                                 &iterations,
+                                 &extra);
+  }
 
   solver->min_rayleigh = extra.min_rayleigh;
   solver->max_rayleigh = extra.max_rayleigh;
@@ -278,6 +318,69 @@ sleqp_hipfact_tr_set_hessian(SleqpHipfactTR* solver, const SleqpMat* hess_lower)
 }
 
 SLEQP_RETCODE
+sleqp_hipfact_tr_set_gauss_newton(SleqpHipfactTR* solver, const SleqpMat* lsq_jac, double lm_factor)
+{
+  if (!lsq_jac)
+  {
+    if (solver->lsq_jac)
+    {
+      hipfact_spmat_free(&solver->lsq_jac);
+    }
+    solver->lm_factor = 0.;
+    return SLEQP_OKAY;
+  }
+
+  const int num_variables = sleqp_problem_num_vars(solver->problem);
+
+  assert(sleqp_mat_num_cols(lsq_jac) == num_variables);
+
+  if (!solver->handle)
+  {
+    sleqp_raise(SLEQP_INTERNAL_ERROR, "hipfact TR solver: bind a factorisation before setting the residual Jacobian");
+  }
+
+  const int nnz       = sleqp_mat_nnz(lsq_jac);
+  const int rows      = sleqp_mat_num_rows(lsq_jac);
+  const uint64_t hash = pattern_hash(lsq_jac);
+
+  solver->lm_factor = lm_factor;
+
+  if (solver->lsq_jac && nnz == solver->lsq_nnz && rows == solver->lsq_rows && hash == solver->lsq_pattern_hash)
+  {
+    /* same pattern (checked, not assumed): values only */
+    const int status = hipfact_spmat_update_values(solver->lsq_jac, sleqp_mat_data(lsq_jac));
+    if (status == HIPFACT_OK)
+    {
+      return SLEQP_OKAY;
+    }
+  }
+
+  if (solver->lsq_jac)
+  {
+    hipfact_spmat_free(&solver->lsq_jac);
+  }
+
+  const int status = hipfact_spmat_create(solver->handle,
+                                          rows,
+                                          num_variables,
+                                          sleqp_mat_cols(lsq_jac),
+                                          sleqp_mat_rows(lsq_jac),
+                                          sleqp_mat_data(lsq_jac),
+                                          &solver->lsq_jac);
+
+  if (status != HIPFACT_OK)
+  {
+    sleqp_raise(SLEQP_INTERNAL_ERROR, "Caught hipfact error <%d> (%s)", status, hipfact_last_error(solver->handle));
+  }
+
+  solver->lsq_nnz          = nnz;
+  solver->lsq_rows         = rows;
+  solver->lsq_pattern_hash = hash;
+
+  return SLEQP_OKAY;
+}
+
+SLEQP_RETCODE
 sleqp_hipfact_tr_bind(SleqpHipfactTR* solver, struct hipfact_handle* handle)
 {
   if (!handle)
@@ -293,6 +396,11 @@ sleqp_hipfact_tr_bind(SleqpHipfactTR* solver, struct hipfact_handle* handle)
   if (solver->hessian)
   {
     hipfact_spmat_free(&solver->hessian); /* lives on the old handle */
+  }
+
+  if (solver->lsq_jac)
+  {
+    hipfact_spmat_free(&solver->lsq_jac);
   }
 
   if (solver->handle)

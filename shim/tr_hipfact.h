@@ -42,4 +42,13 @@ SLEQP_WARNUNUSED
 SLEQP_RETCODE
 sleqp_hipfact_tr_set_hessian(SleqpHipfactTR* ctl, const SleqpMat* hess_lower);
 
+/* Optional, for least-squares problems (SLEQP_FUNC_TYPE_LSQ): the residual Jacobian J_r (r x n, CSC) at the
+ * current iterate and the Levenberg-Marquardt factor.  The Hessian of the solve is then the device operator
+ * [explicit Hessian if set] + J_r' J_r + lm_factor I (lsq_func_hess_product, lsq.c:211-263; J_r' J_r is never
+ * formed) and the problem's product callback is not called.  The pattern may change between calls; NULL
+ * switches the term off, and without it nothing changes. */
+SLEQP_WARNUNUSED
+SLEQP_RETCODE
+sleqp_hipfact_tr_set_gauss_newton(SleqpHipfactTR* ctl, const SleqpMat* lsq_jac, double lm_factor);
+
 #endif /* SLEQP_TR_HIPFACT_H */

@@ -52,7 +52,10 @@ int hipfact_spmat_create(hipfact_handle* h, int num_rows, int num_cols, const in
   M->nnz = nnz;
   std::vector<int> tp(num_rows + 1, 0), ti(nnz), tsrc(nnz);
   for (long long e = 0; e < nnz; ++e) ++tp[rowidx[e] + 1];
-  for (int i = 0; i < num_rows; ++i) tp[i + 1] += tp[i];
+  for (int i = 0; i < num_rows; ++i) {
+    M->max_row = std::max(M->max_row, tp[i + 1]);
+    tp[i + 1] += tp[i];
+  }
   {
     std::vector<int> fill(tp.begin(), tp.end() - 1);
     for (int j = 0; j < num_cols; ++j)
@@ -206,44 +209,7 @@ static int cg_dots(hipfact_handle* h, int n, const double* x0, const double* y0,
   return HIPFACT_OK;
 }
 
-// Hessian of the Lagrangian as an operator: an explicit matrix resident in HBM, or the caller's
-// matrix-free product (SLEQP_FUNC_HESS_PROD behind sleqp_problem_hess_prod, func.c:373-408).  The
-// matrix-free form moves one n-vector down and one up per product through pinned staging; every
-// other vector of the Krylov loop stays on the device.
-struct HessOp {
-  hipfact_spmat* hess;
-  hipfact_hess_prod_fn prod;
-  void* user;
-};
-
-static int apply_hess(hipfact_handle* h, const HessOp& op, int n, const double* d_in, double* d_out) {
-  if (op.hess) return hipfact_spmat_mult_device(op.hess, 2, d_in, d_out);
-  const size_t nb = (size_t)n * sizeof(double);
-  HCHECK(h, h->h_hv.ensure(2 * nb + 16));
-  double* hv = h->h_hv.as<double>();
-  HCHECK(h, hipMemcpyAsync(hv, d_in, nb, hipMemcpyDeviceToHost, h->stream));
-  HCHECK(h, hipStreamSynchronize(h->stream));
-  if (op.prod(op.user, hv, hv + n) != 0) {
-    h->error = "Hessian product callback failed";
-    return HIPFACT_EINTERNAL;
-  }
-  HCHECK(h, hipMemcpyAsync(d_out, hv + n, nb, hipMemcpyHostToDevice, h->stream));
-  return HIPFACT_OK;
-}
-
-static int tr_args_ok(hipfact_handle* h, const HessOp& op, const double* gradient, double* newton_step,
-                      double trust_radius, const char* who) {
-  const Plan& P = h->plan;
-  const int n = P.saddle ? P.n : 0;
-  const bool hess_ok = op.hess ? (op.hess->h == h && op.hess->rows == n && op.hess->cols == n) : op.prod != nullptr;
-  if (!P.saddle || !hess_ok || !gradient || !newton_step || !(trust_radius > 0.0)) {
-    h->error = std::string(who) + ": needs a factorised saddle matrix and an n x n Hessian (explicit, on the same "
-                                  "handle, or a product callback)";
-    return HIPFACT_EINVAL;
-  }
-  return HIPFACT_OK;
-}
-
+#include "krylov_hess_op.inc"
 #include "krylov_device.inc"
 
 static int steihaug_impl(hipfact_handle* h, const HessOp& op, const double* gradient, double trust_radius,
@@ -303,7 +269,7 @@ static int steihaug_impl(hipfact_handle* h, const HessOp& op, const double* grad
   if (!(d_nrm_sq < rel_tol_sq)) {
     bool touched = false;
     int dstate = 0, dits = 0;
-    if ((rc = steihaug_device_loop(h, op.hess, n, r_dot_g, rel_tol_sq, rad_sq, max_iter, r, h->d_cg_z.as<double>(), z, d, Bd, grad,
+    if ((rc = steihaug_device_loop(h, op, n, r_dot_g, rel_tol_sq, rad_sq, max_iter, r, h->d_cg_z.as<double>(), z, d, Bd, grad,
                                    &dev_used, &touched, &dstate, &dits)))
       return rc;
     if (dev_used) {
@@ -402,7 +368,7 @@ int hipfact_steihaug_solve(hipfact_handle* h, hipfact_spmat* hess, const double*
     h->error = "hipfact_steihaug_solve: no Hessian";
     return HIPFACT_EINVAL;
   }
-  const HessOp op = {hess, nullptr, nullptr};
+  const HessOp op = {hess, nullptr, 0.0, nullptr, nullptr};
   return steihaug_impl(h, op, gradient, trust_radius, rel_tol, max_iter, newton_step, tr_dual, iterations);
 }
 
@@ -522,7 +488,7 @@ static int gltr_impl(hipfact_handle* h, const HessOp& op, const double* gradient
   {
     int kd = 0;
     bool used = false, touched = false;
-    if ((rc = lz_device_phase(h, op.hess, n, gamma0, tol, trust_radius, kmax, Q, tb, Hq, delta, gamma, &kd, &used, &touched)))
+    if ((rc = lz_device_phase(h, op, n, gamma0, tol, trust_radius, kmax, Q, tb, Hq, delta, gamma, &kd, &used, &touched)))
       return rc;
     if (used && h->tr.timed_out) {
       // the time limit ended the device phase between two chunks: T of dimension kd is complete, its subproblem is
@@ -649,16 +615,11 @@ static int gltr_impl(hipfact_handle* h, const HessOp& op, const double* gradient
   return HIPFACT_OK;
 }
 
-int hipfact_tr_solve_ex(hipfact_handle* h, int method, hipfact_spmat* hess, hipfact_hess_prod_fn prod, void* user,
-                        const double* gradient, double trust_radius, double rel_tol, int max_iter, double* newton_step,
-                        double* tr_dual, int* iterations, hipfact_tr_extra* extra) {
-  int rc = enter(h);
-  if (rc) return rc;
-  if (!hess && !prod) {
-    h->error = "hipfact_tr_solve: neither an explicit Hessian nor a product callback";
-    return HIPFACT_EINVAL;
-  }
-  const HessOp op = {hess, hess ? nullptr : prod, user};
+// hipfact_tr_solve_ex / hipfact_tr_solve_op behind their argument checks
+static int tr_solve_run(hipfact_handle* h, int method, const HessOp& op, const double* gradient, double trust_radius,
+                        double rel_tol, int max_iter, double* newton_step, double* tr_dual, int* iterations,
+                        hipfact_tr_extra* extra) {
+  int rc;
   h->tr.limit = extra ? extra->time_limit : -1.0;
   h->tr.t0 = std::chrono::steady_clock::now();
   h->tr.timed_out = false;
@@ -677,6 +638,53 @@ int hipfact_tr_solve_ex(hipfact_handle* h, int method, hipfact_spmat* hess, hipf
     extra->max_rayleigh = h->tr.ray_max;
   }
   h->tr.limit = -1.0;
+  return rc;
+}
+
+int hipfact_tr_solve_ex(hipfact_handle* h, int method, hipfact_spmat* hess, hipfact_hess_prod_fn prod, void* user,
+                        const double* gradient, double trust_radius, double rel_tol, int max_iter, double* newton_step,
+                        double* tr_dual, int* iterations, hipfact_tr_extra* extra) {
+  int rc = enter(h);
+  if (rc) return rc;
+  if (!hess && !prod) {
+    h->error = "hipfact_tr_solve: neither an explicit Hessian nor a product callback";
+    return HIPFACT_EINVAL;
+  }
+  const HessOp op = {hess, nullptr, 0.0, hess ? nullptr : prod, user};
+  return tr_solve_run(h, method, op, gradient, trust_radius, rel_tol, max_iter, newton_step, tr_dual, iterations, extra);
+}
+
+int hipfact_tr_solve_op(hipfact_handle* h, int method, const hipfact_hess_op* op_in, const double* gradient,
+                        double trust_radius, double rel_tol, int max_iter, double* newton_step, double* tr_dual,
+                        int* iterations, hipfact_tr_extra* extra) {
+  if (!h) return HIPFACT_EINVAL;
+  HessOp op;
+  int rc = hess_op_from_abi(h, op_in, "hipfact_tr_solve_op", &op);  // (in front of the device: a NULL op touches none)
+  if (rc || (rc = enter(h))) return rc;
+  ++h->hess_op_solves;
+  h->hess_op_call = true;
+  rc = tr_solve_run(h, method, op, gradient, trust_radius, rel_tol, max_iter, newton_step, tr_dual, iterations, extra);
+  h->hess_op_call = false;
+  return rc;
+}
+
+int hipfact_hess_op_apply_device(hipfact_handle* h, const hipfact_hess_op* op_in, const double* d_x, double* d_y) {
+  if (!h) return HIPFACT_EINVAL;
+  HessOp op;
+  int rc = hess_op_from_abi(h, op_in, "hipfact_hess_op_apply_device", &op);  // (in front of the device: a NULL op touches none)
+  if (rc || (rc = enter(h))) return rc;
+  if ((rc = require_factor(h, "hipfact_hess_op_apply_device"))) return rc;
+  // (n from the factorisation, as in the loops, whose check it shares: the vectors stand in for gradient and step)
+  if ((rc = tr_args_ok(h, op, d_x, d_y, 1.0, "hipfact_hess_op_apply_device"))) return rc;
+  if (d_x == d_y) {
+    h->error = "hipfact_hess_op_apply_device: d_x and d_y overlap";
+    return HIPFACT_EINVAL;
+  }
+  const int n = h->plan.n;
+  if (n == 0) return HIPFACT_OK;
+  h->hess_op_call = true;
+  rc = apply_hess(h, op, n, d_x, d_y);
+  h->hess_op_call = false;
   return rc;
 }
 

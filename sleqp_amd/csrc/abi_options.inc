@@ -513,6 +513,7 @@ int hipfact_get_info(const hipfact_handle* h, const char* name, double* value) {
   INFO("no_dataflow", h->no_dataflow) INFO("dataflow_fallbacks", h->dataflow_fallbacks) INFO("turn_waits", (double)h->turn_waits) INFO("dataflow_rearmed", h->dataflow_rearmed) INFO("fused_solve", h->fused_solve) INFO("spanel_folded", h->sp_folded) INFO("solve_items", h->n_sitems) INFO("chain_levels_fused", [&] { int c = 0; for (const LevelInfo& li : h->levels) c += li.mini_cnt > 0; return c; }()) INFO("solve_panel_bytes", h->sp_bytes) INFO("spf_bytes", (double)h->d_SPf.bytes) INFO("sitem_bytes", (double)sizeof(SolveItem)) INFO("N_internal", P.N) INFO("maps_on", h->maps_on) INFO("m_struct", h->m_struct) INFO("analyses", h->analyses) INFO("num_factor", h->num_factor) INFO("cg_device_runs", h->cg_device_runs) INFO("cg_device_fallbacks", h->cg_device_fallbacks) INFO("lz_device_runs", h->lz_device_runs) INFO("lz_device_fallbacks", h->lz_device_fallbacks) INFO("lz_device_iterations", h->lz_device_iterations) INFO("lsqr_runs", h->lsqr_runs) INFO("lsqr_iters", h->lsqr_iters) INFO("dense_columns", h->nd) INFO("late_columns", P.n_late) INFO("late_rows", P.n_late_rows) INFO("m_rows", P.saddle ? P.my : P.m) INFO("vtable_rows", h->vj->rows()) INFO("vtable_retries", h->vtable_retries) INFO("dense_fallbacks", h->dense_fallbacks) INFO("dense_probes", h->dense_probes) INFO("top_block_cols", h->tb_nT) INFO("top_block_below", h->tb_nfb) INFO("top_block_levels", h->tb_levels) INFO("top_block_items", h->tb_ntf) INFO("top_block_builds", h->tb_builds) INFO("top_block_active", h->tb_valid) INFO("superset_vtable", h->superset_vtable) INFO("exact_pattern", h->exact_pattern) INFO("spmv_stream", h->spmv_stream)
   // what hipfact_spmat_mult_device launched (tests): the lanes per row of k_spmv_csr of the last product, 0 when it
   // streamed (k_spmv_stream), -1 before the first product; the streamed products of the handle
+  INFO("hess_op_solves", h->hess_op_solves) INFO("hess_op_products", h->hess_op_products)
   INFO("spmv_last_lanes", h->spmv_last_lanes) INFO("spmv_stream_runs", (double)h->spmv_stream_runs)
   INFO("boundary_fast", h->boundary_fast) INFO("bd_count", h->bd_count) INFO("bd_stage_us", h->bd_stage_us) INFO("bd_queue_us", h->bd_queue_us) INFO("bd_rhs_us", h->bd_rhs_us) INFO("bd_device_us", h->bd_device_us) INFO("bd_d2h_us", h->bd_d2h_us) INFO("bd_wait_us", h->bd_wait_us) INFO("bd_copyout_us", h->bd_copyout_us)
   INFO("multi_solves", h->multi_solves) INFO("multi_cols", h->multi_cols) INFO("multi_blocks", h->multi_blocks)

@@ -12,6 +12,7 @@
 //   runtime_queue.inc   factor / solve queues, graphs, cache     abi_krylov.inc       products, Steihaug CG, GLTR
 //   vtable_superset.inc row dictionary (plain vtable)            abi_options.inc      options, info, debug copies
 //   dense_cols.inc      dense Jacobian columns                   krylov_device.inc    device-controlled CG
+//   krylov_hess_op.inc  the Hessian of the Krylov loops as a device operator H0 + J_r^T J_r + shift I (hipfact_tr_solve_op)
 //   runtime_multi.inc   blocked solve, 16 right-hand sides       abi_multi.inc        hipfact_solve[_device]_multi
 //   runtime_extra.inc   extra-precise solve (dd_arith.h)         abi_extra.inc        hipfact_solve[_device]_extra, _residual_device
 //   runtime_multi_extra.inc blocked extra-precise solve         abi_multi_extra.inc  hipfact_solve[_device]_multi_extra, _residual_device_multi

@@ -121,6 +121,22 @@ struct XupdIn {
   const double* __restrict__ Kval;
   double* __restrict__ res;
 };
+// The rows of stage 2 of a product with the Hessian operator H = sym(H0) + J_r^T J_r + shift I (krylov_hess_op.inc):
+// the lower triangle of H0 by rows (hp, hi, hv) and by columns (hp2, hi2, hv2), null without H0; J_r^T by rows (jp, ji,
+// jv: the column arrays of J_r) against t = J_r x, null without J_r
+struct HessRows {
+  const int* __restrict__ hp;
+  const int* __restrict__ hi;
+  const double* __restrict__ hv;
+  const int* __restrict__ hp2;
+  const int* __restrict__ hi2;
+  const double* __restrict__ hv2;
+  const int* __restrict__ jp;
+  const int* __restrict__ ji;
+  const double* __restrict__ jv;
+  const double* __restrict__ t;
+  double shift;
+};
 struct CgCtl {
   double rg, z_nrm_sq, rel_tol_sq, rad_sq, alpha, beta, tau;
   double ray_min, ray_max;  // smallest / largest d.Bd / d.d seen (steihaug_collect_rayleigh, steihaug_solver.c:150-182); start at 1

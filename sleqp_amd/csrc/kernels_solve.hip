@@ -29,7 +29,7 @@
 //   kernels_saddle.inc        row scaling, right-hand side, x update, residual, refinement verdict
 //   kernels_vector.inc        CSR row product / lane sum / block partial sums shared by the product and Krylov kernels,
 //                             Krylov vector kernels, CSR SpMV, fill_aug_jac on the device
-// (dense_cols.inc, krylov_device.inc and krylov_lsqr.inc carry their own kernels next to the host code that launches
+// (dense_cols.inc, krylov_device.inc, krylov_hess_op.inc and krylov_lsqr.inc carry their own kernels next to the host code that launches
 // them; the Krylov ones are built from the shared pieces of kernels_vector.inc.)
 #include <hip/hip_runtime.h>
 
@@ -53,6 +53,9 @@ namespace hipfact {
 #define KRYLOV_DEVICE_KERNELS
 #include "krylov_device.inc"
 #undef KRYLOV_DEVICE_KERNELS
+#define KRYLOV_HESS_OP_KERNELS
+#include "krylov_hess_op.inc"
+#undef KRYLOV_HESS_OP_KERNELS
 #define KRYLOV_LSQR_KERNELS
 #include "krylov_lsqr.inc"
 #undef KRYLOV_LSQR_KERNELS
@@ -85,6 +88,18 @@ INST_LZ(4)
 INST_LZ(16)
 INST_LZ(64)
 #undef INST_LZ
+#define INST_HOP(L)                                                                                                   \
+  template __global__ void k_hess_op_apply<L>(int, HessRows, const double*, double*);                                 \
+  template __global__ void k_cg_spmv_dots_op<L>(int, const CgCtl*, HessRows, const double*, const double*,            \
+                                                const double*, double*, double*);                                     \
+  template __global__ void k_cg_head_op<L>(int, const CgCtl*, CgCtl*, const double*, int, int, HessRows,              \
+                                           const double*, double*, double*, const double*, const double*, double*);   \
+  template __global__ void k_lz_spmv_dot_op<L>(int, const LzCtl*, HessRows, const double*, double*, double*);
+INST_HOP(1)
+INST_HOP(4)
+INST_HOP(16)
+INST_HOP(64)
+#undef INST_HOP
 #define INST_LSQR(L)                                                                                                  \
   template __global__ void k_lsqr_forward<L>(int, int, const int*, const int*, const double*, const double*,         \
                                              const int*, const int*, const double*, const double*, double, double,   \

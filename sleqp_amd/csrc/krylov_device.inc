@@ -353,9 +353,6 @@ __global__ __launch_bounds__(FB) void k_lanczos_next_dev(int n, const double* __
 }  // namespace hipfact
 #else
 
-// lanes per row of the products with the symmetric Hessian (both triangles from lower storage)
-static int hess_lanes(const hipfact_spmat* hess, int n) { return spmv_lanes(2.0 * (double)hess->nnz / std::max(n, 1)); }
-
 // The launches of the product-with-dots kernels, L lanes per row; they return the number of blocks (= partials).
 static int launch_cg_spmv(hipStream_t st, int L, int n, const CgCtl* c, hipfact_spmat* M, const double* d, const double* z,
                           const double* grad, double* Bd, double* part) {
@@ -434,12 +431,12 @@ static DotPartials project_with_dot(hipfact_handle* h, int n, const double* b, c
 // its loop at iteration k_done - 1 behind the projection.  *used stays false when the conditions do not hold or the
 // check of the last projection failed (*touched: the rotating right-hand sides have been overwritten, the caller
 // starts over).
-static int lz_device_phase(hipfact_handle* h, hipfact_spmat* hess, int n, double gamma0, double tol, double radius,
+static int lz_device_phase(hipfact_handle* h, const HessOp& op, int n, double gamma0, double tol, double radius,
                            int kmax, double* Q, double* const tb[3], double* Hy, std::vector<double>& delta,
                            std::vector<double>& gamma, int* k_done, bool* used, bool* touched) {
   *used = false;
   *touched = false;
-  if (!h->lz_device_loop || !hess || kmax < 2 || !unchecked_solves_ok(h)) return HIPFACT_OK;
+  if (!h->lz_device_loop || op.prod || kmax < 2 || !unchecked_solves_ok(h)) return HIPFACT_OK;
   hipStream_t st = h->stream;
   *touched = true;
   const int vb = nblocks(n);
@@ -462,7 +459,7 @@ static int lz_device_phase(hipfact_handle* h, hipfact_spmat* hess, int n, double
   double* part = h->d_cg_dots.as<double>();
   double* part_x = part + 5 * CG_BLOCKS;
   const double* y = h->d_cg_z.as<double>();
-  const int L = hess_lanes(hess, n);
+  const int L = hess_op_lanes(op, n);
   // (the solves below go past solve_async: its count of solves towards the dense top block of the tree is kept here)
   int rc;
   h->solves_this_factor += 2;
@@ -470,12 +467,18 @@ static int lz_device_phase(hipfact_handle* h, hipfact_spmat* hess, int n, double
   LzCtl host;
   memset(&host, 0, sizeof(host));
   DotPartials px = {0, 1};
-  int solves = 0, written = 0;
+  int solves = 0, written = 0, products = 0;
   for (int k = 0; k <= kmax && !host.stop;) {
     for (int j = 0; j < CG_CHUNK && k <= kmax; ++j, ++k) {
       const LzCtl* ci = c + (k & 1);
       LzCtl* co = c + ((k + 1) & 1);
-      const int nblk = launch_lz_spmv(st, L, n, ci, hess, y, Hy, part);
+      // (an operator that is more than an explicit Hessian: t = J_r y in front, four launches per iteration)
+      int nblk;
+      if (op.plain())
+        nblk = launch_lz_spmv(st, L, n, ci, op.hess, y, Hy, part);
+      else if ((rc = launch_lz_spmv_op(h, op, L, n, ci, y, Hy, part, &nblk)))
+        return rc;
+      ++products;
       double* tn = tb[(k + 1) % 3];
       hipLaunchKernelGGL(k_lz_step, dim3(std::min(vb, 128)), dim3(FB), 0, st, n, ci, co, k, part, nblk, part_x, px.blocks,
                          px.stride, h->d_cg_z.as<double>(), Hy, tb[(k + 2) % 3], tb[k % 3],
@@ -500,6 +503,7 @@ static int lz_device_phase(hipfact_handle* h, hipfact_spmat* hess, int n, double
       if (host.k < 1 || host.k > kmax + 1) break;
       const double* hc = reinterpret_cast<const double*>(h->h_lz_ctl.as<LzCtl>() + 2);
       h->num_solve += solves;
+      if (h->hess_op_call) h->hess_op_products += products;
       gamma.assign(hc, hc + host.k);
       delta.assign(hc + coef, hc + coef + host.k);
       *k_done = host.k;
@@ -518,6 +522,7 @@ static int lz_device_phase(hipfact_handle* h, hipfact_spmat* hess, int n, double
   if ((rc = last_unchecked_solve_ok(h, tb[kd % 3], &ok)) || !ok) return rc;
   const double* hc = reinterpret_cast<const double*>(h->h_lz_ctl.as<LzCtl>() + 2);
   h->num_solve += std::min(solves, kd);
+  if (h->hess_op_call) h->hess_op_products += std::min(products, kd + 1);  // (those in front of the stop: the rest returned at once)
   gamma.assign(hc, hc + kd + 1);
   delta.assign(hc + coef, hc + coef + kd);
   *k_done = kd;
@@ -528,7 +533,7 @@ static int lz_device_phase(hipfact_handle* h, hipfact_spmat* hess, int n, double
 // One chunk of CG_CHUNK iterations: three launches per iteration - tests + z, r | projection (tree, x update and the
 // partials of r.g in one launch) | beta, d, B d and the next iteration's partials.  The control block ping-pongs
 // between c[0] and c[1] (a launch never writes the block its own workgroups read).
-static int cg_chunk_enqueue(hipfact_handle* h, hipfact_spmat* hess, int n, CgCtl* c, double* r, const double* g,
+static int cg_chunk_enqueue(hipfact_handle* h, const HessOp& op, int n, CgCtl* c, double* r, const double* g,
                             double* z, double* d, double* Bd, const double* grad, int iterations = CG_CHUNK) {
   hipStream_t st = h->stream;
   const int vb = nblocks(n);
@@ -536,13 +541,18 @@ static int cg_chunk_enqueue(hipfact_handle* h, hipfact_spmat* hess, int n, CgCtl
   double* part2 = part + 5 * CG_BLOCKS;
   // three launches per iteration: tests + z, r | projection | beta, d, B d (by recurrence) and the partials of the NEXT
   // iteration (k_cg_head).  The product of the first iteration was queued in front of the first chunk.
-  const int L = hess_lanes(hess, n);
+  // (an operator that is more than an explicit Hessian: t = J_r g between the projection and the head, four launches)
+  const int L = hess_op_lanes(op, n);
   const int nblk = row_blocks(n, L, CG_BLOCKS);
+  int rc;
   for (int k = 0; k < iterations; ++k) {
     hipLaunchKernelGGL(k_cg_step_update1, dim3(std::min(vb, 128)), dim3(FB), 0, st, n, c, c + 1, part, nblk, d, Bd, z, r,
                        h->cg_residual_update ? g : nullptr);
     const DotPartials rg = project_with_dot(h, n, h->d_cg_b.as<double>(), &c[1].stop, part2);  // g = P[r], and r.g
-    launch_cg_head(st, L, n, c + 1, c, part2, rg.blocks, rg.stride, hess, g, d, Bd, z, grad, part);
+    if (op.plain())
+      launch_cg_head(st, L, n, c + 1, c, part2, rg.blocks, rg.stride, op.hess, g, d, Bd, z, grad, part);
+    else if ((rc = launch_cg_head_op(h, op, L, n, c + 1, c, part2, rg.blocks, rg.stride, g, d, Bd, z, grad, part)))
+      return rc;
   }
   HCHECK(h, hipGetLastError());
   return HIPFACT_OK;
@@ -550,12 +560,12 @@ static int cg_chunk_enqueue(hipfact_handle* h, hipfact_spmat* hess, int n, CgCtl
 
 // The loop behind the first projection.  Returns HIPFACT_OK with *used = false when the conditions for the
 // device-controlled loop do not hold (the caller runs the host loop), and fills the exit state otherwise.
-static int steihaug_device_loop(hipfact_handle* h, hipfact_spmat* hess, int n, double r_dot_g, double rel_tol_sq,
+static int steihaug_device_loop(hipfact_handle* h, const HessOp& op, int n, double r_dot_g, double rel_tol_sq,
                                 double rad_sq, int max_iter, double* r, const double* g, double* z, double* d,
                                 double* Bd, const double* grad, bool* used, bool* touched, int* state_out, int* it_out) {
   *used = false;
   *touched = false;
-  if (!h->cg_device_loop || !hess || !unchecked_solves_ok(h)) return HIPFACT_OK;
+  if (!h->cg_device_loop || op.prod || !unchecked_solves_ok(h)) return HIPFACT_OK;
   hipStream_t st = h->stream;
   *touched = true;
   HCHECK(h, h->d_cg_ctl.ensure(2 * sizeof(CgCtl)));
@@ -575,12 +585,18 @@ static int steihaug_device_loop(hipfact_handle* h, hipfact_spmat* hess, int n, d
   CgCtl host;
   int rc;
   // the product B d of the first iteration (the later ones ride in k_cg_head)
-  launch_cg_spmv(st, hess_lanes(hess, n), n, c, hess, d, z, grad, Bd, h->d_cg_dots.as<double>());
+  if (op.plain()) {
+    launch_cg_spmv(st, hess_lanes(op.hess, n), n, c, op.hess, d, z, grad, Bd, h->d_cg_dots.as<double>());
+  } else {
+    int nblk;
+    if ((rc = launch_cg_spmv_op(h, op, hess_op_lanes(op, n), n, c, d, z, grad, Bd, h->d_cg_dots.as<double>(), &nblk)))
+      return rc;
+  }
   const int budget = (max_iter == -1) ? (1 << 20) : max_iter + 1;
   for (int done = 0; done < budget; done += CG_CHUNK) {
     // (direct launches - a captured graph of a chunk measured slower -, no more iterations than the cap allows: the last
     // one only takes the cap's exit)
-    rc = cg_chunk_enqueue(h, hess, n, c, r, g, z, d, Bd, grad, std::min(CG_CHUNK, budget - done));
+    rc = cg_chunk_enqueue(h, op, n, c, r, g, z, d, Bd, grad, std::min(CG_CHUNK, budget - done));
     if (rc) return rc;
     HCHECK(h, hipMemcpyAsync(h->h_cg_ctl.p, h->d_cg_ctl.p, sizeof(CgCtl), hipMemcpyDeviceToHost, st));
     HCHECK(h, hipStreamSynchronize(st));
@@ -601,6 +617,7 @@ static int steihaug_device_loop(hipfact_handle* h, hipfact_spmat* hess, int n, d
   bool ok;
   if ((rc = last_unchecked_solve_ok(h, h->d_cg_b.as<double>(), &ok)) || !ok) return rc;
   h->num_solve += host.it + 1;
+  if (h->hess_op_call) h->hess_op_products += host.it + 1;  // (the first product and one per head that ran)
   *state_out = h->tr.timed_out ? 5 : host.state;  // (5: the time limit; z holds the iterate reached)
   *it_out = host.it;
   *used = true;

@@ -1,0 +1,305 @@
+// The Hessian of the trust-region loops as an operator on the device (included by kernels_solve.hip for its kernels and
+// by abi_krylov.inc for the host half, in front of krylov_device.inc):
+//     H = sym(H0) + J_r^T J_r + shift I,
+// the Gauss-Newton Hessian of a least-squares problem (lsq_func_hess_product, lsq.c:211-263: J_r^T (J_r d) + lm_factor d;
+// it is flagged SLEQP_FUNC_HESS_PSD, lsq.c:362-365, so TR_SOLVER = AUTO runs the CG solver on it, newton.c:97-109), a
+// Levenberg-Marquardt / proximal shift on an explicit Hessian, or augmented-Lagrangian curvature H0 + J^T J.  J_r^T J_r is
+// never formed.  A product is TWO stages:
+//   stage 1   t = J_r x, an r-vector of the handle (d_hess_t): the plain product launch of hipfact_spmat_mult_device
+//             (k_spmv_csr, or k_spmv_stream above "spmv_stream_min" - and for a J_r with a very long row, hess_op_jx).
+//             It writes nothing but t, so the device loops queue it unconditionally - also behind a `stop`.
+//   stage 2   per row i of n, with LANES lanes (spmv_lanes of the stage's entries per row, (2 nnz(H0) + nnz(J_r)) / n),
+//             ONE running sum per lane, in this order (hess_op_row below - every kernel here calls it, none restates it):
+//               1. the lane's share of row i of the lower triangle of H0, then of column i without the diagonal - what
+//                  k_cg_spmv_dots walks, in its order -, if H0 is present,
+//               2. onto it the lane's share of row i of J_r^T (the cp / ri / val arrays of the matrix) against t,
+//               3. the shuffle tree over the row's lanes (lanes_sum),
+//               4. fma(shift, x_i, .) in the row's lane 0.
+// The same handle state gives the same bits on every call, and the host-driven loops (apply_hess), the device-controlled
+// loops and hipfact_hess_op_apply_device form the product of one vector with the same bits: same stage 1, same row
+// function, same lane count.  An operator that is an explicit Hessian and nothing else does not come here: it runs the
+// kernels of krylov_device.inc, bit for bit what hipfact_tr_solve_ex gives.
+#ifdef KRYLOV_HESS_OP_KERNELS
+namespace hipfact {
+
+// row `row` of H x from the lane `sub` of its LANES lanes; valid in the row's lane 0
+template <int LANES>
+__device__ __forceinline__ double hess_op_row(const HessRows& o, int row, int sub, const double* __restrict__ x) {
+  double s = 0.0;
+  if (o.hp) {
+    s = csr_row_add<LANES>(s, row, sub, o.hp, o.hi, o.hv, x);
+    s = csr_offdiag_add<LANES>(s, row, sub, o.hp2, o.hi2, o.hv2, x);
+  }
+  if (o.jp) s = csr_row_add<LANES>(s, row, sub, o.jp, o.ji, o.jv, o.t);
+  s = lanes_sum<LANES>(s);
+  return fma(o.shift, x[row], s);
+}
+
+// y = H x (apply_hess of the host-driven loops, hipfact_hess_op_apply_device)
+template <int LANES>
+__global__ __launch_bounds__(FB) void k_hess_op_apply(int n, HessRows o, const double* __restrict__ x,
+                                                      double* __restrict__ y) {
+  const int sub = threadIdx.x % LANES;
+  const int rows_per_block = FB / LANES;
+  for (int row = blockIdx.x * rows_per_block + threadIdx.x / LANES; row < n; row += gridDim.x * rows_per_block) {
+    const double s = hess_op_row<LANES>(o, row, sub, x);
+    if (sub == 0) y[row] = s;
+  }
+}
+
+// k_cg_spmv_dots on the operator: B d and the block partials of d.Bd, z.d, d.d, grad.d, z.Bd
+template <int LANES>
+__global__ __launch_bounds__(FB) void k_cg_spmv_dots_op(int n, const CgCtl* __restrict__ c, HessRows o,
+                                                        const double* __restrict__ d, const double* __restrict__ z,
+                                                        const double* __restrict__ grad, double* __restrict__ Bd,
+                                                        double* __restrict__ out) {
+  if (c->stop) return;
+  const int sub = threadIdx.x % LANES;
+  const int rows_per_block = FB / LANES;
+  double t[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int row = blockIdx.x * rows_per_block + threadIdx.x / LANES; row < n; row += gridDim.x * rows_per_block) {
+    const double s = hess_op_row<LANES>(o, row, sub, d);
+    if (sub == 0) {
+      Bd[row] = s;
+      const double di = d[row], zi = z[row];
+      t[0] += di * s;
+      t[1] += zi * di;
+      t[2] += di * di;
+      t[3] += grad[row] * di;
+      t[4] += zi * s;
+    }
+  }
+  block_partials<5>(t, out);
+}
+
+// k_cg_head on the operator: beta, d = -g + beta d, B d = -(B g) + beta (B d) and the five partials of the next iteration
+// (o.t = J_r g, queued behind the projection)
+template <int LANES>
+__global__ __launch_bounds__(FB) void k_cg_head_op(int n, const CgCtl* __restrict__ ci, CgCtl* __restrict__ co,
+                                                   const double* __restrict__ part_rg, int nblk_rg, int stride,
+                                                   HessRows o, const double* __restrict__ g, double* __restrict__ d,
+                                                   double* __restrict__ Bd, const double* __restrict__ z,
+                                                   const double* __restrict__ grad, double* __restrict__ out) {
+  const bool writer = blockIdx.x == 0 && threadIdx.x == 0;
+  if (ci->stop) {
+    if (writer) cg_ctl_copy(co, ci);
+    return;
+  }
+  double tot[1];
+  block_totals<1>(part_rg, nblk_rg, stride, tot);
+  const double beta = tot[0] / ci->rg;
+  if (writer) {
+    cg_ctl_copy(co, ci);
+    co->beta = beta;
+    co->rg = tot[0];
+    co->it = ci->it + 1;
+  }
+  const int sub = threadIdx.x % LANES;
+  const int rows_per_block = FB / LANES;
+  double t[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int row = blockIdx.x * rows_per_block + threadIdx.x / LANES; row < n; row += gridDim.x * rows_per_block) {
+    const double s = hess_op_row<LANES>(o, row, sub, g);
+    if (sub == 0) {
+      const double bd = -1.0 * s + beta * Bd[row];
+      const double di = -1.0 * g[row] + beta * d[row];
+      Bd[row] = bd;
+      d[row] = di;
+      const double zi = z[row];
+      t[0] += di * bd;
+      t[1] += zi * di;
+      t[2] += di * di;
+      t[3] += grad[row] * di;
+      t[4] += zi * bd;
+    }
+  }
+  block_partials<5>(t, out);
+}
+
+// k_lz_spmv_dot on the operator: H y and the partials of y . H y
+template <int LANES>
+__global__ __launch_bounds__(FB) void k_lz_spmv_dot_op(int n, const LzCtl* __restrict__ c, HessRows o,
+                                                       const double* __restrict__ y, double* __restrict__ Hy,
+                                                       double* __restrict__ out) {
+  if (c->stop) return;
+  const int sub = threadIdx.x % LANES;
+  const int rows_per_block = FB / LANES;
+  double t[1] = {0.0};
+  for (int row = blockIdx.x * rows_per_block + threadIdx.x / LANES; row < n; row += gridDim.x * rows_per_block) {
+    const double s = hess_op_row<LANES>(o, row, sub, y);
+    if (sub == 0) {
+      Hy[row] = s;
+      t[0] += y[row] * s;
+    }
+  }
+  block_partials<1>(t, out);
+}
+
+}  // namespace hipfact
+#else
+
+// Hessian of the Lagrangian as an operator: an explicit matrix resident in HBM, the Gauss-Newton term of a residual
+// Jacobian resident in HBM, a shift - any sum of the three -, or the caller's matrix-free product (SLEQP_FUNC_HESS_PROD
+// behind sleqp_problem_hess_prod, func.c:373-408).  The matrix-free form moves one n-vector down and one up per product
+// through pinned staging; every other vector of the Krylov loop stays on the device.
+struct HessOp {
+  hipfact_spmat* hess;
+  hipfact_spmat* gn_jac;
+  double shift;
+  hipfact_hess_prod_fn prod;
+  void* user;
+  // an explicit Hessian and nothing else: the kernels of krylov_device.inc and the symmetric product of the matrix
+  bool plain() const { return hess && !gn_jac && shift == 0.0 && !prod; }
+};
+
+// lanes per row of the products with the symmetric Hessian (both triangles from lower storage)
+static int hess_lanes(const hipfact_spmat* hess, int n) { return spmv_lanes(2.0 * (double)hess->nnz / std::max(n, 1)); }
+// ... and of stage 2 of the operator: its entries per row (hess_lanes for an explicit Hessian alone)
+static int hess_op_lanes(const HessOp& op, int n) {
+  const double ent = (op.hess ? 2.0 * (double)op.hess->nnz : 0.0) + (op.gn_jac ? (double)op.gn_jac->nnz : 0.0);
+  return spmv_lanes(ent / std::max(n, 1));
+}
+
+// The caller's hipfact_hess_op as a HessOp, or HIPFACT_EINVAL (what needs n is left to tr_args_ok)
+static int hess_op_from_abi(hipfact_handle* h, const hipfact_hess_op* in, const char* who, HessOp* op) {
+  const char* bad = nullptr;
+  if (!in)
+    bad = "no operator";
+  else if (!in->hess && !in->gn_jac && in->shift == 0.0 && !in->prod)
+    bad = "an operator with nothing in it";
+  else if (!std::isfinite(in->shift))
+    bad = "non-finite shift";
+  else if (in->prod && (in->hess || in->gn_jac || in->shift != 0.0))
+    bad = "a product callback stands alone (no matrix, no shift beside it)";
+  else if ((in->hess && in->hess->h != h) || (in->gn_jac && in->gn_jac->h != h))
+    bad = "a matrix of another handle";
+  if (bad) {
+    h->error = std::string(who) + ": " + bad;
+    return HIPFACT_EINVAL;
+  }
+  *op = HessOp{in->hess, in->gn_jac, in->shift, in->prod, in->user};
+  return HIPFACT_OK;
+}
+
+// t = J_r x: the product of hipfact_spmat_mult_device - unless J_r has a row that its lanes-per-row kernel would walk in
+// more than HESS_OP_ROW_STEPS steps per lane (one residual that touches every variable: 25 000 dependent steps at n = 1e5
+// and 4 lanes, 4 ms per product).  Then the streaming kernel, whatever the size of the matrix: a row longer than its
+// block is a block of its own there, summed by a whole workgroup.  Both fix their summation order.
+constexpr int HESS_OP_ROW_STEPS = 512;
+static int hess_op_jx(hipfact_handle* h, hipfact_spmat* J, const double* x, double* t) {
+  const int L = spmv_lanes((double)J->nnz / std::max(J->rows, 1));
+  if (!h->spmv_stream || J->rows == 0 || J->max_row <= HESS_OP_ROW_STEPS * L) return hipfact_spmat_mult_device(J, 0, x, t);
+  hipLaunchKernelGGL(k_spmv_stream, dim3(std::min(J->ntrb, 256 * 16)), dim3(SPMV_T), 0, h->stream, J->ntrb, J->trb.as<int>(),
+                     J->tp.as<int>(), J->ti.as<int>(), J->tval.as<double>(), J->nnz, x, t);
+  HCHECK(h, hipGetLastError());
+  h->spmv_last_lanes = 0;
+  ++h->spmv_stream_runs;
+  return HIPFACT_OK;
+}
+
+// Stage 1 of a product with x, queued on the handle's stream, and the rows of stage 2: t = J_r x in the handle's
+// r-vector (allocated on first use, grown on demand; HIPFACT_ENOMEM leaves the handle usable).
+static int hess_op_stage1(hipfact_handle* h, const HessOp& op, const double* x, HessRows* R) {
+  memset(R, 0, sizeof(*R));
+  R->shift = op.shift;
+  if (op.hess) {
+    hipfact_spmat* M = op.hess;
+    R->hp = M->tp.as<int>(), R->hi = M->ti.as<int>(), R->hv = M->tval.as<double>();
+    R->hp2 = M->cp.as<int>(), R->hi2 = M->ri.as<int>(), R->hv2 = M->val.as<double>();
+  }
+  if (op.gn_jac) {
+    hipfact_spmat* J = op.gn_jac;
+    if (h->d_hess_t.ensure(std::max<size_t>((size_t)J->rows * sizeof(double), 16)) != hipSuccess) {
+      (void)hipGetLastError();
+      h->error = "Hessian operator: out of device memory for the residual-space vector";
+      return HIPFACT_ENOMEM;
+    }
+    int rc;
+    if ((rc = hess_op_jx(h, J, x, h->d_hess_t.as<double>()))) return rc;
+    R->jp = J->cp.as<int>(), R->ji = J->ri.as<int>(), R->jv = J->val.as<double>();
+    R->t = h->d_hess_t.as<double>();
+  }
+  return HIPFACT_OK;
+}
+
+static int apply_hess(hipfact_handle* h, const HessOp& op, int n, const double* d_in, double* d_out) {
+  if (h->hess_op_call) ++h->hess_op_products;
+  if (op.plain()) return hipfact_spmat_mult_device(op.hess, 2, d_in, d_out);
+  if (!op.prod) {
+    HessRows R;
+    int rc;
+    if ((rc = hess_op_stage1(h, op, d_in, &R))) return rc;
+    const int L = hess_op_lanes(op, n);
+    with_lanes(L, [&](auto lanes) {
+      hipLaunchKernelGGL(k_hess_op_apply<decltype(lanes)::value>, dim3(row_blocks(n, L, 8192)), dim3(FB), 0, h->stream, n,
+                         R, d_in, d_out);
+    });
+    HCHECK(h, hipGetLastError());
+    return HIPFACT_OK;
+  }
+  const size_t nb = (size_t)n * sizeof(double);
+  HCHECK(h, h->h_hv.ensure(2 * nb + 16));
+  double* hv = h->h_hv.as<double>();
+  HCHECK(h, hipMemcpyAsync(hv, d_in, nb, hipMemcpyDeviceToHost, h->stream));
+  HCHECK(h, hipStreamSynchronize(h->stream));
+  if (op.prod(op.user, hv, hv + n) != 0) {
+    h->error = "Hessian product callback failed";
+    return HIPFACT_EINTERNAL;
+  }
+  HCHECK(h, hipMemcpyAsync(d_out, hv + n, nb, hipMemcpyHostToDevice, h->stream));
+  return HIPFACT_OK;
+}
+
+static int tr_args_ok(hipfact_handle* h, const HessOp& op, const double* gradient, double* newton_step,
+                      double trust_radius, const char* who) {
+  const Plan& P = h->plan;
+  const int n = P.saddle ? P.n : 0;
+  bool hess_ok = op.hess || op.gn_jac || op.shift != 0.0 || op.prod != nullptr;
+  if (op.hess) hess_ok = hess_ok && op.hess->h == h && op.hess->rows == n && op.hess->cols == n;
+  if (op.gn_jac) hess_ok = hess_ok && op.gn_jac->h == h && op.gn_jac->cols == n;
+  if (!P.saddle || !hess_ok || !gradient || !newton_step || !(trust_radius > 0.0)) {
+    h->error = std::string(who) + ": needs a factorised saddle matrix and an n x n Hessian (explicit, on the same "
+                                  "handle, a residual Jacobian with n columns, or a product callback)";
+    return HIPFACT_EINVAL;
+  }
+  return HIPFACT_OK;
+}
+
+// The product-with-dots launches of the device loops on an operator that is more than an explicit Hessian: stage 1 and
+// the operator form of the kernel, L lanes per row; *nblk = the number of blocks (= partials).
+static int launch_cg_spmv_op(hipfact_handle* h, const HessOp& op, int L, int n, const CgCtl* c, const double* d,
+                             const double* z, const double* grad, double* Bd, double* part, int* nblk) {
+  HessRows R;
+  int rc;
+  if ((rc = hess_op_stage1(h, op, d, &R))) return rc;
+  *nblk = row_blocks(n, L, CG_BLOCKS);
+  with_lanes(L, [&](auto lanes) {
+    hipLaunchKernelGGL(k_cg_spmv_dots_op<decltype(lanes)::value>, dim3(*nblk), dim3(FB), 0, h->stream, n, c, R, d, z, grad,
+                       Bd, part);
+  });
+  return HIPFACT_OK;
+}
+static int launch_cg_head_op(hipfact_handle* h, const HessOp& op, int L, int n, const CgCtl* ci, CgCtl* co,
+                             const double* part_rg, int nblk_rg, int stride, const double* g, double* d, double* Bd,
+                             const double* z, const double* grad, double* part) {
+  HessRows R;
+  int rc;
+  if ((rc = hess_op_stage1(h, op, g, &R))) return rc;
+  with_lanes(L, [&](auto lanes) {
+    hipLaunchKernelGGL(k_cg_head_op<decltype(lanes)::value>, dim3(row_blocks(n, L, CG_BLOCKS)), dim3(FB), 0, h->stream, n,
+                       ci, co, part_rg, nblk_rg, stride, R, g, d, Bd, z, grad, part);
+  });
+  return HIPFACT_OK;
+}
+static int launch_lz_spmv_op(hipfact_handle* h, const HessOp& op, int L, int n, const LzCtl* c, const double* y, double* Hy,
+                             double* part, int* nblk) {
+  HessRows R;
+  int rc;
+  if ((rc = hess_op_stage1(h, op, y, &R))) return rc;
+  *nblk = row_blocks(n, L, CG_BLOCKS);
+  with_lanes(L, [&](auto lanes) {
+    hipLaunchKernelGGL(k_lz_spmv_dot_op<decltype(lanes)::value>, dim3(*nblk), dim3(FB), 0, h->stream, n, c, R, y, Hy,
+                       part);
+  });
+  return HIPFACT_OK;
+}
+#endif

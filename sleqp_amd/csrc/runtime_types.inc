@@ -472,6 +472,11 @@ struct hipfact_handle : PlanState, SingleSolveMemo {
   bool cg_residual_update = true;  // projected CG: r := P[r] before B d is added (the reference's loop, steihaug_solver.c:218-496, keeps r: 0)
   bool cg_device_loop = true;  // projected CG with the loop control on the device (krylov_device.inc)
   long cg_device_runs = 0, cg_device_fallbacks = 0;
+  // the Hessian as an operator (krylov_hess_op.inc): t = J_r x of its Gauss-Newton term, r doubles, allocated on first use
+  // and grown on demand; calls of hipfact_tr_solve_op, and the products formed under it and hipfact_hess_op_apply_device
+  DevBuf d_hess_t;
+  long hess_op_solves = 0, hess_op_products = 0;
+  bool hess_op_call = false;
   // the trust-region solve in progress (hipfact_tr_solve_ex): the caller's time limit (tr/tr_types.h:9-16: seconds,
   // < 0 = SLEQP_NONE) against a clock started at the entry point, whether it ended the iteration, and the Rayleigh
   // quotients the loop has seen (tr/tr_types.h:18-20)
@@ -608,6 +613,7 @@ struct hipfact_spmat {
   hipfact_handle* h = nullptr;
   int rows = 0, cols = 0;
   long long nnz = 0;
+  int max_row = 0;  // entries of the longest row (the Hessian operator sends a matrix with a very long row through the streaming product)
   DevBuf cp, ri, val;      // CSC as given (= CSR of M^T)
   DevBuf tp, ti, tval, tsrc;  // CSR of M
   DevBuf rb, trb;             // row blocks of the streaming product (k_spmv_stream): of the CSC copy (M^T x) / of the CSR copy (M x)

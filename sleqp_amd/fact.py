@@ -458,6 +458,65 @@ class HipFact:
                         "max_rayleigh": extra.max_rayleigh}
         return step, dual.value, its.value
 
+    def _hess_op(self, hess, gn_jac, shift, n):
+        """hipfact_hess_op from an SpMat / callable / None, an SpMat / None and a shift; returns (op, keepalive)."""
+        if hess is not None and not isinstance(hess, SpMat):
+            def _prod(_user, direction, product):
+                try:
+                    d = np.ctypeslib.as_array(direction, shape=(n,))
+                    np.ctypeslib.as_array(product, shape=(n,))[:] = hess(d)
+                    return 0
+                except Exception:  # noqa: BLE001
+                    return -1
+
+            cb = HESS_PROD(_prod)
+            return HessOpStruct(None, gn_jac._m if gn_jac is not None else None, float(shift), cb, None), cb
+        return HessOpStruct(hess._m if hess is not None else None, gn_jac._m if gn_jac is not None else None,
+                            float(shift), C.cast(None, HESS_PROD), None), None
+
+    def tr_solve_op(self, gradient, trust_radius: float, hess=None, gn_jac=None, shift: float = 0.0, method: int = 0,
+                    stat_tol: float = 1e-6, max_iter: int = 100, time_limit: float = -1.0):
+        """hipfact_tr_solve_op: tr_solve on the operator H = sym(hess) + gn_jac' gn_jac + shift I (the Gauss-Newton
+        Hessian of lsq.c:211-263 with gn_jac = J_r, shift = lm_factor).  `hess` / `gn_jac` are SpMat or None; a callable
+        `hess` is the matrix-free product and stands alone.  Returns (step, tr_dual, iterations); `self.last_tr` as
+        tr_solve leaves it."""
+        g = np.ascontiguousarray(gradient, dtype=np.float64)
+        step = np.empty_like(g)
+        dual, its = C.c_double(), C.c_int()
+        op, _keep = self._hess_op(hess, gn_jac, shift, g.size)
+        extra = TrExtra(float(time_limit), 0, 1.0, 1.0)
+        self._check(self._lib.hipfact_tr_solve_op(self._h, int(method), C.byref(op), _ptr(g), float(trust_radius),
+                                                  stat_tol * 1e-2, int(max_iter), _ptr(step), C.byref(dual),
+                                                  C.byref(its), C.byref(extra)))
+        self.last_tr = {"timed_out": bool(extra.timed_out), "min_rayleigh": extra.min_rayleigh,
+                        "max_rayleigh": extra.max_rayleigh}
+        return step, dual.value, its.value
+
+    def hess_op_apply(self, x, hess=None, gn_jac=None, shift: float = 0.0) -> np.ndarray:
+        """hipfact_hess_op_apply_device around a host vector: y = (sym(hess) + gn_jac' gn_jac + shift I) x for the n
+        variables of the factorised saddle matrix."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        n = x.size
+        if n != int(self.info("n")):  # (the library trusts the length of a device vector)
+            raise ValueError(f"hess_op_apply: {n} entries for n = {int(self.info('n'))}")
+        out = np.empty(n, dtype=np.float64)
+        op, _keep = self._hess_op(hess, gn_jac, shift, n)
+        hip = C.CDLL("libamdhip64.so")
+        buf = C.c_void_p()  # x | y
+        if hip.hipMalloc(C.byref(buf), C.c_size_t(max(16 * n, 16))) != 0:
+            raise MemoryError("hipMalloc")
+        try:
+            d_x, d_y = buf.value, buf.value + 8 * n
+            if n and hip.hipMemcpy(C.c_void_p(d_x), _ptr(x), C.c_size_t(x.nbytes), 1) != 0:
+                raise RuntimeError("hipMemcpy")
+            self._check(self._lib.hipfact_hess_op_apply_device(self._h, C.byref(op), C.c_void_p(d_x), C.c_void_p(d_y)))
+            self._check(self._lib.hipfact_synchronize(self._h))
+            if n and hip.hipMemcpy(_ptr(out), C.c_void_p(d_y), C.c_size_t(out.nbytes), 2) != 0:
+                raise RuntimeError("hipMemcpy")
+        finally:
+            hip.hipFree(buf)
+        return out
+
     def lsqr(self, jac_r, cons, rhs, trust_radius: float, stat_tol: float = 1e-6, max_iter: int = -1,
              time_limit: float = -1.0, eps: float = 1e-10):
         """hipfact_lsqr_solve: the Gauss-Newton LSQR loop (tr/lsqr.c:173-330 on the operator of gauss_newton.c) on the
@@ -722,6 +781,15 @@ class TrExtra(C.Structure):
     """hipfact_tr_extra (include/hipfact.h)"""
     _fields_ = [("time_limit", C.c_double), ("timed_out", C.c_int), ("min_rayleigh", C.c_double),
                 ("max_rayleigh", C.c_double)]
+
+
+HESS_PROD = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double))
+
+
+class HessOpStruct(C.Structure):
+    """hipfact_hess_op (include/hipfact.h)"""
+    _fields_ = [("hess", C.c_void_p), ("gn_jac", C.c_void_p), ("shift", C.c_double), ("prod", HESS_PROD),
+                ("user", C.c_void_p)]
 
 
 LSQR_PROD = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double))
