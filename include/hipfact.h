@@ -859,6 +859,53 @@ int hipfact_tr_solve_op(hipfact_handle* h, int method, const hipfact_hess_op* op
  * Return codes as above. */
 int hipfact_hess_op_apply_device(hipfact_handle* h, const hipfact_hess_op* op, const double* d_x, double* d_y);
 
+/* A low-rank term beside the operator:  H = sym(hess) + gn_jac' gn_jac + shift I + V diag(coef) V',  the form of a
+ * limited-memory quasi-Newton Hessian (BFGS: shift = the initial scale, two columns per stored pair; SR1: one column per
+ * pair, coefficients of either sign - quasi_newton/bfgs.c, quasi_newton/sr1.c of the reference; hipfact_debug_qn_terms
+ * builds both from the pairs) and of any other curvature on a few dense vectors.  V is dense, column-major, n x rank
+ * with leading dimension ld, in device memory of the caller, read during the call only; coef is a host array.
+ * A product gains a second stage-1 pass - w = V' x for all columns in one sweep over x, summed in a fixed order, then
+ * u = diag(coef) w - and one step in the row sweep: after the row of J_r', lane `sub` of the row's lanes adds V_ik u_k
+ * for k = sub, sub + lanes, ..., fused; the lanes per row count `rank` more entries per row.  The determinism contract
+ * of hipfact_hess_op holds unchanged. */
+typedef struct hipfact_low_rank
+{
+  int rank;           /* 0 .. 32 */
+  long long ld;       /* >= n */
+  const double* d_V;  /* device, column-major n x rank, caller-owned, read during the call only */
+  const double* coef; /* host, rank doubles, any finite sign (SR1 is indefinite) */
+} hipfact_low_rank;
+
+/* hipfact_tr_solve_op / hipfact_hess_op_apply_device on the operator with the term.  lr == NULL or rank == 0: exactly
+ * those calls - the same launches, the same bits.  With rank >= 1 an op with nothing else in it is accepted (also a zero
+ * shift).  HIPFACT_EINVAL, beside what those calls refuse and behind it: `prod` beside a term, rank outside 0 .. 32, a
+ * NULL d_V or coef, a non-finite coefficient - and, behind HIPFACT_ESTATE before a factorisation, ld < n.
+ * HIPFACT_ENOMEM when the buffer of the sums cannot be had; the handle stays usable.  Info "hess_lr_products": products
+ * formed with a term (counted where "hess_op_products" is); "hess_lr_rank": the rank of the last one. */
+int hipfact_tr_solve_lr(hipfact_handle* h, int method, const hipfact_hess_op* op, const hipfact_low_rank* lr,
+                        const double* gradient, double trust_radius, double rel_tol, int max_iter, double* newton_step,
+                        double* tr_dual, int* iterations, hipfact_tr_extra* extra);
+int hipfact_hess_lr_apply_device(hipfact_handle* h, const hipfact_hess_op* op, const hipfact_low_rank* lr,
+                                 const double* d_x, double* d_y);
+
+/* For callers without a HIP runtime of their own (the shim keeps V of its quasi-Newton term this way): a device copy of
+ * `bytes` bytes of a host array on the handle's device, and its release (waits for the handle's stream first - and for that stream only: work
+ * queued on another stream that reads the buffer is the caller's to wait for; *d_buf becomes NULL; a NULL *d_buf is
+ * fine).  HIPFACT_ENOMEM leaves the handle usable. */
+int hipfact_device_upload(hipfact_handle* h, const void* host, size_t bytes, void** d_out);
+int hipfact_device_release(hipfact_handle* h, void** d_buf);
+
+/* Pure host functions (no GPU needed; used by the tests and the shim).  The number of workgroups of the sweep that
+ * forms V' x for n rows - it depends on n alone and is part of the summation order.  And the quasi-Newton terms of
+ * stored pairs (qn_terms.h, beside this header): S, Y are n x npairs, column-major with leading dimension max(n, 1), oldest
+ * pair first, of which the last min(npairs, memory) count (memory 1 .. 16); kind 0 = SR1, 1 = simple BFGS, 2 = damped
+ * BFGS (Powell, factor 0.2).  Out: the scale of the identity, V (n x rank, room for 2 min(npairs, memory) columns),
+ * coef, rank and, bit j, whether used pair j was damped.  B = scale I + V diag(coef) V'.  The sizing of BFGS is not
+ * built: its factors would fold into scale and coef. */
+int hipfact_debug_lr_dots_blocks(long long n);
+int hipfact_debug_qn_terms(int kind, int n, int npairs, int memory, const double* S, const double* Y, double* scale,
+                           double* V, double* coef, int* rank, unsigned* damped);
+
 /* ---- Gauss-Newton LSQR (least-squares problems, TR_SOLVER = LSQR) ------- */
 
 /* Residual Jacobian J_r (r x n) as a product on host vectors: trans = 0: out (r) = J_r in (n); trans = 1: out (n) =
@@ -1056,7 +1103,9 @@ int hipfact_get_info(const hipfact_handle* h, const char* name, double* value);
 /* Debugging aid (tests, scripts): copies the first `bytes` of a named device buffer of the active plan
  * state to the host ("L", "SPf", "sitems", "y", "xhat", "ysol", "uvec", "dscale"; "mY": the m x 16 block of
  * the last pass of the blocked solve, pivot order; "res": the last residual of the single solve, caller's numbering;
- * "norms": the partial maxima (r, b, z per block, info "resid_blocks" blocks) its kernel left), or of one of the
+ * "norms": the partial maxima (r, b, z per block, info "resid_blocks" blocks) its kernel left; "cg_vec": the
+ * n-vectors z | d | B d | gradient of the last projected CG run, H q | s of the last GLTR run; "cg_z": the solution of
+ * the last projection of either, its first n entries), or of one of the
  * active host plan's front arrays ("perm", "sn_c0", "sn_r", "sn_rowptr", "sn_rows", "sn_Loff", "sn_Uoff", "late_cols", "sn_level",
  * "dense_cols"; int32, except int64 for sn_rowptr, sn_Loff and sn_Uoff). */
 int hipfact_debug_copy(hipfact_handle* h, const char* name, void* out, size_t bytes);

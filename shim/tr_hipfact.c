@@ -13,7 +13,10 @@
  * provide the Hessian as an explicit matrix (sleqp_hipfact_tr_set_hessian) avoid that as well, and so do
  * least-squares problems (SLEQP_FUNC_TYPE_LSQ), whose Hessian product is J_r' (J_r d) + lm_factor d
  * (lsq_func_hess_product, lsq.c:211-263): with the residual Jacobian resident in HBM
- * (sleqp_hipfact_tr_set_gauss_newton) the product is a device operator, hipfact_tr_solve_op.
+ * (sleqp_hipfact_tr_set_gauss_newton) the product is a device operator, hipfact_tr_solve_op.  A quasi-Newton
+ * Hessian (SLEQP_HESS_EVAL_SR1 / SIMPLE_BFGS / DAMPED_BFGS) is scale I + V diag(coef) V' on a few dense vectors: with
+ * sleqp_hipfact_tr_set_low_rank, or sleqp_hipfact_tr_push_pair on the accepted steps, its product stays on the device
+ * as well (hipfact_tr_solve_lr).
  *
  * The projection comes from the factorisation inside the hipfact handle of the augmented Jacobian
  * (aug_jac_hipfact.c); the solver holds its own reference to that handle (sleqp_hipfact_tr_bind) —
@@ -32,6 +35,11 @@
 #endif
 
 #include "hipfact.h"
+#include "qn_terms.h"
+
+/* pairs kept for sleqp_hipfact_tr_push_pair: the reference's default number (quasi_newton num_iter = 5) */
+#define QN_MEMORY 5
+#define LR_MAX_RANK 32
 
 struct SleqpHipfactTR
 {
@@ -48,6 +56,21 @@ struct SleqpHipfactTR
   int lsq_rows;
   uint64_t lsq_pattern_hash;
   double lm_factor;
+
+  /* low-rank term of the Hessian, scale I + V diag(coef) V' (a quasi-Newton Hessian): V on the device (owned) */
+  int lr_active;
+  int lr_rank;
+  long long lr_ld;
+  void* lr_dev_V;
+  double lr_coef[LR_MAX_RANK];
+  double lr_scale;
+
+  /* the stored pairs (num_variables x QN_MEMORY each, column-major, oldest first) and the terms built from them */
+  int qn_len;
+  double* qn_S;
+  double* qn_Y;
+  double* qn_V;    /* num_variables x 2 QN_MEMORY */
+  double* qn_work; /* num_variables */
 
   int method; /* HIPFACT_TR_GLTR / HIPFACT_TR_STEIHAUG */
   int max_iter;
@@ -103,7 +126,17 @@ hipfact_tr_free(void** star)
     hipfact_spmat_free(&solver->lsq_jac);
   }
 
+  if (solver->lr_dev_V)
+  {
+    hipfact_device_release(solver->handle, &solver->lr_dev_V);
+  }
+
   hipfact_free(&solver->handle); /* our reference */
+
+  sleqp_free(&solver->qn_work);
+  sleqp_free(&solver->qn_V);
+  sleqp_free(&solver->qn_Y);
+  sleqp_free(&solver->qn_S);
 
   SLEQP_CALL(sleqp_vec_free(&solver->sparse_product));
   SLEQP_CALL(sleqp_vec_free(&solver->sparse_direction));
@@ -193,18 +226,25 @@ tr_callback_solve(SleqpAugJac* jacobian,
   hipfact_tr_extra extra = {.time_limit = time_limit, .timed_out = 0, .min_rayleigh = 1., .max_rayleigh = 1.};
   int status;
 
-  if (solver->lsq_jac)
+  if (solver->lsq_jac || solver->lr_active)
   {
-    /* lsq_func_hess_product (lsq.c:211-263) as a device operator, on top of the explicit Hessian if one is set */
+    /* lsq_func_hess_product (lsq.c:211-263) as a device operator, on top of the explicit Hessian if one is set - and / or
+     * a quasi-Newton Hessian scale I + V diag(coef) V' (without a term: hipfact_tr_solve_op itself) */
     const hipfact_hess_op op = {.hess   = solver->hessian,
                                 .gn_jac = solver->lsq_jac,
-                                .shift  = solver->lm_factor,
+                                .shift  = solver->lm_factor + (solver->lr_active ? solver->lr_scale : 0.),
                                 .prod   = NULL,
                                 .user   = NULL};
 
-    status = hipfact_tr_solve_op(solver->handle,
+    const hipfact_low_rank lr = {.rank = solver->lr_active ? solver->lr_rank : 0,
+                                 .ld   = solver->lr_ld,
+                                 .d_V  = (const double*)solver->lr_dev_V,
+                                 .coef = solver->lr_coef};
+
+    status = hipfact_tr_solve_lr(solver->handle,
                                  solver->method,
                                  &op,
+                                 &lr,
                                  solver->dense_gradient,
                                  trust_radius,
                                  solver->rel_tol,
@@ -380,6 +420,153 @@ sleqp_hipfact_tr_set_gauss_newton(SleqpHipfactTR* solver, const SleqpMat* lsq_ja
   return SLEQP_OKAY;
 }
 
+/* scale I + V diag(coef) V' as the term of the next solves; rank 0 with a scale is the scaled identity alone */
+static SLEQP_RETCODE
+low_rank_store(SleqpHipfactTR* solver, int rank, const double* V, long long ld, const double* coef, double scale)
+{
+  const int num_variables = sleqp_problem_num_vars(solver->problem);
+
+  if (solver->lr_dev_V)
+  {
+    hipfact_device_release(solver->handle, &solver->lr_dev_V);
+  }
+
+  solver->lr_active = 1;
+  solver->lr_rank   = rank;
+  solver->lr_ld     = ld;
+  solver->lr_scale  = scale;
+
+  if (rank == 0 || num_variables == 0)
+  {
+    solver->lr_rank = 0;
+    return SLEQP_OKAY;
+  }
+
+  for (int k = 0; k < rank; ++k)
+  {
+    solver->lr_coef[k] = coef[k];
+  }
+
+  /* (the last column ends behind its n-th entry) */
+  const size_t count = (size_t)(rank - 1) * (size_t)ld + (size_t)num_variables;
+
+  const int status = hipfact_device_upload(solver->handle, V, count * sizeof(double), &solver->lr_dev_V);
+
+  if (status != HIPFACT_OK)
+  {
+    solver->lr_active = 0;
+    solver->lr_rank   = 0;
+    sleqp_raise(SLEQP_INTERNAL_ERROR, "Caught hipfact error <%d> (%s)", status, hipfact_last_error(solver->handle));
+  }
+
+  return SLEQP_OKAY;
+}
+
+SLEQP_RETCODE
+sleqp_hipfact_tr_set_low_rank(SleqpHipfactTR* solver,
+                              int rank,
+                              const double* V,
+                              long long ld,
+                              const double* coef,
+                              double scale)
+{
+  if (rank == 0)
+  {
+    if (solver->lr_dev_V)
+    {
+      hipfact_device_release(solver->handle, &solver->lr_dev_V);
+    }
+    solver->lr_active = 0;
+    solver->lr_rank   = 0;
+    solver->lr_scale  = 0.;
+    return SLEQP_OKAY;
+  }
+
+  if (!solver->handle)
+  {
+    sleqp_raise(SLEQP_INTERNAL_ERROR, "hipfact TR solver: bind a factorisation before setting the low-rank term");
+  }
+
+  if (rank < 0 || rank > LR_MAX_RANK || !V || !coef || ld < sleqp_problem_num_vars(solver->problem))
+  {
+    sleqp_raise(SLEQP_ILLEGAL_ARGUMENT, "hipfact TR solver: low-rank term of rank %d, leading dimension %lld", rank, ld);
+  }
+
+  return low_rank_store(solver, rank, V, ld, coef, scale);
+}
+
+SLEQP_RETCODE
+sleqp_hipfact_tr_reset_pairs(SleqpHipfactTR* solver)
+{
+  solver->qn_len = 0;
+  return sleqp_hipfact_tr_set_low_rank(solver, 0, NULL, 0, NULL, 0.);
+}
+
+SLEQP_RETCODE
+sleqp_hipfact_tr_push_pair(SleqpHipfactTR* solver, int kind, const SleqpVec* step_diff, const SleqpVec* grad_diff)
+{
+  const int num_variables = sleqp_problem_num_vars(solver->problem);
+  const size_t n          = (size_t)num_variables;
+
+  if (!solver->handle)
+  {
+    sleqp_raise(SLEQP_INTERNAL_ERROR, "hipfact TR solver: bind a factorisation before pushing a pair");
+  }
+
+  if (kind < HIPFACT_QN_SR1 || kind > HIPFACT_QN_DAMPED_BFGS || step_diff->dim != num_variables
+      || grad_diff->dim != num_variables)
+  {
+    sleqp_raise(SLEQP_ILLEGAL_ARGUMENT, "hipfact TR solver: quasi-Newton pair of kind %d", kind);
+  }
+
+  if (!solver->qn_S)
+  {
+    SLEQP_CALL(sleqp_alloc_array(&solver->qn_S, n * QN_MEMORY + 1));
+    SLEQP_CALL(sleqp_alloc_array(&solver->qn_Y, n * QN_MEMORY + 1));
+    SLEQP_CALL(sleqp_alloc_array(&solver->qn_V, n * 2 * QN_MEMORY + 1));
+    SLEQP_CALL(sleqp_alloc_array(&solver->qn_work, n + 1));
+  }
+
+  if (solver->qn_len == QN_MEMORY)
+  {
+    /* the oldest pair leaves */
+    memmove(solver->qn_S, solver->qn_S + n, n * (QN_MEMORY - 1) * sizeof(double));
+    memmove(solver->qn_Y, solver->qn_Y + n, n * (QN_MEMORY - 1) * sizeof(double));
+    --solver->qn_len;
+  }
+
+  SLEQP_CALL(sleqp_vec_to_raw(step_diff, solver->qn_S + n * (size_t)solver->qn_len));
+  SLEQP_CALL(sleqp_vec_to_raw(grad_diff, solver->qn_Y + n * (size_t)solver->qn_len));
+  ++solver->qn_len;
+
+  const long long ld = num_variables > 0 ? num_variables : 1;
+  double coef[2 * QN_MEMORY];
+  double scale = 1.;
+  int rank     = 0;
+
+  if (hipfact_qn_terms(kind,
+                       num_variables,
+                       solver->qn_len,
+                       QN_MEMORY,
+                       solver->qn_S,
+                       ld,
+                       solver->qn_Y,
+                       ld,
+                       &scale,
+                       solver->qn_V,
+                       ld,
+                       coef,
+                       &rank,
+                       NULL,
+                       solver->qn_work)
+      != 0)
+  {
+    sleqp_raise(SLEQP_INTERNAL_ERROR, "hipfact TR solver: quasi-Newton terms");
+  }
+
+  return low_rank_store(solver, rank, solver->qn_V, ld, coef, scale);
+}
+
 SLEQP_RETCODE
 sleqp_hipfact_tr_bind(SleqpHipfactTR* solver, struct hipfact_handle* handle)
 {
@@ -401,6 +588,14 @@ sleqp_hipfact_tr_bind(SleqpHipfactTR* solver, struct hipfact_handle* handle)
   if (solver->lsq_jac)
   {
     hipfact_spmat_free(&solver->lsq_jac);
+  }
+
+  if (solver->lr_dev_V)
+  {
+    /* lives on the old handle's device; the pairs stay, the next push rebuilds the term */
+    hipfact_device_release(solver->handle, &solver->lr_dev_V);
+    solver->lr_active = 0;
+    solver->lr_rank   = 0;
   }
 
   if (solver->handle)

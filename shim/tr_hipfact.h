@@ -51,4 +51,33 @@ SLEQP_WARNUNUSED
 SLEQP_RETCODE
 sleqp_hipfact_tr_set_gauss_newton(SleqpHipfactTR* ctl, const SleqpMat* lsq_jac, double lm_factor);
 
+/* Optional: a low-rank term of the Hessian,  scale I + V diag(coef) V'  with V dense, num_variables x rank (rank <= 32),
+ * column-major with leading dimension ld, and coefficients of any sign - a limited-memory BFGS / SR1 Hessian, or other
+ * curvature on a few dense vectors.  The host arrays are copied into a device buffer the solver owns.  The Hessian of
+ * the solve is then the device operator [explicit Hessian if set] + [Gauss-Newton term if set] + scale I + V diag(coef)
+ * V' (hipfact_tr_solve_lr) and the problem's product callback is not called.  rank = 0 clears the term, and without it
+ * nothing changes.  Binding another handle (sleqp_hipfact_tr_bind) drops the term with its device buffer, like the
+ * explicit Hessian: set it again behind the bind. */
+SLEQP_WARNUNUSED
+SLEQP_RETCODE
+sleqp_hipfact_tr_set_low_rank(SleqpHipfactTR* ctl,
+                              int rank,
+                              const double* V,
+                              long long ld,
+                              const double* coef,
+                              double scale);
+
+/* The same term kept up to date from the pairs of a quasi-Newton method: s = x_{k+1} - x_k and y = the difference of
+ * the gradients of the Lagrangian, what sleqp_quasi_newton_push forms from the two iterates (called at solver.c:249-257).  kind: 0 = SR1,
+ * 1 = simple BFGS, 2 = damped BFGS (SLEQP_HESS_EVAL_SR1 / SIMPLE_BFGS / DAMPED_BFGS).  The solver keeps the last five
+ * pairs (the reference's default), rebuilds the terms by the reference's update rules (qn_terms.h; without the sizing
+ * of BFGS) and sets them as above.  sleqp_hipfact_tr_reset_pairs drops the pairs and the term. */
+SLEQP_WARNUNUSED
+SLEQP_RETCODE
+sleqp_hipfact_tr_push_pair(SleqpHipfactTR* ctl, int kind, const SleqpVec* step_diff, const SleqpVec* grad_diff);
+
+SLEQP_WARNUNUSED
+SLEQP_RETCODE
+sleqp_hipfact_tr_reset_pairs(SleqpHipfactTR* ctl);
+
 #endif /* SLEQP_TR_HIPFACT_H */

@@ -42,9 +42,9 @@ SYMBOLS = [
     "hipfact_solution_device", "hipfact_synchronize", "hipfact_check", "hipfact_stream",
     "hipfact_assemble_kkt", "hipfact_reduced_matrix", "hipfact_spmat_create", "hipfact_spmat_update_values", "hipfact_spmat_free",
     "hipfact_spmat_mult_vec", "hipfact_spmat_mult_vec_trans", "hipfact_spmat_mult_vec_sym",
-    "hipfact_spmat_mult_device", "hipfact_steihaug_solve", "hipfact_tr_solve", "hipfact_tr_solve_ex", "hipfact_tr_solve_op", "hipfact_hess_op_apply_device", "hipfact_lsqr_solve", "hipfact_tridiag_tr", "hipfact_set_option", "hipfact_get_info", "hipfact_debug_copy", "hipfact_debug_pool_selftest",
+    "hipfact_spmat_mult_device", "hipfact_steihaug_solve", "hipfact_tr_solve", "hipfact_tr_solve_ex", "hipfact_tr_solve_op", "hipfact_hess_op_apply_device", "hipfact_tr_solve_lr", "hipfact_hess_lr_apply_device", "hipfact_lsqr_solve", "hipfact_tridiag_tr", "hipfact_set_option", "hipfact_get_info", "hipfact_debug_copy", "hipfact_debug_pool_selftest",
     "hipfact_debug_place_rows", "hipfact_debug_place_items", "hipfact_debug_multi_slices", "hipfact_debug_schur_items", "hipfact_debug_refine_cadence", "hipfact_plan_create",
-    "hipfact_debug_spmat_row_blocks", "hipfact_debug_spmv_lanes",
+    "hipfact_debug_spmat_row_blocks", "hipfact_debug_spmv_lanes", "hipfact_debug_lr_dots_blocks", "hipfact_debug_qn_terms", "hipfact_device_upload", "hipfact_device_release",
     "hipfact_plan_free", "hipfact_plan_error", "hipfact_plan_array", "hipfact_plan_scalar",
 ]
 
@@ -151,6 +151,14 @@ def load() -> C.CDLL:
     if hasattr(lib, "hipfact_tr_solve_op"):
         lib.hipfact_tr_solve_op.argtypes = [vp, ci, vp, vp, cd, cd, ci, vp, C.POINTER(cd), C.POINTER(ci), vp]
         lib.hipfact_hess_op_apply_device.argtypes = [vp, vp, vp, vp]
+    if hasattr(lib, "hipfact_tr_solve_lr"):
+        lib.hipfact_tr_solve_lr.argtypes = [vp, ci, vp, vp, vp, cd, cd, ci, vp, C.POINTER(cd), C.POINTER(ci), vp]
+        lib.hipfact_hess_lr_apply_device.argtypes = [vp, vp, vp, vp, vp]
+        lib.hipfact_debug_lr_dots_blocks.argtypes = [C.c_longlong]
+        lib.hipfact_device_upload.argtypes = [vp, vp, C.c_size_t, C.POINTER(vp)]
+        lib.hipfact_device_release.argtypes = [vp, C.POINTER(vp)]
+        lib.hipfact_debug_qn_terms.argtypes = [ci, ci, ci, ci, vp, vp, C.POINTER(cd), vp, vp, C.POINTER(ci),
+                                               C.POINTER(C.c_uint)]
     lib.hipfact_lsqr_solve.argtypes = [vp, vp, vp, cd, cd, cd, ci, vp, vp]
     lib.hipfact_tridiag_tr.argtypes = [ci, vp, vp, cd, cd, vp, C.POINTER(cd)]
     lib.hipfact_set_option.argtypes = [vp, C.c_char_p, cd]

@@ -654,12 +654,15 @@ int hipfact_tr_solve_ex(hipfact_handle* h, int method, hipfact_spmat* hess, hipf
   return tr_solve_run(h, method, op, gradient, trust_radius, rel_tol, max_iter, newton_step, tr_dual, iterations, extra);
 }
 
-int hipfact_tr_solve_op(hipfact_handle* h, int method, const hipfact_hess_op* op_in, const double* gradient,
-                        double trust_radius, double rel_tol, int max_iter, double* newton_step, double* tr_dual,
-                        int* iterations, hipfact_tr_extra* extra) {
+// hipfact_tr_solve_op / hipfact_tr_solve_lr, and hipfact_hess_op_apply_device / hipfact_hess_lr_apply_device: one body
+// each, the low-rank term `lr` beside the operator or NULL (NULL or rank 0: no term - the launches and the bits of the
+// operator alone)
+static int tr_solve_op_lr(hipfact_handle* h, const char* who, int method, const hipfact_hess_op* op_in,
+                          const hipfact_low_rank* lr, const double* gradient, double trust_radius, double rel_tol,
+                          int max_iter, double* newton_step, double* tr_dual, int* iterations, hipfact_tr_extra* extra) {
   if (!h) return HIPFACT_EINVAL;
   HessOp op;
-  int rc = hess_op_from_abi(h, op_in, "hipfact_tr_solve_op", &op);  // (in front of the device: a NULL op touches none)
+  int rc = hess_op_from_abi(h, op_in, who, &op, lr);  // (in front of the device: a NULL op touches none)
   if (rc || (rc = enter(h))) return rc;
   ++h->hess_op_solves;
   h->hess_op_call = true;
@@ -668,16 +671,17 @@ int hipfact_tr_solve_op(hipfact_handle* h, int method, const hipfact_hess_op* op
   return rc;
 }
 
-int hipfact_hess_op_apply_device(hipfact_handle* h, const hipfact_hess_op* op_in, const double* d_x, double* d_y) {
+static int hess_op_lr_apply(hipfact_handle* h, const char* who, const hipfact_hess_op* op_in, const hipfact_low_rank* lr,
+                            const double* d_x, double* d_y) {
   if (!h) return HIPFACT_EINVAL;
   HessOp op;
-  int rc = hess_op_from_abi(h, op_in, "hipfact_hess_op_apply_device", &op);  // (in front of the device: a NULL op touches none)
+  int rc = hess_op_from_abi(h, op_in, who, &op, lr);  // (in front of the device: a NULL op touches none)
   if (rc || (rc = enter(h))) return rc;
-  if ((rc = require_factor(h, "hipfact_hess_op_apply_device"))) return rc;
+  if ((rc = require_factor(h, who))) return rc;
   // (n from the factorisation, as in the loops, whose check it shares: the vectors stand in for gradient and step)
-  if ((rc = tr_args_ok(h, op, d_x, d_y, 1.0, "hipfact_hess_op_apply_device"))) return rc;
+  if ((rc = tr_args_ok(h, op, d_x, d_y, 1.0, who))) return rc;
   if (d_x == d_y) {
-    h->error = "hipfact_hess_op_apply_device: d_x and d_y overlap";
+    h->error = std::string(who) + ": d_x and d_y overlap";
     return HIPFACT_EINVAL;
   }
   const int n = h->plan.n;
@@ -686,6 +690,70 @@ int hipfact_hess_op_apply_device(hipfact_handle* h, const hipfact_hess_op* op_in
   rc = apply_hess(h, op, n, d_x, d_y);
   h->hess_op_call = false;
   return rc;
+}
+
+int hipfact_tr_solve_op(hipfact_handle* h, int method, const hipfact_hess_op* op_in, const double* gradient,
+                        double trust_radius, double rel_tol, int max_iter, double* newton_step, double* tr_dual,
+                        int* iterations, hipfact_tr_extra* extra) {
+  return tr_solve_op_lr(h, "hipfact_tr_solve_op", method, op_in, nullptr, gradient, trust_radius, rel_tol, max_iter,
+                        newton_step, tr_dual, iterations, extra);
+}
+int hipfact_tr_solve_lr(hipfact_handle* h, int method, const hipfact_hess_op* op_in, const hipfact_low_rank* lr,
+                        const double* gradient, double trust_radius, double rel_tol, int max_iter, double* newton_step,
+                        double* tr_dual, int* iterations, hipfact_tr_extra* extra) {
+  return tr_solve_op_lr(h, "hipfact_tr_solve_lr", method, op_in, lr, gradient, trust_radius, rel_tol, max_iter, newton_step,
+                        tr_dual, iterations, extra);
+}
+
+int hipfact_hess_op_apply_device(hipfact_handle* h, const hipfact_hess_op* op_in, const double* d_x, double* d_y) {
+  return hess_op_lr_apply(h, "hipfact_hess_op_apply_device", op_in, nullptr, d_x, d_y);
+}
+int hipfact_hess_lr_apply_device(hipfact_handle* h, const hipfact_hess_op* op_in, const hipfact_low_rank* lr,
+                                 const double* d_x, double* d_y) {
+  return hess_op_lr_apply(h, "hipfact_hess_lr_apply_device", op_in, lr, d_x, d_y);
+}
+
+// a device copy of a host array for callers without a HIP runtime of their own (the shim's V), and its release
+int hipfact_device_upload(hipfact_handle* h, const void* host, size_t bytes, void** d_out) {
+  int rc = enter(h);
+  if (rc) return rc;
+  if (!host || !d_out || bytes == 0) return HIPFACT_EINVAL;
+  *d_out = nullptr;
+  void* p = nullptr;
+  if (hipMalloc(&p, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    h->error = "hipfact_device_upload: out of device memory";
+    return HIPFACT_ENOMEM;
+  }
+  if (hipMemcpy(p, host, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipGetLastError();
+    (void)hipFree(p);
+    h->error = "hipfact_device_upload: upload failed";
+    return HIPFACT_EDEVICE;
+  }
+  *d_out = p;
+  return HIPFACT_OK;
+}
+int hipfact_device_release(hipfact_handle* h, void** d_buf) {
+  int rc = enter(h);
+  if (rc) return rc;
+  if (d_buf && *d_buf) {
+    (void)hipStreamSynchronize(h->stream);  // (a queued product may still read it)
+    (void)hipFree(*d_buf);
+    *d_buf = nullptr;
+  }
+  return HIPFACT_OK;
+}
+
+// the grid of k_lr_dots for n rows (tests: its edges), and the quasi-Newton terms of qn_terms.h on host arrays
+int hipfact_debug_lr_dots_blocks(long long n) { return n < 0 ? HIPFACT_EINVAL : lr_blocks(n); }
+int hipfact_debug_qn_terms(int kind, int n, int npairs, int memory, const double* S, const double* Y, double* scale,
+                           double* V, double* coef, int* rank, unsigned* damped) {
+  std::vector<double> work((size_t)std::max(n, 1));
+  const long long ld = std::max(n, 1);
+  return hipfact_qn_terms(kind, n, npairs, memory, S, ld, Y, ld, scale, V, ld, coef, rank, damped, work.data()) == 0
+             ? HIPFACT_OK
+             : HIPFACT_EINVAL;
 }
 
 int hipfact_tr_solve(hipfact_handle* h, int method, hipfact_spmat* hess, hipfact_hess_prod_fn prod, void* user,

@@ -293,6 +293,8 @@ int hipfact_debug_copy(hipfact_handle* h, const char* name, void* out, size_t by
   else if (!strcmp(name, "res")) b = &h->d_res;      // the last residual of the single solve, caller's numbering
   else if (!strcmp(name, "norms")) b = &h->d_norms;  // ... and the partial maxima (r, b, z per block) its kernel left
   else if (!strcmp(name, "mY")) b = &h->d_mY;  // the last block of the blocked solve: m x MR, pivot order
+  else if (!strcmp(name, "cg_vec")) b = &h->d_cg_vec;  // the vectors of the last trust-region loop: z | d | B d | gradient of projected CG, H q | s of GLTR
+  else if (!strcmp(name, "cg_z")) b = &h->d_cg_z;  // ... and the solution of its last projection (head: n entries)
   if (!strcmp(name, "cond_d")) {  // diag(D) of the last condition estimate, caller's numbering (behind blocks, witness, h, a)
     const size_t N = (size_t)h->N_ext, off = (2 * COND_T + 3) * N * sizeof(double);
     if (!h->d_cblk.p || bytes > N * sizeof(double)) {
@@ -514,6 +516,7 @@ int hipfact_get_info(const hipfact_handle* h, const char* name, double* value) {
   // what hipfact_spmat_mult_device launched (tests): the lanes per row of k_spmv_csr of the last product, 0 when it
   // streamed (k_spmv_stream), -1 before the first product; the streamed products of the handle
   INFO("hess_op_solves", h->hess_op_solves) INFO("hess_op_products", h->hess_op_products)
+  INFO("hess_lr_products", h->hess_lr_products) INFO("hess_lr_rank", h->hess_lr_rank)
   INFO("spmv_last_lanes", h->spmv_last_lanes) INFO("spmv_stream_runs", (double)h->spmv_stream_runs)
   INFO("boundary_fast", h->boundary_fast) INFO("bd_count", h->bd_count) INFO("bd_stage_us", h->bd_stage_us) INFO("bd_queue_us", h->bd_queue_us) INFO("bd_rhs_us", h->bd_rhs_us) INFO("bd_device_us", h->bd_device_us) INFO("bd_d2h_us", h->bd_d2h_us) INFO("bd_wait_us", h->bd_wait_us) INFO("bd_copyout_us", h->bd_copyout_us)
   INFO("multi_solves", h->multi_solves) INFO("multi_cols", h->multi_cols) INFO("multi_blocks", h->multi_blocks)

@@ -12,7 +12,8 @@
 //   runtime_queue.inc   factor / solve queues, graphs, cache     abi_krylov.inc       products, Steihaug CG, GLTR
 //   vtable_superset.inc row dictionary (plain vtable)            abi_options.inc      options, info, debug copies
 //   dense_cols.inc      dense Jacobian columns                   krylov_device.inc    device-controlled CG
-//   krylov_hess_op.inc  the Hessian of the Krylov loops as a device operator H0 + J_r^T J_r + shift I (hipfact_tr_solve_op)
+//   krylov_hess_op.inc  the Hessian of the Krylov loops as a device operator H0 + J_r^T J_r + shift I + V diag(c) V^T
+//                       (hipfact_tr_solve_op, hipfact_tr_solve_lr; qn_terms.h: BFGS / SR1 pairs as such a term, pure host)
 //   runtime_multi.inc   blocked solve, 16 right-hand sides       abi_multi.inc        hipfact_solve[_device]_multi
 //   runtime_extra.inc   extra-precise solve (dd_arith.h)         abi_extra.inc        hipfact_solve[_device]_extra, _residual_device
 //   runtime_multi_extra.inc blocked extra-precise solve         abi_multi_extra.inc  hipfact_solve[_device]_multi_extra, _residual_device_multi
@@ -63,6 +64,7 @@
 #include "selinv_types.h"
 #include "selinv_host.h"
 #include "dd_arith.h"
+#include "../../include/qn_terms.h"
 
 #include "runtime_types.inc"
 #include "runtime_plan.inc"

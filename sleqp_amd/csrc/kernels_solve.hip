@@ -100,6 +100,13 @@ INST_HOP(4)
 INST_HOP(16)
 INST_HOP(64)
 #undef INST_HOP
+#define INST_LR(RC)                                                                                       \
+  template __global__ void k_lr_dots<RC>(int, int, const double*, long long, const double*, double*);     \
+  template __global__ void k_lr_totals<RC>(int, LrCoef, const double*, int, double*);
+INST_LR(8)
+INST_LR(16)
+INST_LR(32)
+#undef INST_LR
 #define INST_LSQR(L)                                                                                                  \
   template __global__ void k_lsqr_forward<L>(int, int, const int*, const int*, const double*, const double*,         \
                                              const int*, const int*, const double*, const double*, double, double,   \

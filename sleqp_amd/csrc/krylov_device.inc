@@ -503,7 +503,7 @@ static int lz_device_phase(hipfact_handle* h, const HessOp& op, int n, double ga
       if (host.k < 1 || host.k > kmax + 1) break;
       const double* hc = reinterpret_cast<const double*>(h->h_lz_ctl.as<LzCtl>() + 2);
       h->num_solve += solves;
-      if (h->hess_op_call) h->hess_op_products += products;
+      hess_op_count(h, op, products);
       gamma.assign(hc, hc + host.k);
       delta.assign(hc + coef, hc + coef + host.k);
       *k_done = host.k;
@@ -522,7 +522,7 @@ static int lz_device_phase(hipfact_handle* h, const HessOp& op, int n, double ga
   if ((rc = last_unchecked_solve_ok(h, tb[kd % 3], &ok)) || !ok) return rc;
   const double* hc = reinterpret_cast<const double*>(h->h_lz_ctl.as<LzCtl>() + 2);
   h->num_solve += std::min(solves, kd);
-  if (h->hess_op_call) h->hess_op_products += std::min(products, kd + 1);  // (those in front of the stop: the rest returned at once)
+  hess_op_count(h, op, std::min(products, kd + 1));  // (those in front of the stop: the rest returned at once)
   gamma.assign(hc, hc + kd + 1);
   delta.assign(hc + coef, hc + coef + kd);
   *k_done = kd;
@@ -617,7 +617,7 @@ static int steihaug_device_loop(hipfact_handle* h, const HessOp& op, int n, doub
   bool ok;
   if ((rc = last_unchecked_solve_ok(h, h->d_cg_b.as<double>(), &ok)) || !ok) return rc;
   h->num_solve += host.it + 1;
-  if (h->hess_op_call) h->hess_op_products += host.it + 1;  // (the first product and one per head that ran)
+  hess_op_count(h, op, host.it + 1);  // (the first product and one per head that ran)
   *state_out = h->tr.timed_out ? 5 : host.state;  // (5: the time limit; z holds the iterate reached)
   *it_out = host.it;
   *used = true;

@@ -13,8 +13,18 @@
 //               1. the lane's share of row i of the lower triangle of H0, then of column i without the diagonal - what
 //                  k_cg_spmv_dots walks, in its order -, if H0 is present,
 //               2. onto it the lane's share of row i of J_r^T (the cp / ri / val arrays of the matrix) against t,
+//               2b. onto it the lane's share of row i of V against u, fma(V_ik, u_k, .) for k = sub, sub + LANES, ...
+//                  ascending, if a low-rank term is present (below),
 //               3. the shuffle tree over the row's lanes (lanes_sum),
 //               4. fma(shift, x_i, .) in the row's lane 0.
+// A low-rank term V diag(coef) V^T (hipfact_low_rank: the outer products of a BFGS / SR1 Hessian, qn_terms.h; rank <= 32,
+// V dense, column-major, on the device) adds to stage 1
+//   stage 1b  w_k = V_k . x for all k in ONE pass over x (k_lr_dots: a thread reads x_i once and V_ik for ascending k,
+//             coalesced per column, one running sum per column in registers - a template on the rank ceiling 8 / 16 /
+//             32 -, block_partials at the end; the grid follows from n alone, at most LR_BLOCKS blocks) and
+//             u_k = coef_k w_k (k_lr_totals: ONE workgroup sums the partials with block_totals, in index order, and
+//             leaves u in the handle's buffer behind them).  Like t = J_r x both write nothing but those buffers of the
+//             handle and are queued unconditionally.
 // The same handle state gives the same bits on every call, and the host-driven loops (apply_hess), the device-controlled
 // loops and hipfact_hess_op_apply_device form the product of one vector with the same bits: same stage 1, same row
 // function, same lane count.  An operator that is an explicit Hessian and nothing else does not come here: it runs the
@@ -31,8 +41,37 @@ __device__ __forceinline__ double hess_op_row(const HessRows& o, int row, int su
     s = csr_offdiag_add<LANES>(s, row, sub, o.hp2, o.hi2, o.hv2, x);
   }
   if (o.jp) s = csr_row_add<LANES>(s, row, sub, o.jp, o.ji, o.jv, o.t);
+  if (o.lv)
+    for (int k = sub; k < o.lrank; k += LANES) s = fma(o.lv[row + k * o.lld], o.lu[k], s);
   s = lanes_sum<LANES>(s);
   return fma(o.shift, x[row], s);
+}
+
+// stage 1b: the block partials of w_k = V_k . x, k < rank <= RC, part[RC b + k] of block b (columns rank .. RC - 1: zero)
+template <int RC>
+__global__ __launch_bounds__(FB) void k_lr_dots(int n, int rank, const double* __restrict__ V, long long ld,
+                                                const double* __restrict__ x, double* __restrict__ part) {
+  double w[RC];
+#pragma unroll
+  for (int k = 0; k < RC; ++k) w[k] = 0.0;
+  for (long long i = (long long)blockIdx.x * FB + threadIdx.x; i < n; i += (long long)gridDim.x * FB) {
+    const double xi = x[i];
+#pragma unroll
+    for (int k = 0; k < RC; ++k)
+      if (k < rank) w[k] = fma(V[i + k * ld], xi, w[k]);
+  }
+  block_partials<RC>(w, part);
+}
+
+// ... and u_k = coef_k w_k from the nblk partials per column: one workgroup, the order of block_totals
+template <int RC>
+__global__ __launch_bounds__(FB) void k_lr_totals(int rank, LrCoef coef, const double* __restrict__ part, int nblk,
+                                                  double* __restrict__ u) {
+  double tot[RC];
+  block_totals<RC>(part, nblk, RC, tot);
+#pragma unroll
+  for (int k = 0; k < RC; ++k)
+    if (k < rank && (int)threadIdx.x == k) u[k] = coef.c[k] * tot[k];
 }
 
 // y = H x (apply_hess of the host-driven loops, hipfact_hess_op_apply_device)
@@ -147,8 +186,13 @@ struct HessOp {
   double shift;
   hipfact_hess_prod_fn prod;
   void* user;
+  // the low-rank term V diag(coef) V^T (hipfact_low_rank; lrank 0: none): V on the device, the coefficients by value
+  const double* lV = nullptr;
+  long long lld = 0;
+  int lrank = 0;
+  LrCoef lcoef = {};
   // an explicit Hessian and nothing else: the kernels of krylov_device.inc and the symmetric product of the matrix
-  bool plain() const { return hess && !gn_jac && shift == 0.0 && !prod; }
+  bool plain() const { return hess && !gn_jac && shift == 0.0 && !prod && lrank == 0; }
 };
 
 // lanes per row of the products with the symmetric Hessian (both triangles from lower storage)
@@ -156,15 +200,19 @@ static int hess_lanes(const hipfact_spmat* hess, int n) { return spmv_lanes(2.0 
 // ... and of stage 2 of the operator: its entries per row (hess_lanes for an explicit Hessian alone)
 static int hess_op_lanes(const HessOp& op, int n) {
   const double ent = (op.hess ? 2.0 * (double)op.hess->nnz : 0.0) + (op.gn_jac ? (double)op.gn_jac->nnz : 0.0);
-  return spmv_lanes(ent / std::max(n, 1));
+  return spmv_lanes(ent / std::max(n, 1) + op.lrank);  // (the term: `rank` more entries in every row)
 }
+// blocks of k_lr_dots (= partials per column of the low-rank term): from n alone
+static int lr_blocks(long long n) { return (int)std::max(1LL, std::min<long long>(LR_BLOCKS, (n + FB - 1) / FB)); }
 
 // The caller's hipfact_hess_op as a HessOp, or HIPFACT_EINVAL (what needs n is left to tr_args_ok)
-static int hess_op_from_abi(hipfact_handle* h, const hipfact_hess_op* in, const char* who, HessOp* op) {
+static int hess_op_from_abi(hipfact_handle* h, const hipfact_hess_op* in, const char* who, HessOp* op,
+                            const hipfact_low_rank* lr = nullptr) {
   const char* bad = nullptr;
+  const bool term = lr && lr->rank != 0;
   if (!in)
     bad = "no operator";
-  else if (!in->hess && !in->gn_jac && in->shift == 0.0 && !in->prod)
+  else if (!in->hess && !in->gn_jac && in->shift == 0.0 && !in->prod && !term)
     bad = "an operator with nothing in it";
   else if (!std::isfinite(in->shift))
     bad = "non-finite shift";
@@ -172,11 +220,28 @@ static int hess_op_from_abi(hipfact_handle* h, const hipfact_hess_op* in, const 
     bad = "a product callback stands alone (no matrix, no shift beside it)";
   else if ((in->hess && in->hess->h != h) || (in->gn_jac && in->gn_jac->h != h))
     bad = "a matrix of another handle";
+  else if (term) {
+    if (in->prod)
+      bad = "a low-rank term beside a product callback";
+    else if (lr->rank < 0 || lr->rank > LR_MAX_RANK)
+      bad = "rank of the low-rank term outside 0 .. 32";
+    else if (!lr->d_V || !lr->coef)
+      bad = "a low-rank term without V or coef";
+    else
+      for (int k = 0; k < lr->rank; ++k)
+        if (!std::isfinite(lr->coef[k])) bad = "non-finite coefficient of the low-rank term";
+  }
   if (bad) {
     h->error = std::string(who) + ": " + bad;
     return HIPFACT_EINVAL;
   }
   *op = HessOp{in->hess, in->gn_jac, in->shift, in->prod, in->user};
+  if (term) {
+    op->lV = lr->d_V;
+    op->lld = lr->ld;
+    op->lrank = lr->rank;
+    for (int k = 0; k < lr->rank; ++k) op->lcoef.c[k] = lr->coef[k];
+  }
   return HIPFACT_OK;
 }
 
@@ -197,8 +262,9 @@ static int hess_op_jx(hipfact_handle* h, hipfact_spmat* J, const double* x, doub
 }
 
 // Stage 1 of a product with x, queued on the handle's stream, and the rows of stage 2: t = J_r x in the handle's
-// r-vector (allocated on first use, grown on demand; HIPFACT_ENOMEM leaves the handle usable).
-static int hess_op_stage1(hipfact_handle* h, const HessOp& op, const double* x, HessRows* R) {
+// r-vector, and u = diag(coef) V^T x of a low-rank term behind its partials in the handle's buffer for them (both
+// allocated on first use, grown on demand; HIPFACT_ENOMEM leaves the handle usable).
+static int hess_op_stage1(hipfact_handle* h, const HessOp& op, int n, const double* x, HessRows* R) {
   memset(R, 0, sizeof(*R));
   R->shift = op.shift;
   if (op.hess) {
@@ -218,16 +284,50 @@ static int hess_op_stage1(hipfact_handle* h, const HessOp& op, const double* x, 
     R->jp = J->cp.as<int>(), R->ji = J->ri.as<int>(), R->jv = J->val.as<double>();
     R->t = h->d_hess_t.as<double>();
   }
+  if (op.lrank > 0) {
+    const int nblk = lr_blocks(n);
+    int rc_err = HIPFACT_OK;
+    with_rank_ceiling(op.lrank, [&](auto ceiling) {
+      constexpr int RC = decltype(ceiling)::value;
+      if (h->d_hess_lr.ensure((size_t)(nblk + 1) * RC * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        h->error = "Hessian operator: out of device memory for the sums of the low-rank term";
+        rc_err = HIPFACT_ENOMEM;
+        return;
+      }
+      double* part = h->d_hess_lr.as<double>();
+      double* u = part + (size_t)nblk * RC;
+      hipLaunchKernelGGL(k_lr_dots<RC>, dim3(nblk), dim3(FB), 0, h->stream, n, op.lrank, op.lV, op.lld, x, part);
+      hipLaunchKernelGGL(k_lr_totals<RC>, dim3(1), dim3(FB), 0, h->stream, op.lrank, op.lcoef, part, nblk, u);
+      R->lu = u;
+    });
+    if (rc_err) return rc_err;
+    HCHECK(h, hipGetLastError());
+    R->lv = op.lV;
+    R->lrank = op.lrank;
+    R->lld = op.lld;
+  }
   return HIPFACT_OK;
 }
 
+// `products` more products under a call that counts them (info "hess_op_products"; with a term also "hess_lr_products",
+// and "hess_lr_rank" is the rank of the last one)
+static void hess_op_count(hipfact_handle* h, const HessOp& op, long products) {
+  if (!h->hess_op_call) return;
+  h->hess_op_products += products;
+  if (op.lrank > 0 && products > 0) {
+    h->hess_lr_products += products;
+    h->hess_lr_rank = op.lrank;
+  }
+}
+
 static int apply_hess(hipfact_handle* h, const HessOp& op, int n, const double* d_in, double* d_out) {
-  if (h->hess_op_call) ++h->hess_op_products;
+  hess_op_count(h, op, 1);
   if (op.plain()) return hipfact_spmat_mult_device(op.hess, 2, d_in, d_out);
   if (!op.prod) {
     HessRows R;
     int rc;
-    if ((rc = hess_op_stage1(h, op, d_in, &R))) return rc;
+    if ((rc = hess_op_stage1(h, op, n, d_in, &R))) return rc;
     const int L = hess_op_lanes(op, n);
     with_lanes(L, [&](auto lanes) {
       hipLaunchKernelGGL(k_hess_op_apply<decltype(lanes)::value>, dim3(row_blocks(n, L, 8192)), dim3(FB), 0, h->stream, n,
@@ -253,12 +353,16 @@ static int tr_args_ok(hipfact_handle* h, const HessOp& op, const double* gradien
                       double trust_radius, const char* who) {
   const Plan& P = h->plan;
   const int n = P.saddle ? P.n : 0;
-  bool hess_ok = op.hess || op.gn_jac || op.shift != 0.0 || op.prod != nullptr;
+  bool hess_ok = op.hess || op.gn_jac || op.shift != 0.0 || op.prod != nullptr || op.lrank > 0;
   if (op.hess) hess_ok = hess_ok && op.hess->h == h && op.hess->rows == n && op.hess->cols == n;
   if (op.gn_jac) hess_ok = hess_ok && op.gn_jac->h == h && op.gn_jac->cols == n;
   if (!P.saddle || !hess_ok || !gradient || !newton_step || !(trust_radius > 0.0)) {
     h->error = std::string(who) + ": needs a factorised saddle matrix and an n x n Hessian (explicit, on the same "
                                   "handle, a residual Jacobian with n columns, or a product callback)";
+    return HIPFACT_EINVAL;
+  }
+  if (op.lrank > 0 && op.lld < n) {
+    h->error = std::string(who) + ": leading dimension of the low-rank term below n";
     return HIPFACT_EINVAL;
   }
   return HIPFACT_OK;
@@ -270,7 +374,7 @@ static int launch_cg_spmv_op(hipfact_handle* h, const HessOp& op, int L, int n, 
                              const double* z, const double* grad, double* Bd, double* part, int* nblk) {
   HessRows R;
   int rc;
-  if ((rc = hess_op_stage1(h, op, d, &R))) return rc;
+  if ((rc = hess_op_stage1(h, op, n, d, &R))) return rc;
   *nblk = row_blocks(n, L, CG_BLOCKS);
   with_lanes(L, [&](auto lanes) {
     hipLaunchKernelGGL(k_cg_spmv_dots_op<decltype(lanes)::value>, dim3(*nblk), dim3(FB), 0, h->stream, n, c, R, d, z, grad,
@@ -283,7 +387,7 @@ static int launch_cg_head_op(hipfact_handle* h, const HessOp& op, int L, int n, 
                              const double* z, const double* grad, double* part) {
   HessRows R;
   int rc;
-  if ((rc = hess_op_stage1(h, op, g, &R))) return rc;
+  if ((rc = hess_op_stage1(h, op, n, g, &R))) return rc;
   with_lanes(L, [&](auto lanes) {
     hipLaunchKernelGGL(k_cg_head_op<decltype(lanes)::value>, dim3(row_blocks(n, L, CG_BLOCKS)), dim3(FB), 0, h->stream, n,
                        ci, co, part_rg, nblk_rg, stride, R, g, d, Bd, z, grad, part);
@@ -294,7 +398,7 @@ static int launch_lz_spmv_op(hipfact_handle* h, const HessOp& op, int L, int n, 
                              double* part, int* nblk) {
   HessRows R;
   int rc;
-  if ((rc = hess_op_stage1(h, op, y, &R))) return rc;
+  if ((rc = hess_op_stage1(h, op, n, y, &R))) return rc;
   *nblk = row_blocks(n, L, CG_BLOCKS);
   with_lanes(L, [&](auto lanes) {
     hipLaunchKernelGGL(k_lz_spmv_dot_op<decltype(lanes)::value>, dim3(*nblk), dim3(FB), 0, h->stream, n, c, R, y, Hy,

@@ -1246,6 +1246,17 @@ static inline void with_lanes(int L, F&& f) {
   else
     f(std::integral_constant<int, 64>());
 }
+// f(std::integral_constant<int, RC>()) for the rank ceiling RC (8 / 16 / 32) of a rank in 1 .. LR_MAX_RANK: the instances of
+// k_lr_dots / k_lr_totals (krylov_hess_op.inc)
+template <class F>
+static inline void with_rank_ceiling(int rank, F&& f) {
+  if (rank <= 8)
+    f(std::integral_constant<int, 8>());
+  else if (rank <= 16)
+    f(std::integral_constant<int, 16>());
+  else
+    f(std::integral_constant<int, 32>());
+}
 // blocks of FB threads for `rows` rows with L lanes each, one pass over the rows when `cap` blocks suffice.  Where the
 // kernel leaves a partial sum per block this is the number of partials, i.e. part of the summation order.
 static inline int row_blocks(long long rows, int L, int cap) {

@@ -475,6 +475,11 @@ struct hipfact_handle : PlanState, SingleSolveMemo {
   // the Hessian as an operator (krylov_hess_op.inc): t = J_r x of its Gauss-Newton term, r doubles, allocated on first use
   // and grown on demand; calls of hipfact_tr_solve_op, and the products formed under it and hipfact_hess_op_apply_device
   DevBuf d_hess_t;
+  // ... the block partials of V^T x of its low-rank term and, behind them, u = diag(coef) V^T x; the products formed with
+  // a term and the rank of the last one
+  DevBuf d_hess_lr;
+  long hess_lr_products = 0;
+  int hess_lr_rank = 0;
   long hess_op_solves = 0, hess_op_products = 0;
   bool hess_op_call = false;
   // the trust-region solve in progress (hipfact_tr_solve_ex): the caller's time limit (tr/tr_types.h:9-16: seconds,

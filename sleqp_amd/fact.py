@@ -517,6 +517,100 @@ class HipFact:
             hip.hipFree(buf)
         return out
 
+    def _low_rank(self, V, coef, ld, n, pad_value):
+        """V (n x rank, any layout) as the column-major array with leading dimension ld that goes to the device, and
+        coef as float64; rows n .. ld - 1 of every column hold pad_value (they are never read)."""
+        V = np.asarray(V, dtype=np.float64)
+        if V.ndim != 2 or V.shape[0] != n:
+            raise ValueError(f"low-rank term: V must be n x rank with n = {n}")
+        rank = V.shape[1]
+        ld = n if ld is None else int(ld)
+        coef = np.ascontiguousarray(coef, dtype=np.float64)
+        if coef.size != rank:
+            raise ValueError("low-rank term: one coefficient per column of V")
+        cols = np.full((rank, max(ld, n)), pad_value, dtype=np.float64)
+        cols[:, :n] = V.T
+        return cols, coef, rank, ld
+
+    def tr_solve_lr(self, gradient, trust_radius: float, V, coef, ld=None, hess=None, gn_jac=None, shift: float = 0.0,
+                    method: int = 0, stat_tol: float = 1e-6, max_iter: int = 100, time_limit: float = -1.0,
+                    pad_value: float = 0.0):
+        """hipfact_tr_solve_lr: tr_solve_op on H = sym(hess) + gn_jac' gn_jac + shift I + V diag(coef) V' with a dense
+        V (n x rank, rank <= 32; a limited-memory BFGS / SR1 Hessian: `qn_terms`).  V = None or rank 0: tr_solve_op
+        itself.  Returns (step, tr_dual, iterations); `self.last_tr` as tr_solve leaves it."""
+        g = np.ascontiguousarray(gradient, dtype=np.float64)
+        n = g.size
+        step = np.empty_like(g)
+        dual, its = C.c_double(), C.c_int()
+        op, _keep = self._hess_op(hess, gn_jac, shift, n)
+        extra = TrExtra(float(time_limit), 0, 1.0, 1.0)
+        hip = C.CDLL("libamdhip64.so")
+        buf = C.c_void_p()
+        lr_ref = None
+        try:
+            if V is not None:
+                cols, coef, rank, ld = self._low_rank(V, coef, ld, n, pad_value)
+                if hip.hipMalloc(C.byref(buf), C.c_size_t(max(cols.nbytes, 16))) != 0:
+                    raise MemoryError("hipMalloc")
+                if cols.nbytes and hip.hipMemcpy(buf, _ptr(cols), C.c_size_t(cols.nbytes), 1) != 0:
+                    raise RuntimeError("hipMemcpy")
+                lr = LowRankStruct(rank, ld, buf.value, coef.ctypes.data_as(C.c_void_p))
+                lr_ref = C.byref(lr)
+            self._check(self._lib.hipfact_tr_solve_lr(self._h, int(method), C.byref(op), lr_ref, _ptr(g),
+                                                      float(trust_radius), stat_tol * 1e-2, int(max_iter), _ptr(step),
+                                                      C.byref(dual), C.byref(its), C.byref(extra)))
+        finally:
+            if buf:
+                hip.hipFree(buf)
+        self.last_tr = {"timed_out": bool(extra.timed_out), "min_rayleigh": extra.min_rayleigh,
+                        "max_rayleigh": extra.max_rayleigh}
+        return step, dual.value, its.value
+
+    def hess_lr_apply(self, x, V, coef, ld=None, hess=None, gn_jac=None, shift: float = 0.0, pad_value: float = 0.0,
+                      witness: bool = False):
+        """hipfact_hess_lr_apply_device around a host vector: y = (sym(hess) + gn_jac' gn_jac + shift I +
+        V diag(coef) V') x.  witness: returns (y, guard, V_after) - eight doubles behind y that were set to a pattern
+        before the call, and V as it stands on the device after it."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        n = x.size
+        if n != int(self.info("n")):  # (the library trusts the length of a device vector)
+            raise ValueError(f"hess_lr_apply: {n} entries for n = {int(self.info('n'))}")
+        op, _keep = self._hess_op(hess, gn_jac, shift, n)
+        G = 8
+        out = np.full(n + G, -7.25, dtype=np.float64)
+        lr_ref, cols = None, np.empty(0)
+        if V is not None:
+            cols, coef, rank, ld = self._low_rank(V, coef, ld, n, pad_value)
+        hip = C.CDLL("libamdhip64.so")
+        buf = C.c_void_p()  # x | y | guard | V
+        if hip.hipMalloc(C.byref(buf), C.c_size_t(16 * n + 8 * G + cols.nbytes + 16)) != 0:
+            raise MemoryError("hipMalloc")
+        try:
+            d_x, d_y = buf.value, buf.value + 8 * n
+            d_V = d_y + 8 * (n + G)
+            if n and hip.hipMemcpy(C.c_void_p(d_x), _ptr(x), C.c_size_t(x.nbytes), 1) != 0:
+                raise RuntimeError("hipMemcpy")
+            if hip.hipMemcpy(C.c_void_p(d_y), _ptr(out), C.c_size_t(out.nbytes), 1) != 0:
+                raise RuntimeError("hipMemcpy")
+            if cols.nbytes and hip.hipMemcpy(C.c_void_p(d_V), _ptr(cols), C.c_size_t(cols.nbytes), 1) != 0:
+                raise RuntimeError("hipMemcpy")
+            if V is not None:
+                lr = LowRankStruct(rank, ld, d_V, coef.ctypes.data_as(C.c_void_p))
+                lr_ref = C.byref(lr)
+            self._check(self._lib.hipfact_hess_lr_apply_device(self._h, C.byref(op), lr_ref, C.c_void_p(d_x),
+                                                               C.c_void_p(d_y)))
+            self._check(self._lib.hipfact_synchronize(self._h))
+            if hip.hipMemcpy(_ptr(out), C.c_void_p(d_y), C.c_size_t(out.nbytes), 2) != 0:
+                raise RuntimeError("hipMemcpy")
+            after = np.empty_like(cols)
+            if cols.nbytes and hip.hipMemcpy(_ptr(after), C.c_void_p(d_V), C.c_size_t(cols.nbytes), 2) != 0:
+                raise RuntimeError("hipMemcpy")
+        finally:
+            hip.hipFree(buf)
+        if witness:
+            return out[:n].copy(), out[n:].copy(), (after, cols)
+        return out[:n].copy()
+
     def lsqr(self, jac_r, cons, rhs, trust_radius: float, stat_tol: float = 1e-6, max_iter: int = -1,
              time_limit: float = -1.0, eps: float = 1e-10):
         """hipfact_lsqr_solve: the Gauss-Newton LSQR loop (tr/lsqr.c:173-330 on the operator of gauss_newton.c) on the
@@ -790,6 +884,38 @@ class HessOpStruct(C.Structure):
     """hipfact_hess_op (include/hipfact.h)"""
     _fields_ = [("hess", C.c_void_p), ("gn_jac", C.c_void_p), ("shift", C.c_double), ("prod", HESS_PROD),
                 ("user", C.c_void_p)]
+
+
+class LowRankStruct(C.Structure):
+    """hipfact_low_rank (include/hipfact.h)"""
+    _fields_ = [("rank", C.c_int), ("ld", C.c_longlong), ("d_V", C.c_void_p), ("coef", C.c_void_p)]
+
+
+QN_SR1, QN_BFGS, QN_DAMPED_BFGS = 0, 1, 2
+
+
+def qn_terms(kind: int, S, Y, memory: int = 5):
+    """hipfact_debug_qn_terms (no GPU): the limited-memory quasi-Newton Hessian of the pairs (columns of S, Y, oldest
+    first; the last `memory` count) as B = scale I + V diag(coef) V'.  kind: QN_SR1, QN_BFGS, QN_DAMPED_BFGS.  Returns
+    (scale, V (n x rank), coef, damped) with damped[j]: used pair j was damped."""
+    from . import _lib
+
+    lib = _lib.load()
+    S = np.asfortranarray(S, dtype=np.float64)
+    Y = np.asfortranarray(Y, dtype=np.float64)
+    if S.ndim != 2 or S.shape != Y.shape:
+        raise ValueError("qn_terms: S and Y must be n x npairs")
+    n, npairs = S.shape
+    used = min(npairs, memory)
+    V = np.zeros((max(n, 1), 2 * max(used, 1)), order="F")
+    coef = np.zeros(2 * max(used, 1))
+    scale, rank, damped = C.c_double(), C.c_int(), C.c_uint()
+    rc = lib.hipfact_debug_qn_terms(int(kind), n, npairs, int(memory), _ptr(S), _ptr(Y), C.byref(scale), _ptr(V),
+                                    _ptr(coef), C.byref(rank), C.byref(damped))
+    if rc != 0:
+        raise ValueError(f"hipfact_debug_qn_terms: {rc}")
+    r = rank.value
+    return scale.value, np.ascontiguousarray(V[:n, :r]), coef[:r].copy(), [bool(damped.value >> j & 1) for j in range(used)]
 
 
 LSQR_PROD = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double))
