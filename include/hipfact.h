@@ -906,6 +906,79 @@ int hipfact_debug_lr_dots_blocks(long long n);
 int hipfact_debug_qn_terms(int kind, int n, int npairs, int memory, const double* S, const double* Y, double* scale,
                            double* V, double* coef, int* rank, unsigned* damped);
 
+/* ---- extreme eigenpairs of the projected Hessian (Lanczos) ---------------- */
+
+/* The extreme eigenpair of the reduced Hessian Z' H Z on the null space of the working set, Z an orthonormal basis of
+ * null(A_W): the question the reference can only ask of the Rayleigh quotients its Krylov run happened to see -
+ * check_spectrum (newton.c:318-346) reads min_rayleigh / max_rayleigh and warns about a negative one for a Hessian
+ * flagged PSD, and both are public solver state (SLEQP_SOLVER_STATE_REAL_MIN_RAYLEIGH / _MAX_RAYLEIGH,
+ * problem_solver/state.c:46-51).  hipfact_tr_extra reproduces those numbers; they are the extremes of d.Hd / d.d over the
+ * few directions of one CG run, a loose bound from the inside that certifies nothing.  This call answers: is
+ * lambda_min(Z' H Z) >= 0 at the final iterate, and along which direction not; which `shift` of hipfact_hess_op makes the
+ * operator positive definite (CG where GLTR runs today); the condition lambda_max / lambda_min of the reduced Hessian.
+ *
+ * Explicitly restarted Lanczos on P H P (P: the factorised KKT projection of the handle, H: any operator form of
+ * hipfact_tr_solve_lr, the callback `prod` alone included) with two passes of classical Gram-Schmidt against the kept
+ * basis of `basis` vectors; the rule is sleqp_amd/csrc/ritz_rule.h, and the order of its step - three-term subtraction,
+ * THEN the projection, THEN the reorthogonalisation - is what keeps the run off the |W| zero eigenvalues P H P has on
+ * range(A_W').  theta is an eigenvalue of Z' H Z, not one of those zeros.  A y much shorter than the w it was projected
+ * from (gamma_{k+1} < ||w|| / 16: the first step behind a restart) is projected a second time, so that every basis vector
+ * lies in null(A_W) to rounding: a restarted cycle has one projection more than steps.
+ *   which        HIPFACT_EIG_LEFTMOST / HIPFACT_EIG_RIGHTMOST
+ *   start        n values or NULL: element i is the top 53 bits of splitmix64(i + 1) scaled to [-0.5, 0.5)
+ *   vec          n values or NULL: the unit eigenvector in the caller's variables, its first component of largest
+ *                magnitude positive; not written for the statuses EMPTY and NONFINITE
+ *   info in      rel_tol (<= 0: 2^-40), basis (0: 32; else 2 .. 64), max_restarts (< 0: 40), time_limit (seconds from
+ *                the entry, < 0: none; looked at behind every Lanczos step)
+ *   info out     status; restarts; products: the products of the Lanczos steps (the measured residual takes one more);
+ *                projections: every projection of the call, the residual's included; dim = n - |W| with |W| = N - n
+ *                (unit rows of active bounds included); theta; resid = ||P (H x) - theta x||_2 of the returned x,
+ *                MEASURED by one more product and projection behind the loop; est = gamma_{k+1} |s_k|, the Lanczos
+ *                estimate of the last step; scale = max |eigenvalue| of the last tridiagonal matrix
+ *   status       CONVERGED: est <= rel_tol scale.  EXHAUSTED: the Krylov space is invariant (gamma_{k+1} <= 2^-40 scale)
+ *                or as large as the null space: the pair is exact to rounding.  RESTART_LIMIT: theta is still a Rayleigh
+ *                quotient, a bound from the inside (>= lambda_min, <= lambda_max).  TIME.  EMPTY: dim = 0 or the projected
+ *                start vector is 0.  NONFINITE.  Every status returns HIPFACT_OK.
+ * The call blocks and begins with what hipfact_check does.  It is not "the last solve": hipfact_solution* are unchanged.
+ * Its projections ARE counted, as those of the loops above: each is a cadence projection by route (a), "num_solve"
+ * advances by info.projections; its products count as hipfact_hess_op_apply_device counts them.  Info "eig_calls":
+ * calls that passed the checks; "eig_products": products formed under them.  The same handle state gives the same bits.
+ * The basis (n_even x basis doubles) is allocated on first use and kept with the plan; HIPFACT_ENOMEM leaves the handle
+ * usable.  Refused: everything hipfact_tr_solve_lr refuses, with its codes and in its order; HIPFACT_ESTATE in the
+ * generic mode; HIPFACT_EINVAL for a NULL info, `which` outside +-1, basis outside 0, 2 .. 64; and HIPFACT_ESTATE on a
+ * factor with an active static-pivot shift - a rank-deficient working set has a null space larger than n - |W|, see
+ * hipfact_nullspace. */
+enum
+{
+  HIPFACT_EIG_LEFTMOST  = -1,
+  HIPFACT_EIG_RIGHTMOST = 1
+};
+enum
+{
+  HIPFACT_EIG_CONVERGED     = 0, /* est <= rel_tol * scale */
+  HIPFACT_EIG_EXHAUSTED     = 1, /* Krylov space invariant or as large as the null space: the pair is exact to rounding */
+  HIPFACT_EIG_RESTART_LIMIT = 2, /* theta is still a Rayleigh quotient: a bound from the inside */
+  HIPFACT_EIG_TIME          = 3,
+  HIPFACT_EIG_EMPTY         = 4, /* null space of dimension 0, or the projected start vector is 0 */
+  HIPFACT_EIG_NONFINITE     = 5
+};
+typedef struct hipfact_eig_info
+{
+  /* in  */
+  double rel_tol;
+  int basis;
+  int max_restarts;
+  double time_limit;
+  /* out */
+  int status, restarts, products, projections, dim;
+  double theta, resid, est, scale;
+} hipfact_eig_info;
+int hipfact_projected_eig_device(hipfact_handle* h, const hipfact_hess_op* op, const hipfact_low_rank* lr /* nullable */,
+                                 int which, const double* d_start /* nullable */, double* d_vec /* nullable */,
+                                 hipfact_eig_info* info);
+int hipfact_projected_eig(hipfact_handle* h, const hipfact_hess_op* op, const hipfact_low_rank* lr /* nullable */, int which,
+                          const double* start /* nullable */, double* vec /* nullable */, hipfact_eig_info* info);
+
 /* ---- Gauss-Newton LSQR (least-squares problems, TR_SOLVER = LSQR) ------- */
 
 /* Residual Jacobian J_r (r x n) as a product on host vectors: trans = 0: out (r) = J_r in (n); trans = 1: out (n) =
@@ -1210,6 +1283,20 @@ int hipfact_debug_gmres_dense_steps(int N, int n0, const double* K, const double
  * y (k values) minimises ||beta e_1 - H y||_2; *est = |g_{k+1}|, the norm of that residual.  HIPFACT_EINVAL for k
  * outside [1, 16] or a NULL array. */
 int hipfact_debug_gmres_hessenberg(int k, const double* H, double beta, double* y, double* est);
+/* The rule of hipfact_projected_eig (sleqp_amd/csrc/ritz_rule.h) with dense products, no GPU needed; used by the tests.
+ * H and P (the orthogonal projector onto the null space, of rank dim) symmetric n x n, column-major with ld >= n; start
+ * n values or NULL (the default vector); info as in the call (a time limit counts from the entry); vec n values or NULL;
+ * Q_out n x basis with leading dimension n or NULL: the basis of the last cycle, zero columns behind it.  Every sum in
+ * index order.  HIPFACT_EINVAL for n < 0, ld < n, dim outside [0, n], which outside +-1, basis outside 0, 2 .. 64 or a
+ * NULL matrix or info. */
+int hipfact_debug_ritz_dense(int n, const double* H, const double* P, long long ld, int dim, int which,
+                             const double* start /* nullable */, hipfact_eig_info* info, double* vec /* nullable */,
+                             double* Q_out /* nullable */);
+/* The tridiagonal eigenpair of that rule: the extreme pair (which = -1 leftmost, +1 rightmost) of
+ * tridiag(delta[0 .. k); gamma[0 .. k - 1)), gamma[i] coupling i and i + 1, k in 1 .. 64 - the Sturm bisection of the
+ * trust-region subproblem (tridiag_tr.cpp) run until the interval no longer splits, inverse iteration with row exchanges,
+ * theta = s' T s; s has unit length.  HIPFACT_EINVAL for k or which out of range, a NULL or a non-finite array. */
+int hipfact_debug_ritz_tridiag(int k, const double* delta, const double* gamma, int which, double* theta, double* s);
 /* The k x k LU of hipfact_border_set (sleqp_amd/csrc/border_rule.h), no GPU needed; used by the tests.  S: k x k
  * column-major; LU receives P S = L U (unit L below the diagonal), piv[j] the row exchanged with row j at step j,
  * *rcond = 1 / (||S||_1 ||S^-1||_1) from the explicit inverse (0 behind a zero or non-finite pivot).  Returns

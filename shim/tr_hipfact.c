@@ -568,6 +568,64 @@ sleqp_hipfact_tr_push_pair(SleqpHipfactTR* solver, int kind, const SleqpVec* ste
 }
 
 SLEQP_RETCODE
+sleqp_hipfact_tr_spectrum(SleqpHipfactTR* solver, int which, double rel_tol, double* theta, double* resid, int* status)
+{
+  if (!solver->handle)
+  {
+    sleqp_raise(SLEQP_INTERNAL_ERROR, "hipfact TR solver: no factorisation bound (sleqp_hipfact_tr_bind)");
+  }
+
+  if (!solver->hessian && !solver->lsq_jac && !solver->lr_active)
+  {
+    sleqp_raise(SLEQP_ILLEGAL_ARGUMENT,
+                "hipfact TR solver: the spectrum needs a device-resident Hessian (sleqp_hipfact_tr_set_hessian, "
+                "_set_gauss_newton or _set_low_rank); only the problem's product callback is set, and that product "
+                "needs the multipliers of a solve in progress");
+  }
+
+  /* the operator of tr_callback_solve */
+  const hipfact_hess_op op = {.hess   = solver->hessian,
+                              .gn_jac = solver->lsq_jac,
+                              .shift  = solver->lm_factor + (solver->lr_active ? solver->lr_scale : 0.),
+                              .prod   = NULL,
+                              .user   = NULL};
+
+  const hipfact_low_rank lr = {.rank = solver->lr_active ? solver->lr_rank : 0,
+                               .ld   = solver->lr_ld,
+                               .d_V  = (const double*)solver->lr_dev_V,
+                               .coef = solver->lr_coef};
+
+  hipfact_eig_info info = {.rel_tol = rel_tol, .basis = 0, .max_restarts = -1, .time_limit = -1.};
+
+  const int rc = hipfact_projected_eig(solver->handle, &op, &lr, which, NULL, NULL, &info);
+
+  if (rc == HIPFACT_EINVAL)
+  {
+    sleqp_raise(SLEQP_ILLEGAL_ARGUMENT, "Caught hipfact error <%d> (%s)", rc, hipfact_last_error(solver->handle));
+  }
+
+  if (rc != HIPFACT_OK)
+  {
+    sleqp_raise(SLEQP_INTERNAL_ERROR, "Caught hipfact error <%d> (%s)", rc, hipfact_last_error(solver->handle));
+  }
+
+  if (theta)
+  {
+    *theta = info.theta;
+  }
+  if (resid)
+  {
+    *resid = info.resid;
+  }
+  if (status)
+  {
+    *status = info.status;
+  }
+
+  return SLEQP_OKAY;
+}
+
+SLEQP_RETCODE
 sleqp_hipfact_tr_bind(SleqpHipfactTR* solver, struct hipfact_handle* handle)
 {
   if (!handle)

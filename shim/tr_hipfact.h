@@ -80,4 +80,16 @@ SLEQP_WARNUNUSED
 SLEQP_RETCODE
 sleqp_hipfact_tr_reset_pairs(SleqpHipfactTR* ctl);
 
+/* The extreme eigenvalue of the reduced Hessian Z' H Z on the null space of the bound factorisation's working set
+ * (hipfact_projected_eig): what check_spectrum (newton.c:318-346) can only bound from the inside with the Rayleigh
+ * quotients of one Krylov run (SLEQP_SOLVER_STATE_REAL_MIN_RAYLEIGH / _MAX_RAYLEIGH, problem_solver/state.c:46-51).  H is
+ * the device-resident form the solver holds - the explicit Hessian, the Gauss-Newton term, the low-rank term, any sum of
+ * them, as in the solve.  which: -1 the leftmost, +1 the rightmost eigenvalue; rel_tol <= 0: 2^-40.  Out: theta, the
+ * measured residual ||P H x - theta x||_2 of its unit vector, and the status HIPFACT_EIG_* (0 converged, 1 exhausted: exact
+ * to rounding, 2 restart limit: a bound from the inside, 4 empty null space).  With nothing but the problem's product
+ * callback set it raises SLEQP_ILLEGAL_ARGUMENT: that product needs the multipliers of a solve in progress. */
+SLEQP_WARNUNUSED
+SLEQP_RETCODE
+sleqp_hipfact_tr_spectrum(SleqpHipfactTR* ctl, int which, double rel_tol, double* theta, double* resid, int* status);
+
 #endif /* SLEQP_TR_HIPFACT_H */

@@ -45,6 +45,7 @@ SYMBOLS = [
     "hipfact_spmat_mult_device", "hipfact_steihaug_solve", "hipfact_tr_solve", "hipfact_tr_solve_ex", "hipfact_tr_solve_op", "hipfact_hess_op_apply_device", "hipfact_tr_solve_lr", "hipfact_hess_lr_apply_device", "hipfact_lsqr_solve", "hipfact_tridiag_tr", "hipfact_set_option", "hipfact_get_info", "hipfact_debug_copy", "hipfact_debug_pool_selftest",
     "hipfact_debug_place_rows", "hipfact_debug_place_items", "hipfact_debug_multi_slices", "hipfact_debug_schur_items", "hipfact_debug_refine_cadence", "hipfact_plan_create",
     "hipfact_debug_spmat_row_blocks", "hipfact_debug_spmv_lanes", "hipfact_debug_lr_dots_blocks", "hipfact_debug_qn_terms", "hipfact_device_upload", "hipfact_device_release",
+    "hipfact_projected_eig_device", "hipfact_projected_eig", "hipfact_debug_ritz_dense", "hipfact_debug_ritz_tridiag",
     "hipfact_plan_free", "hipfact_plan_error", "hipfact_plan_array", "hipfact_plan_scalar",
 ]
 
@@ -159,6 +160,11 @@ def load() -> C.CDLL:
         lib.hipfact_device_release.argtypes = [vp, C.POINTER(vp)]
         lib.hipfact_debug_qn_terms.argtypes = [ci, ci, ci, ci, vp, vp, C.POINTER(cd), vp, vp, C.POINTER(ci),
                                                C.POINTER(C.c_uint)]
+    if hasattr(lib, "hipfact_projected_eig"):
+        lib.hipfact_projected_eig_device.argtypes = [vp, vp, vp, ci, vp, vp, vp]
+        lib.hipfact_projected_eig.argtypes = [vp, vp, vp, ci, vp, vp, vp]
+        lib.hipfact_debug_ritz_dense.argtypes = [ci, vp, vp, C.c_longlong, ci, ci, vp, vp, vp, vp]
+        lib.hipfact_debug_ritz_tridiag.argtypes = [ci, vp, vp, ci, C.POINTER(cd), vp]
     lib.hipfact_lsqr_solve.argtypes = [vp, vp, vp, cd, cd, cd, ci, vp, vp]
     lib.hipfact_tridiag_tr.argtypes = [ci, vp, vp, cd, cd, vp, C.POINTER(cd)]
     lib.hipfact_set_option.argtypes = [vp, C.c_char_p, cd]

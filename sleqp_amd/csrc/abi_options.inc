@@ -530,6 +530,7 @@ int hipfact_get_info(const hipfact_handle* h, const char* name, double* value) {
   INFO("null_dim", (h->null_for_factor == h->num_factor && h->null_for_delta == h->reg_delta) ? h->null_res.dim : -1)
   INFO("null_status", (h->null_for_factor == h->num_factor && h->null_for_delta == h->reg_delta) ? h->null_res.status : -1)
   INFO("border_k", border_current(h) ? h->border_k : -1) INFO("border_sets", h->border_sets) INFO("border_solves", h->border_solves) INFO("border_passes", h->border_passes) INFO("border_last_status", h->border_last_status) INFO("border_rcond", h->border_rcond)
+  INFO("eig_calls", h->eig_calls) INFO("eig_products", h->eig_products)
   INFO("gmres_solves", h->gmres_solves) INFO("gmres_cycles", h->gmres_cycles) INFO("gmres_steps", h->gmres_steps) INFO("gmres_last_status", h->gmres_last_status)
   INFO("extra_solves", h->extra_solves) INFO("extra_passes", h->extra_passes) INFO("extra_last_status", h->extra_last_status)
   INFO("extra_multi_solves", h->extra_multi_solves) INFO("extra_multi_cols", h->extra_multi_cols) INFO("extra_multi_passes", h->extra_multi_passes)

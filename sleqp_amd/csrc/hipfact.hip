@@ -5,7 +5,7 @@
 // state.  All numerics run on the device; there is no CPU fallback: without a
 // usable GPU hipfact_create fails with HIPFACT_EDEVICE.
 //
-// The host translation unit (the kernels are compiled separately: kernels_factor.hip / kernels_solve.hip / kernels_extra.hip / kernels_nullspace.hip / kernels_selinv.hip / kernels_gmres.hip / kernels_border.hip, declared in the
+// The host translation unit (the kernels are compiled separately: kernels_factor.hip / kernels_solve.hip / kernels_extra.hip / kernels_nullspace.hip / kernels_selinv.hip / kernels_gmres.hip / kernels_border.hip / kernels_ritz.hip, declared in the
 // generated kernels_decl.h), split by role:
 //   runtime_types.inc   buffers, plan state, the handle          abi_core.inc         create .. solution (SleqpFact)
 //   runtime_plan.inc    upload of a plan, work items             abi_working_set.inc  superset plans, assemble_kkt
@@ -22,6 +22,8 @@
 //   runtime_selinv.inc  selected inverse: K^-1 on the pattern of the factor (selinv_host.h) abi_selinv.inc hipfact_selected_inverse, hipfact_inverse_diagonal[_device], hipfact_inverse_entries_device
 //   runtime_gmres.inc   GMRES(16) on the statically pivoted factor (gmres_rule.h) abi_gmres.inc hipfact_solve[_device]_gmres, _debug_gmres_dense
 //   runtime_border.inc  bordered solve [K B; B^T C] on the factor of K (border_rule.h) abi_border.inc hipfact_border_set / _clear, hipfact_solve[_device]_bordered, _debug_border_*
+//   runtime_ritz.inc    extreme eigenpairs of the projected Hessian, restarted Lanczos (ritz_rule.h) abi_ritz.inc hipfact_projected_eig[_device], _debug_ritz_*
+//                       (included by abi_ritz.inc behind abi_krylov.inc: it runs on that file's operator product)
 //   refine_cadence.h    refinement cadence of the single solve: passes in the graph, residual checks, deferred verdicts
 //                       (pure host rules, like xcd_place.h and multi_slices.h)
 #include <hip/hip_runtime.h>
@@ -61,6 +63,7 @@
 #include "nullspace_rule.h"
 #include "gmres_rule.h"
 #include "border_rule.h"
+#include "ritz_rule.h"
 #include "selinv_types.h"
 #include "selinv_host.h"
 #include "dd_arith.h"
@@ -90,5 +93,6 @@ extern "C" {
 #include "abi_border.inc"
 #include "abi_working_set.inc"
 #include "abi_krylov.inc"
+#include "abi_ritz.inc"
 #include "abi_options.inc"
 }  // extern "C"

@@ -274,6 +274,11 @@ struct PlanState : FactorMemo {
   // block (d_bmat).  They live with the plan because its solve graphs hold two of the addresses.  Allocated by
   // hipfact_border_set.
   DevBuf d_bvec, d_bmat;
+  // projected eigenpairs (runtime_ritz.inc): the kept Lanczos basis, n_even x basis doubles (d_ritzQ), and the vectors
+  // of the recurrence behind one another (d_ritzvec: right-hand side and solution of the projections, N_ext each, then
+  // y | H q | x | the start vector, n_even each).  They live with the plan because its solve graphs hold two of the
+  // addresses.  Allocated by the first such call of the state, the basis grown when a call asks for more columns.
+  DevBuf d_ritzQ, d_ritzvec;
   // selected inverse (runtime_selinv.inc): the Z panels and W = L21 X in the layout of d_L, the Z_UU blocks (sum of u^2
   // doubles, no reuse), their offsets, the tree's arrays for the lookup and iperm; a 16-column block of the fallback.
   // Allocated by the first such call of the state (selinv_ws); Z belongs to the factorisation number selinv_for_factor
@@ -583,6 +588,12 @@ struct hipfact_handle : PlanState, SingleSolveMemo {
   PinBuf h_selout;
   long selinv_runs = 0;
   long long selinv_served = 0, selinv_fallback_cols = 0;
+  // projected eigenpairs (runtime_ritz.inc): partials of its sums, the coefficients c and the scalars of a step; the
+  // pinned words the host reads behind a step's synchronisation and the staging of the coordinates s; counters of
+  // hipfact_get_info
+  DevBuf d_ritzsmall;
+  PinBuf h_ritz;
+  long eig_calls = 0, eig_products = 0;
 };
 
 // The refinement cadence of the handle (refine_cadence.h): its four parts, the option values it reads, and what the

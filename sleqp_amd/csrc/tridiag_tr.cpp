@@ -168,6 +168,104 @@ int tridiag_tr_solve(int k, const double* delta, const double* gamma, double gam
   return 0;
 }
 
+namespace {
+
+// leftmost eigenvalue by the bisection above, run until the interval no longer splits (the subproblem's own call stops
+// at 1e-15 max(1, |.|): enough for a multiplier, not for an eigenvalue far below 1 in magnitude)
+double leftmost_eigenvalue_tight(int k, const double* delta, const double* gamma) {
+  double lo = delta[0], hi = delta[0];
+  for (int i = 0; i < k; ++i) {
+    const double r = (i > 0 ? std::fabs(gamma[i]) : 0.0) + (i + 1 < k ? std::fabs(gamma[i + 1]) : 0.0);
+    lo = std::min(lo, delta[i] - r);
+    hi = std::max(hi, delta[i] + r);
+  }
+  for (int it = 0; it < 2200; ++it) {
+    const double mid = 0.5 * (lo + hi);
+    if (!(mid > lo && mid < hi)) break;
+    if (sturm_count(k, delta, gamma, mid) >= 1)
+      hi = mid;
+    else
+      lo = mid;
+  }
+  return 0.5 * (lo + hi);
+}
+
+}  // namespace
+
+int tridiag_leftmost_pair(int k, const double* delta, const double* gamma, double* theta, double* s, double* absmax) {
+  if (k <= 0) return -1;
+  for (int i = 0; i < k; ++i)
+    if (!(std::fabs(delta[i]) < 1.7e308) || (i > 0 && !(std::fabs(gamma[i]) < 1.7e308))) return -2;
+  const double lam = leftmost_eigenvalue_tight(k, delta, gamma);
+  {
+    std::vector<double> nd(delta, delta + k);
+    for (int i = 0; i < k; ++i) nd[i] = -nd[i];
+    const double top = -leftmost_eigenvalue_tight(k, nd.data(), gamma);
+    *absmax = std::max(std::fabs(lam), std::fabs(top));
+  }
+  if (k == 1) {
+    s[0] = 1.0;
+    *theta = delta[0];
+    return 0;
+  }
+  // U of P (T - lam I) = L U: diagonal u0, the two superdiagonals u1 and u2; multipliers m and the exchanges
+  std::vector<double> u0(k), u1(k, 0.0), u2(k, 0.0), m(k, 0.0), x(k), t(k);
+  std::vector<char> swapped(k, 0);
+  const double tiny = std::max(*absmax, 1e-300) * 0x1p-52;
+  {
+    double d = delta[0] - lam, c = gamma[1];  // the row in work: (d, c, 0)
+    for (int i = 0; i + 1 < k; ++i) {
+      const double sub = gamma[i + 1], dn = delta[i + 1] - lam, cn = i + 2 < k ? gamma[i + 2] : 0.0;
+      if (std::fabs(sub) > std::fabs(d)) {
+        swapped[i] = 1;
+        u0[i] = sub, u1[i] = dn, u2[i] = cn;
+        m[i] = d / sub;
+        d = c - m[i] * dn;
+        c = -m[i] * cn;
+      } else {
+        if (d == 0.0) d = tiny;
+        u0[i] = d, u1[i] = c, u2[i] = 0.0;
+        m[i] = sub / d;
+        d = dn - m[i] * c;
+        c = cn;
+      }
+    }
+    u0[k - 1] = d;
+  }
+  for (int i = 0; i < k; ++i)
+    if (std::fabs(u0[i]) < tiny) u0[i] = u0[i] < 0.0 ? -tiny : tiny;
+  for (int i = 0; i < k; ++i) x[i] = 1.0 + 0.37 * ((i * 2654435761u) % 1000) / 1000.0;  // no accidental orthogonality
+  for (int it = 0; it < 4; ++it) {
+    for (int i = 0; i < k; ++i) t[i] = x[i];
+    for (int i = 0; i + 1 < k; ++i) {
+      if (swapped[i]) std::swap(t[i], t[i + 1]);
+      t[i + 1] -= m[i] * t[i];
+    }
+    for (int i = k - 1; i >= 0; --i) {
+      double v = t[i];
+      if (i + 1 < k) v -= u1[i] * t[i + 1];
+      if (i + 2 < k) v -= u2[i] * t[i + 2];
+      t[i] = v / u0[i];
+    }
+    double big = 0.0;
+    for (int i = 0; i < k; ++i) big = std::max(big, std::fabs(t[i]));
+    if (!(big > 0.0) || !(big < 1.7e308)) return -3;
+    for (int i = 0; i < k; ++i) t[i] /= big;  // (no overflow in the norm)
+    const double nt = norm2(k, t.data());
+    for (int i = 0; i < k; ++i) x[i] = t[i] / nt;
+  }
+  double rq = 0.0;
+  for (int i = 0; i < k; ++i) {
+    double ti = delta[i] * x[i];
+    if (i > 0) ti += gamma[i] * x[i - 1];
+    if (i + 1 < k) ti += gamma[i + 1] * x[i + 1];
+    rq += x[i] * ti;
+  }
+  for (int i = 0; i < k; ++i) s[i] = x[i];
+  *theta = rq;
+  return 0;
+}
+
 }  // namespace hipfact
 
 extern "C" int hipfact_tridiag_tr(int k, const double* delta, const double* gamma, double gamma0, double radius,

@@ -9,4 +9,10 @@ namespace hipfact {
 int tridiag_tr_solve(int k, const double* delta, const double* gamma, double gamma0, double radius, double* h,
                      double* lambda);
 
+// The leftmost eigenpair of T (same arrays; k >= 1): the eigenvalue by the Sturm bisection of the subproblem above, run
+// until the interval no longer splits, its unit vector s by inverse iteration on T - theta I (elimination with row
+// exchanges), then *theta = s^T T s.  *absmax = max |eigenvalue of T| (the other end by the same bisection on -T).
+// Returns 0 on success.  gamma may have either sign.  (The rightmost pair of T: the leftmost of -T, the eigenvalue negated.)
+int tridiag_leftmost_pair(int k, const double* delta, const double* gamma, double* theta, double* s, double* absmax);
+
 }  // namespace hipfact

@@ -611,6 +611,59 @@ class HipFact:
             return out[:n].copy(), out[n:].copy(), (after, cols)
         return out[:n].copy()
 
+    def projected_eig(self, which: int = -1, hess=None, gn_jac=None, shift: float = 0.0, V=None, coef=None, ld=None,
+                      prod=None, start=None, want_vec: bool = True, rel_tol: float = 0.0, basis: int = 0,
+                      max_restarts: int = -1, time_limit: float = -1.0, device=None):
+        """hipfact_projected_eig: the extreme eigenpair (which = EIG_LEFTMOST / EIG_RIGHTMOST) of the reduced Hessian
+        Z' H Z on the null space of the working set, H = sym(hess) + gn_jac' gn_jac + shift I + V diag(coef) V' as in
+        tr_solve_lr, or the callable `prod` (d -> H d on host arrays) alone.  start: n values or None (the default
+        vector).  Returns (info, vec): the hipfact_eig_info as a dict (status, status_name, restarts, products,
+        projections, dim, theta, resid, est, scale) and the unit eigenvector, or None without want_vec and for the
+        statuses EMPTY and NONFINITE."""
+        n = int(self.info("n"))
+        if prod is not None and hess is not None:
+            raise ValueError("projected_eig: `prod` stands alone")
+        op, _keep = self._hess_op(prod if prod is not None else hess, gn_jac, shift, n)
+        info = EigInfo(float(rel_tol), int(basis), int(max_restarts), float(time_limit))
+        vec = np.full(n, np.nan) if want_vec else None
+        st = None
+        if start is not None:
+            st = np.ascontiguousarray(start, dtype=np.float64)
+            if st.size != n:
+                raise ValueError(f"projected_eig: {st.size} start values for n = {n}")
+        hip = C.CDLL("libamdhip64.so")
+        buf = C.c_void_p()
+        lr_ref = None
+        try:
+            if V is not None:
+                cols, coef, rank, ld = self._low_rank(V, coef, ld, n, 0.0)
+                if hip.hipMalloc(C.byref(buf), C.c_size_t(max(cols.nbytes, 16))) != 0:
+                    raise MemoryError("hipMalloc")
+                if cols.nbytes and hip.hipMemcpy(buf, _ptr(cols), C.c_size_t(cols.nbytes), 1) != 0:
+                    raise RuntimeError("hipMemcpy")
+                lr = LowRankStruct(rank, ld, buf.value, coef.ctypes.data_as(C.c_void_p))
+                lr_ref = C.byref(lr)
+            if device is not None:  # (projected_eig_device: device pointers, or 0 / None for "none")
+                self._check(self._lib.hipfact_projected_eig_device(self._h, C.byref(op), lr_ref, int(which),
+                                                                   C.c_void_p(device[0] or None), C.c_void_p(device[1] or None),
+                                                                   C.byref(info)))
+            else:
+                self._check(self._lib.hipfact_projected_eig(self._h, C.byref(op), lr_ref, int(which),
+                                                            _ptr(st) if st is not None else None,
+                                                            _ptr(vec) if vec is not None else None, C.byref(info)))
+        finally:
+            if buf:
+                hip.hipFree(buf)
+        out = info.as_dict()
+        if out["status"] in (EIG_EMPTY, EIG_NONFINITE) or device is not None:
+            vec = None
+        return out, vec
+
+    def projected_eig_device(self, which: int, d_start_ptr, d_vec_ptr, **kw) -> dict:
+        """hipfact_projected_eig_device: projected_eig with the start vector read from and the eigenvector written to
+        device memory of the caller (n doubles each; 0 / None: the default start vector / no vector).  Returns the info."""
+        return self.projected_eig(which, want_vec=False, device=(d_start_ptr, d_vec_ptr), **kw)[0]
+
     def lsqr(self, jac_r, cons, rhs, trust_radius: float, stat_tol: float = 1e-6, max_iter: int = -1,
              time_limit: float = -1.0, eps: float = 1e-10):
         """hipfact_lsqr_solve: the Gauss-Newton LSQR loop (tr/lsqr.c:173-330 on the operator of gauss_newton.c) on the
@@ -761,6 +814,65 @@ def gmres_hessenberg(H, beta: float):
     if rc != 0:
         raise HipfactError(rc, "hipfact_debug_gmres_hessenberg")
     return y, est.value
+
+
+EIG_LEFTMOST, EIG_RIGHTMOST = -1, 1
+EIG_CONVERGED, EIG_EXHAUSTED, EIG_RESTART_LIMIT, EIG_TIME, EIG_EMPTY, EIG_NONFINITE = range(6)
+EIG_STATUS = ["CONVERGED", "EXHAUSTED", "RESTART_LIMIT", "TIME", "EMPTY", "NONFINITE"]
+
+
+class EigInfo(C.Structure):
+    """hipfact_eig_info (include/hipfact.h)"""
+    _fields_ = [("rel_tol", C.c_double), ("basis", C.c_int), ("max_restarts", C.c_int), ("time_limit", C.c_double),
+                ("status", C.c_int), ("restarts", C.c_int), ("products", C.c_int), ("projections", C.c_int),
+                ("dim", C.c_int), ("theta", C.c_double), ("resid", C.c_double), ("est", C.c_double), ("scale", C.c_double)]
+
+    def as_dict(self) -> dict:
+        out = {k: getattr(self, k) for k, _ in self._fields_[4:]}
+        out["status_name"] = EIG_STATUS[self.status] if 0 <= self.status < len(EIG_STATUS) else str(self.status)
+        return out
+
+
+def ritz_dense(H, P, dim: int, which: int = -1, start=None, rel_tol: float = 0.0, basis: int = 0, max_restarts: int = -1,
+               time_limit: float = -1.0, want_basis: bool = False):
+    """hipfact_debug_ritz_dense: the rule of hipfact_projected_eig with dense products (H and the orthogonal projector P
+    of rank dim), on the host (no GPU).  Returns (info, vec) as HipFact.projected_eig does - and with want_basis
+    (info, vec, Q): the basis of the last cycle, n x basis, zero columns behind its vectors."""
+    H = np.asfortranarray(H, dtype=np.float64)
+    P = np.asfortranarray(P, dtype=np.float64)
+    assert H.ndim == 2 and H.shape[0] == H.shape[1] and P.shape == H.shape, (H.shape, P.shape)
+    n = H.shape[0]
+    info = EigInfo(float(rel_tol), int(basis), int(max_restarts), float(time_limit))
+    vec = np.full(n, np.nan)
+    nb = 32 if basis == 0 else int(basis)
+    Q = np.zeros((n, max(nb, 1)), order="F") if want_basis else None
+    st = None
+    if start is not None:
+        st = np.ascontiguousarray(start, dtype=np.float64)
+        assert st.size == n
+    rc = _lib.load().hipfact_debug_ritz_dense(n, _ptr(H), _ptr(P), max(n, 1), int(dim), int(which),
+                                              _ptr(st) if st is not None else None, C.byref(info), _ptr(vec),
+                                              _ptr(Q) if Q is not None else None)
+    if rc != 0:
+        raise HipfactError(rc, "hipfact_debug_ritz_dense")
+    out = info.as_dict()
+    v = None if out["status"] in (EIG_EMPTY, EIG_NONFINITE) else vec
+    return (out, v, Q) if want_basis else (out, v)
+
+
+def ritz_tridiag(delta, gamma, which: int = -1):
+    """hipfact_debug_ritz_tridiag: (theta, s), the extreme eigenpair of tridiag(delta; gamma) with len(gamma) =
+    len(delta) - 1, by the bisection and inverse iteration of the rule (no GPU)."""
+    d = np.ascontiguousarray(delta, dtype=np.float64)
+    g = np.ascontiguousarray(gamma, dtype=np.float64)
+    k = d.size
+    assert g.size == max(k - 1, 0), (k, g.size)
+    s = np.empty(max(k, 1))
+    theta = C.c_double(0.0)
+    rc = _lib.load().hipfact_debug_ritz_tridiag(k, _ptr(d), _ptr(g) if k > 1 else None, int(which), C.byref(theta), _ptr(s))
+    if rc != 0:
+        raise HipfactError(rc, "hipfact_debug_ritz_tridiag")
+    return theta.value, s[:k]
 
 
 class BorderInfo(C.Structure):
