@@ -888,6 +888,77 @@ int hipfact_tr_solve_lr(hipfact_handle* h, int method, const hipfact_hess_op* op
 int hipfact_hess_lr_apply_device(hipfact_handle* h, const hipfact_hess_op* op, const hipfact_low_rank* lr,
                                  const double* d_x, double* d_y);
 
+/* ---- device-resident trust-region solves, a queued Hessian product ------- */
+
+/* A matrix-free Hessian product that stays on the device: `fn` QUEUES d_y = H_user d_x on `stream` (the handle's
+ * hipStream_t) - a caller's own HIP kernel, an autodiff Hessian-vector product on the same GPU - and returns 0, or
+ * non-zero to end the call.  d_x and d_y are n-vectors in HBM; d_y is a buffer of the handle (allocated on first use,
+ * kept with the plan; HIPFACT_ENOMEM leaves the handle usable) and is fully overwritten; d_x is not to be written.
+ *   queue_only  1: fn only queues work on `stream`; it never waits for the device and never reads device results on the
+ *               host.  Then the device-controlled CG and GLTR phases run whenever they would for an operator without
+ *               `prod` (options "cg_device_loop" / "lz_device_loop", a judged factorisation).  They queue 8 iterations
+ *               (CG_CHUNK) between two looks at their control block and call fn once per queued iteration, WHETHER OR
+ *               NOT the block has stopped: behind a stop the result is not read (as t = J_r x is not), d_x is finite
+ *               and unchanged - the vector of the last product in front of the stop's projection -, and at most 7 such
+ *               calls are made per run (CG cuts its chunks in front of the launch that carries the product, so that the
+ *               bound is 7 there as well and not 8).
+ *               0: the host-driven loops, one synchronisation per iteration as with every other operator they run; fn
+ *               may synchronise.  No vector leaves HBM on either route.
+ * The product of a vector x with H = H_user + sym(hess) + gn_jac' gn_jac + shift I + V diag(coef) V' is: fn(user, stream,
+ * n, x, e) FIRST, then the operator's own stage 1 (t = J_r x, w = V' x), then the row sweep of hipfact_hess_op with one
+ * step in front: the running sum of row i (in the row's lane 0) starts from e_i instead of 0.  Lanes per row by the rule
+ * of hipfact_hess_op; H_user counts zero entries per row, so H_user alone runs one lane per row.  Because fn runs in
+ * front of stage 1 it may itself call, on THIS handle, hipfact_spmat_mult_device, hipfact_hess_op_apply_device and
+ * hipfact_hess_lr_apply_device (they overwrite the handle's t and low-rank sums, which stage 1 fills afterwards) - and
+ * nothing else of the handle.  Such calls are part of the product in flight: they move no counter of the products and
+ * a failure of theirs is fn's to report through its return value.  The handle holds no lock across fn.
+ * Determinism: the same handle state and the same bits from fn give the same bits. */
+typedef int (*hipfact_hess_prod_device_fn)(void* user, void* stream, int n, const double* d_x, double* d_y);
+
+typedef struct hipfact_device_prod
+{
+  hipfact_hess_prod_device_fn fn;
+  void* user;
+  int queue_only; /* 1: fn only queues work, it never waits for the device or reads device results */
+} hipfact_device_prod;
+
+/* hipfact_tr_solve_lr with the gradient read from and the step written to device memory of the caller (n doubles each,
+ * not overlapping), and optionally the queued product above beside the operator.  op, lr and dprod are each nullable;
+ * at least one part of H must be present (op == NULL stands for an operator with nothing in it).
+ * Without dprod: the launches of hipfact_tr_solve_lr and its bits for step, tr_dual and iterations; the upload through
+ * the staging buffer and the download are gone.  The call blocks; d_step is written when it returns HIPFACT_OK.
+ * Everything else is the contract of hipfact_tr_solve_lr: time limit, Rayleigh bounds, tr_dual, the zero step of
+ * Steihaug at the iteration cap, the counted projections with routes (a) and (b), the fall-back to the host loop when the
+ * last unchecked projection fails (fn is then called again from the start).
+ * Refused: everything hipfact_tr_solve_lr refuses, with its codes and in its order (a NULL op only when nothing stands
+ * for it); a host `op->prod`, beside dprod or alone (HIPFACT_EINVAL: that caller uses the host entry points); behind
+ * those HIPFACT_EINVAL for a dprod with a NULL fn, a NULL d_gradient or d_step, and d_step overlapping d_gradient.
+ * A non-zero return of fn ends the call with HIPFACT_EINTERNAL ("device product callback failed") after a wait for the
+ * stream; the handle stays usable and the factorisation stays judged.
+ * Info "dprod_solves": calls with a dprod that passed the checks; "dprod_calls": every invocation of fn.
+ * "hess_op_solves" / "hess_op_products" count as for hipfact_tr_solve_lr (products in front of the stop), so
+ * dprod_calls - products of a call lies in 0 .. 7 on the device-controlled route and is 0 on the host-driven one.
+ * What it costs (scripts/dprod_probe.py, profiles/dprod_probe.txt; the problem of hipfact_tr_solve_op's figures, H_user =
+ * that operator's own apply called back through ctypes, fresh processes): queue_only = 1 runs at the speed of the explicit
+ * operator - 0.118 ms per CG and 0.117 ms per GLTR iteration against 0.120 / 0.116 -, queue_only = 0 at 0.155 / 0.137, and
+ * both far below the 1.99 / 2.02 of the host callback `prod`.  A CG solve that stops in its first iteration pays for the
+ * chunk it has queued on either device-controlled route (0.47 ms against 0.24 ms host-driven), of which the 7 unread
+ * callbacks are 0.02 ms. */
+int hipfact_tr_solve_device(hipfact_handle* h, int method, const hipfact_hess_op* op /* nullable */,
+                            const hipfact_low_rank* lr /* nullable */, const hipfact_device_prod* dprod /* nullable */,
+                            const double* d_gradient, double trust_radius, double rel_tol, int max_iter, double* d_step,
+                            double* tr_dual, int* iterations, hipfact_tr_extra* extra /* nullable */);
+
+/* One product d_y = H d_x on the handle's stream with the operator above, with the bits the loops give it; queued like
+ * hipfact_hess_lr_apply_device (fn may synchronise whatever queue_only says).  Refusals as above. */
+int hipfact_hess_apply_device_ex(hipfact_handle* h, const hipfact_hess_op* op /* nullable */,
+                                 const hipfact_low_rank* lr /* nullable */, const hipfact_device_prod* dprod /* nullable */,
+                                 const double* d_x, double* d_y);
+
+/* Pure host function: sizeof of a struct of this header by name ("hipfact_device_prod", "hipfact_hess_op",
+ * "hipfact_low_rank", "hipfact_tr_extra"), for the mirrors of other languages; 0 for a name it does not know. */
+size_t hipfact_debug_sizeof(const char* name);
+
 /* For callers without a HIP runtime of their own (the shim keeps V of its quasi-Newton term this way): a device copy of
  * `bytes` bytes of a host array on the handle's device, and its release (waits for the handle's stream first - and for that stream only: work
  * queued on another stream that reads the buffer is the caller's to wait for; *d_buf becomes NULL; a NULL *d_buf is

@@ -46,6 +46,7 @@ SYMBOLS = [
     "hipfact_debug_place_rows", "hipfact_debug_place_items", "hipfact_debug_multi_slices", "hipfact_debug_schur_items", "hipfact_debug_refine_cadence", "hipfact_plan_create",
     "hipfact_debug_spmat_row_blocks", "hipfact_debug_spmv_lanes", "hipfact_debug_lr_dots_blocks", "hipfact_debug_qn_terms", "hipfact_device_upload", "hipfact_device_release",
     "hipfact_projected_eig_device", "hipfact_projected_eig", "hipfact_debug_ritz_dense", "hipfact_debug_ritz_tridiag",
+    "hipfact_tr_solve_device", "hipfact_hess_apply_device_ex", "hipfact_debug_sizeof",
     "hipfact_plan_free", "hipfact_plan_error", "hipfact_plan_array", "hipfact_plan_scalar",
 ]
 
@@ -165,6 +166,11 @@ def load() -> C.CDLL:
         lib.hipfact_projected_eig.argtypes = [vp, vp, vp, ci, vp, vp, vp]
         lib.hipfact_debug_ritz_dense.argtypes = [ci, vp, vp, C.c_longlong, ci, ci, vp, vp, vp, vp]
         lib.hipfact_debug_ritz_tridiag.argtypes = [ci, vp, vp, ci, C.POINTER(cd), vp]
+    if hasattr(lib, "hipfact_tr_solve_device"):
+        lib.hipfact_tr_solve_device.argtypes = [vp, ci, vp, vp, vp, vp, cd, cd, ci, vp, C.POINTER(cd), C.POINTER(ci), vp]
+        lib.hipfact_hess_apply_device_ex.argtypes = [vp, vp, vp, vp, vp, vp]
+        lib.hipfact_debug_sizeof.argtypes = [C.c_char_p]
+        lib.hipfact_debug_sizeof.restype = C.c_size_t
     lib.hipfact_lsqr_solve.argtypes = [vp, vp, vp, cd, cd, cd, ci, vp, vp]
     lib.hipfact_tridiag_tr.argtypes = [ci, vp, vp, cd, cd, vp, C.POINTER(cd)]
     lib.hipfact_set_option.argtypes = [vp, C.c_char_p, cd]

@@ -212,8 +212,11 @@ static int cg_dots(hipfact_handle* h, int n, const double* x0, const double* y0,
 #include "krylov_hess_op.inc"
 #include "krylov_device.inc"
 
+// (dev_vecs: gradient and newton_step are device vectors - hipfact_tr_solve_device -; the same launches, with the upload
+// through the staging buffer and the download replaced by copies on the device)
 static int steihaug_impl(hipfact_handle* h, const HessOp& op, const double* gradient, double trust_radius,
-                         double rel_tol, int max_iter, double* newton_step, double* tr_dual, int* iterations) {
+                         double rel_tol, int max_iter, double* newton_step, double* tr_dual, int* iterations,
+                         bool dev_vecs = false) {
   int rc;
   if ((rc = require_factor(h, "hipfact_steihaug_solve"))) return rc;
   if ((rc = tr_args_ok(h, op, gradient, newton_step, trust_radius, "hipfact_steihaug_solve"))) return rc;
@@ -236,9 +239,12 @@ static int steihaug_impl(hipfact_handle* h, const HessOp& op, const double* grad
   double* Bd = d + n;
   double* grad = Bd + n;
   HCHECK(h, hipStreamSynchronize(st));
-  memcpy(h->h_stage.p, gradient, nb);
+  if (!dev_vecs) memcpy(h->h_stage.p, gradient, nb);
   HCHECK(h, hipMemsetAsync(h->d_cg_b.p, 0, (size_t)N * sizeof(double), st));
-  HCHECK(h, hipMemcpyAsync(r, h->h_stage.p, nb, hipMemcpyHostToDevice, st));
+  if (dev_vecs)
+    HCHECK(h, hipMemcpyAsync(r, gradient, nb, hipMemcpyDeviceToDevice, st));
+  else
+    HCHECK(h, hipMemcpyAsync(r, h->h_stage.p, nb, hipMemcpyHostToDevice, st));
   HCHECK(h, hipMemcpyAsync(grad, r, nb, hipMemcpyDeviceToDevice, st));
   HCHECK(h, hipMemsetAsync(z, 0, nb, st));
   const int vb = nblocks(n);
@@ -281,7 +287,7 @@ static int steihaug_impl(hipfact_handle* h, const HessOp& op, const double* grad
       // a projection did not meet the tolerance unchecked: once more from the start with the host in the loop
       h->cg_device_fallbacks++;
       h->cg_device_loop = false;
-      rc = steihaug_impl(h, op, gradient, trust_radius, rel_tol, max_iter, newton_step, tr_dual, iterations);
+      rc = steihaug_impl(h, op, gradient, trust_radius, rel_tol, max_iter, newton_step, tr_dual, iterations, dev_vecs);
       h->cg_device_loop = true;
       return rc;
     }
@@ -353,6 +359,13 @@ static int steihaug_impl(hipfact_handle* h, const HessOp& op, const double* grad
     *tr_dual = comb < 0.0 ? (-comb) / rad_sq : 0.0;
   }
   HCHECK(h, hipGetLastError());
+  if (dev_vecs) {
+    if ((rc = check_info(h, Phase::solve))) return rc;  // synchronises; a timed-out sweep invalidates the step
+    HCHECK(h, hipMemcpyAsync(newton_step, z, nb, hipMemcpyDeviceToDevice, st));
+    HCHECK(h, hipStreamSynchronize(st));
+    if (iterations) *iterations = it;
+    return HIPFACT_OK;
+  }
   HCHECK(h, hipMemcpyAsync(h->h_stage.p, z, nb, hipMemcpyDeviceToHost, st));
   if ((rc = check_info(h, Phase::solve))) return rc;  // synchronises; a timed-out sweep invalidates the step
   memcpy(newton_step, h->h_stage.p, nb);
@@ -418,7 +431,7 @@ static void lanczos_rayleigh(const std::vector<double>& delta, const std::vector
 }
 
 static int gltr_impl(hipfact_handle* h, const HessOp& op, const double* gradient, double trust_radius, double rel_tol,
-                     int max_iter, double* newton_step, double* tr_dual, int* iterations) {
+                     int max_iter, double* newton_step, double* tr_dual, int* iterations, bool dev_vecs = false) {
   int rc;
   if ((rc = require_factor(h, "hipfact_tr_solve"))) return rc;
   if ((rc = tr_args_ok(h, op, gradient, newton_step, trust_radius, "hipfact_tr_solve"))) return rc;
@@ -448,9 +461,12 @@ static int gltr_impl(hipfact_handle* h, const HessOp& op, const double* gradient
   h->tr.ray_min = h->tr.ray_max = 1.0;
   h->tr.timed_out = false;
   if (n == 0) return HIPFACT_OK;
-  memcpy(h->h_stage.p, gradient, nb);
+  if (!dev_vecs) memcpy(h->h_stage.p, gradient, nb);
   HCHECK(h, hipMemsetAsync(h->d_lz_b.p, 0, (size_t)3 * N * sizeof(double), st));  // the tails [.; 0] stay zero
-  HCHECK(h, hipMemcpyAsync(tb[0], h->h_stage.p, nb, hipMemcpyHostToDevice, st));
+  if (dev_vecs)
+    HCHECK(h, hipMemcpyAsync(tb[0], gradient, nb, hipMemcpyDeviceToDevice, st));
+  else
+    HCHECK(h, hipMemcpyAsync(tb[0], h->h_stage.p, nb, hipMemcpyHostToDevice, st));
   std::vector<double> delta, gamma, hvec;
   double dots[3];
   bool cont = false;
@@ -461,8 +477,13 @@ static int gltr_impl(hipfact_handle* h, const HessOp& op, const double* gradient
     if ((rc = finish_solve(h, &cont))) return rc;
   } while (cont);
   const double gamma0 = dots[0] > 0.0 ? sqrt(dots[0]) : 0.0;
-  auto finish_zero = [&]() {
-    memset(newton_step, 0, nb);
+  auto finish_zero = [&]() -> int {
+    if (dev_vecs) {
+      HCHECK(h, hipMemsetAsync(newton_step, 0, nb, st));
+      HCHECK(h, hipStreamSynchronize(st));
+    } else {
+      memset(newton_step, 0, nb);
+    }
     return HIPFACT_OK;
   };
   if (!(gamma0 > 0.0) || !(gamma0 < 1.7e308)) {
@@ -516,7 +537,7 @@ static int gltr_impl(hipfact_handle* h, const HessOp& op, const double* gradient
       // phase has been through the rotating right-hand sides: t_0 is gone)
       h->lz_device_fallbacks++;
       h->lz_device_loop = false;
-      rc = gltr_impl(h, op, gradient, trust_radius, rel_tol, max_iter, newton_step, tr_dual, iterations);
+      rc = gltr_impl(h, op, gradient, trust_radius, rel_tol, max_iter, newton_step, tr_dual, iterations, dev_vecs);
       h->lz_device_loop = true;
       return rc;
     }
@@ -607,9 +628,15 @@ static int gltr_impl(hipfact_handle* h, const HessOp& op, const double* gradient
   hipLaunchKernelGGL(k_combine, dim3(vb), dim3(FB), 0, st, n, dim, Q, h->d_lz_coef.as<double>(), s);
   HCHECK(h, hipGetLastError());
   HCHECK(h, hipStreamSynchronize(st));
-  HCHECK(h, hipMemcpyAsync(h->h_stage.p, s, nb, hipMemcpyDeviceToHost, st));
-  if ((rc = check_info(h, Phase::solve))) return rc;  // synchronises
-  memcpy(newton_step, h->h_stage.p, nb);
+  if (dev_vecs) {
+    if ((rc = check_info(h, Phase::solve))) return rc;  // synchronises
+    HCHECK(h, hipMemcpyAsync(newton_step, s, nb, hipMemcpyDeviceToDevice, st));
+    HCHECK(h, hipStreamSynchronize(st));
+  } else {
+    HCHECK(h, hipMemcpyAsync(h->h_stage.p, s, nb, hipMemcpyDeviceToHost, st));
+    if ((rc = check_info(h, Phase::solve))) return rc;  // synchronises
+    memcpy(newton_step, h->h_stage.p, nb);
+  }
   if (tr_dual) *tr_dual = lambda;
   if (iterations) *iterations = h->tr.timed_out ? dim : std::min(k, dim);
   return HIPFACT_OK;
@@ -618,16 +645,16 @@ static int gltr_impl(hipfact_handle* h, const HessOp& op, const double* gradient
 // hipfact_tr_solve_ex / hipfact_tr_solve_op behind their argument checks
 static int tr_solve_run(hipfact_handle* h, int method, const HessOp& op, const double* gradient, double trust_radius,
                         double rel_tol, int max_iter, double* newton_step, double* tr_dual, int* iterations,
-                        hipfact_tr_extra* extra) {
+                        hipfact_tr_extra* extra, bool dev_vecs = false) {
   int rc;
   h->tr.limit = extra ? extra->time_limit : -1.0;
   h->tr.t0 = std::chrono::steady_clock::now();
   h->tr.timed_out = false;
   h->tr.ray_min = h->tr.ray_max = 1.0;
   if (method == HIPFACT_TR_STEIHAUG)
-    rc = steihaug_impl(h, op, gradient, trust_radius, rel_tol, max_iter, newton_step, tr_dual, iterations);
+    rc = steihaug_impl(h, op, gradient, trust_radius, rel_tol, max_iter, newton_step, tr_dual, iterations, dev_vecs);
   else if (method == HIPFACT_TR_GLTR)
-    rc = gltr_impl(h, op, gradient, trust_radius, rel_tol, max_iter, newton_step, tr_dual, iterations);
+    rc = gltr_impl(h, op, gradient, trust_radius, rel_tol, max_iter, newton_step, tr_dual, iterations, dev_vecs);
   else {
     h->error = "hipfact_tr_solve: unknown method";
     rc = HIPFACT_EINVAL;
@@ -671,23 +698,67 @@ static int tr_solve_op_lr(hipfact_handle* h, const char* who, int method, const 
   return rc;
 }
 
+// (device_entry: hipfact_hess_apply_device_ex, with the queued product `dp` or NULL.  Called from inside a device product
+// callback - dprod_depth > 0 - the call is part of the product in flight: it counts nothing and leaves the flag of the
+// counting call as it is.)
 static int hess_op_lr_apply(hipfact_handle* h, const char* who, const hipfact_hess_op* op_in, const hipfact_low_rank* lr,
-                            const double* d_x, double* d_y) {
+                            const double* d_x, double* d_y, const hipfact_device_prod* dp = nullptr,
+                            bool device_entry = false) {
   if (!h) return HIPFACT_EINVAL;
   HessOp op;
-  int rc = hess_op_from_abi(h, op_in, who, &op, lr);  // (in front of the device: a NULL op touches none)
+  int rc = hess_op_from_abi(h, op_in, who, &op, lr, dp, device_entry);  // (in front of the device: a NULL op touches none)
   if (rc || (rc = enter(h))) return rc;
   if ((rc = require_factor(h, who))) return rc;
   // (n from the factorisation, as in the loops, whose check it shares: the vectors stand in for gradient and step)
   if ((rc = tr_args_ok(h, op, d_x, d_y, 1.0, who))) return rc;
+  if (op.dhave && !op.dfn) {
+    h->error = std::string(who) + ": a device product without a callback";
+    return HIPFACT_EINVAL;
+  }
   if (d_x == d_y) {
     h->error = std::string(who) + ": d_x and d_y overlap";
     return HIPFACT_EINVAL;
   }
   const int n = h->plan.n;
   if (n == 0) return HIPFACT_OK;
-  h->hess_op_call = true;
+  const bool nested = h->dprod_depth > 0;
+  if (!nested) h->hess_op_call = true;
   rc = apply_hess(h, op, n, d_x, d_y);
+  if (!nested) h->hess_op_call = false;
+  return rc;
+}
+
+// hipfact_tr_solve_device: hipfact_tr_solve_lr on device vectors, with the caller's queued product beside the operator
+static int tr_solve_device_impl(hipfact_handle* h, int method, const hipfact_hess_op* op_in, const hipfact_low_rank* lr,
+                                const hipfact_device_prod* dp, const double* d_gradient, double trust_radius,
+                                double rel_tol, int max_iter, double* d_step, double* tr_dual, int* iterations,
+                                hipfact_tr_extra* extra) {
+  const char* who = "hipfact_tr_solve_device";
+  if (!h) return HIPFACT_EINVAL;
+  HessOp op;
+  int rc = hess_op_from_abi(h, op_in, who, &op, lr, dp, true);
+  if (rc || (rc = enter(h))) return rc;
+  ++h->hess_op_solves;
+  // what the loops refuse, here in their order, so that the checks of the device form stand behind it
+  if ((rc = require_factor(h, who))) return rc;
+  if ((rc = tr_args_ok(h, op, d_gradient, d_step, trust_radius, who))) return rc;
+  if (method != HIPFACT_TR_STEIHAUG && method != HIPFACT_TR_GLTR) {
+    h->error = "hipfact_tr_solve: unknown method";
+    return HIPFACT_EINVAL;
+  }
+  if (op.dhave && !op.dfn) {
+    h->error = std::string(who) + ": a device product without a callback";
+    return HIPFACT_EINVAL;
+  }
+  const int n = h->plan.n;
+  const uintptr_t g0 = (uintptr_t)d_gradient, s0 = (uintptr_t)d_step, len = (uintptr_t)n * sizeof(double);
+  if (s0 < g0 + len && g0 < s0 + len) {
+    h->error = std::string(who) + ": d_step overlaps d_gradient";
+    return HIPFACT_EINVAL;
+  }
+  if (op.dhave) ++h->dprod_solves;
+  h->hess_op_call = true;
+  rc = tr_solve_run(h, method, op, d_gradient, trust_radius, rel_tol, max_iter, d_step, tr_dual, iterations, extra, true);
   h->hess_op_call = false;
   return rc;
 }
@@ -711,6 +782,27 @@ int hipfact_hess_op_apply_device(hipfact_handle* h, const hipfact_hess_op* op_in
 int hipfact_hess_lr_apply_device(hipfact_handle* h, const hipfact_hess_op* op_in, const hipfact_low_rank* lr,
                                  const double* d_x, double* d_y) {
   return hess_op_lr_apply(h, "hipfact_hess_lr_apply_device", op_in, lr, d_x, d_y);
+}
+
+int hipfact_tr_solve_device(hipfact_handle* h, int method, const hipfact_hess_op* op_in, const hipfact_low_rank* lr,
+                            const hipfact_device_prod* dprod, const double* d_gradient, double trust_radius,
+                            double rel_tol, int max_iter, double* d_step, double* tr_dual, int* iterations,
+                            hipfact_tr_extra* extra) {
+  return tr_solve_device_impl(h, method, op_in, lr, dprod, d_gradient, trust_radius, rel_tol, max_iter, d_step, tr_dual,
+                              iterations, extra);
+}
+int hipfact_hess_apply_device_ex(hipfact_handle* h, const hipfact_hess_op* op_in, const hipfact_low_rank* lr,
+                                 const hipfact_device_prod* dprod, const double* d_x, double* d_y) {
+  return hess_op_lr_apply(h, "hipfact_hess_apply_device_ex", op_in, lr, d_x, d_y, dprod, true);
+}
+// sizeof of a struct of the ABI by name, for the mirrors of other languages (0: not a name it knows)
+size_t hipfact_debug_sizeof(const char* name) {
+  if (!name) return 0;
+  if (!strcmp(name, "hipfact_device_prod")) return sizeof(hipfact_device_prod);
+  if (!strcmp(name, "hipfact_hess_op")) return sizeof(hipfact_hess_op);
+  if (!strcmp(name, "hipfact_low_rank")) return sizeof(hipfact_low_rank);
+  if (!strcmp(name, "hipfact_tr_extra")) return sizeof(hipfact_tr_extra);
+  return 0;
 }
 
 // a device copy of a host array for callers without a HIP runtime of their own (the shim's V), and its release

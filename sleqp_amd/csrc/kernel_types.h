@@ -124,7 +124,8 @@ struct XupdIn {
 // The rows of stage 2 of a product with the Hessian operator H = sym(H0) + J_r^T J_r + shift I (krylov_hess_op.inc):
 // the lower triangle of H0 by rows (hp, hi, hv) and by columns (hp2, hi2, hv2), null without H0; J_r^T by rows (jp, ji,
 // jv: the column arrays of J_r) against t = J_r x, null without J_r; the low-rank term V diag(coef) V^T as lv (column-major,
-// leading dimension lld), lrank columns and lu[k] = coef_k (V_k . x), null / 0 without a term
+// leading dimension lld), lrank columns and lu[k] = coef_k (V_k . x), null / 0 without a term; e = H_user x, the product the
+// caller queued in front of stage 1 (hipfact_device_prod), null without one
 constexpr int LR_MAX_RANK = 32;  // most columns of the low-rank term
 constexpr int LR_BLOCKS = 256;   // most blocks (= partial sums per column) of k_lr_dots
 struct LrCoef {
@@ -146,6 +147,7 @@ struct HessRows {
   const double* __restrict__ lu;
   int lrank;
   long long lld;
+  const double* __restrict__ e;
 };
 struct CgCtl {
   double rg, z_nrm_sq, rel_tol_sq, rad_sq, alpha, beta, tau;

@@ -436,7 +436,7 @@ static int lz_device_phase(hipfact_handle* h, const HessOp& op, int n, double ga
                            std::vector<double>& gamma, int* k_done, bool* used, bool* touched) {
   *used = false;
   *touched = false;
-  if (!h->lz_device_loop || op.prod || kmax < 2 || !unchecked_solves_ok(h)) return HIPFACT_OK;
+  if (!h->lz_device_loop || op.host_driven() || kmax < 2 || !unchecked_solves_ok(h)) return HIPFACT_OK;
   hipStream_t st = h->stream;
   *touched = true;
   const int vb = nblocks(n);
@@ -533,8 +533,14 @@ static int lz_device_phase(hipfact_handle* h, const HessOp& op, int n, double ga
 // One chunk of CG_CHUNK iterations: three launches per iteration - tests + z, r | projection (tree, x update and the
 // partials of r.g in one launch) | beta, d, B d and the next iteration's partials.  The control block ping-pongs
 // between c[0] and c[1] (a launch never writes the block its own workgroups read).
+// With a queued product of the caller's (HessOp::dhave) the chunk is cut in front of the head instead of behind it
+// (head_first: the head of the previous chunk's last iteration leads, none trails): the head is where the caller's
+// callback is called, stop or not, and a chunk cut behind its last head would call it CG_CHUNK times for nothing when
+// the first test of the chunk stops the loop.  Cut in front, at most CG_CHUNK - 1 heads stand behind a stop.  The
+// launches and their order on the stream are the same; the block the host reads is then c[1].
 static int cg_chunk_enqueue(hipfact_handle* h, const HessOp& op, int n, CgCtl* c, double* r, const double* g,
-                            double* z, double* d, double* Bd, const double* grad, int iterations = CG_CHUNK) {
+                            double* z, double* d, double* Bd, const double* grad, int iterations, bool head_first,
+                            bool head_last, DotPartials* rg_io) {
   hipStream_t st = h->stream;
   const int vb = nblocks(n);
   double* part = h->d_cg_dots.as<double>();
@@ -545,15 +551,22 @@ static int cg_chunk_enqueue(hipfact_handle* h, const HessOp& op, int n, CgCtl* c
   const int L = hess_op_lanes(op, n);
   const int nblk = row_blocks(n, L, CG_BLOCKS);
   int rc;
+  DotPartials rg = *rg_io;  // (in: of the projection in front of a leading head; out: of the chunk's last one)
+  auto head = [&]() -> int {
+    if (op.plain()) {
+      launch_cg_head(st, L, n, c + 1, c, part2, rg.blocks, rg.stride, op.hess, g, d, Bd, z, grad, part);
+      return HIPFACT_OK;
+    }
+    return launch_cg_head_op(h, op, L, n, c + 1, c, part2, rg.blocks, rg.stride, g, d, Bd, z, grad, part);
+  };
   for (int k = 0; k < iterations; ++k) {
+    if ((k > 0 || head_first) && (rc = head())) return rc;
     hipLaunchKernelGGL(k_cg_step_update1, dim3(std::min(vb, 128)), dim3(FB), 0, st, n, c, c + 1, part, nblk, d, Bd, z, r,
                        h->cg_residual_update ? g : nullptr);
-    const DotPartials rg = project_with_dot(h, n, h->d_cg_b.as<double>(), &c[1].stop, part2);  // g = P[r], and r.g
-    if (op.plain())
-      launch_cg_head(st, L, n, c + 1, c, part2, rg.blocks, rg.stride, op.hess, g, d, Bd, z, grad, part);
-    else if ((rc = launch_cg_head_op(h, op, L, n, c + 1, c, part2, rg.blocks, rg.stride, g, d, Bd, z, grad, part)))
-      return rc;
+    rg = project_with_dot(h, n, h->d_cg_b.as<double>(), &c[1].stop, part2);  // g = P[r], and r.g
   }
+  if (iterations > 0 && head_last && (rc = head())) return rc;
+  *rg_io = rg;
   HCHECK(h, hipGetLastError());
   return HIPFACT_OK;
 }
@@ -565,7 +578,7 @@ static int steihaug_device_loop(hipfact_handle* h, const HessOp& op, int n, doub
                                 double* Bd, const double* grad, bool* used, bool* touched, int* state_out, int* it_out) {
   *used = false;
   *touched = false;
-  if (!h->cg_device_loop || op.prod || !unchecked_solves_ok(h)) return HIPFACT_OK;
+  if (!h->cg_device_loop || op.host_driven() || !unchecked_solves_ok(h)) return HIPFACT_OK;
   hipStream_t st = h->stream;
   *touched = true;
   HCHECK(h, h->d_cg_ctl.ensure(2 * sizeof(CgCtl)));
@@ -593,12 +606,16 @@ static int steihaug_device_loop(hipfact_handle* h, const HessOp& op, int n, doub
       return rc;
   }
   const int budget = (max_iter == -1) ? (1 << 20) : max_iter + 1;
+  // (a queued product of the caller's: chunks cut in front of the head, the host reads the block the tests wrote)
+  const bool cut_at_head = op.dhave;
+  DotPartials rg = {0, 1};
   for (int done = 0; done < budget; done += CG_CHUNK) {
     // (direct launches - a captured graph of a chunk measured slower -, no more iterations than the cap allows: the last
     // one only takes the cap's exit)
-    rc = cg_chunk_enqueue(h, op, n, c, r, g, z, d, Bd, grad, std::min(CG_CHUNK, budget - done));
+    rc = cg_chunk_enqueue(h, op, n, c, r, g, z, d, Bd, grad, std::min(CG_CHUNK, budget - done), cut_at_head && done > 0,
+                          !cut_at_head, &rg);
     if (rc) return rc;
-    HCHECK(h, hipMemcpyAsync(h->h_cg_ctl.p, h->d_cg_ctl.p, sizeof(CgCtl), hipMemcpyDeviceToHost, st));
+    HCHECK(h, hipMemcpyAsync(h->h_cg_ctl.p, cut_at_head ? c + 1 : c, sizeof(CgCtl), hipMemcpyDeviceToHost, st));
     HCHECK(h, hipStreamSynchronize(st));
     memcpy(&host, h->h_cg_ctl.p, sizeof(host));
     if (host.stop) break;

@@ -10,6 +10,8 @@
 //             It writes nothing but t, so the device loops queue it unconditionally - also behind a `stop`.
 //   stage 2   per row i of n, with LANES lanes (spmv_lanes of the stage's entries per row, (2 nnz(H0) + nnz(J_r)) / n),
 //             ONE running sum per lane, in this order (hess_op_row below - every kernel here calls it, none restates it):
+//               0. the sum of the row's lane 0 starts from e_i = (H_user x)_i instead of 0, if the caller's queued product
+//                  is present (below),
 //               1. the lane's share of row i of the lower triangle of H0, then of column i without the diagonal - what
 //                  k_cg_spmv_dots walks, in its order -, if H0 is present,
 //               2. onto it the lane's share of row i of J_r^T (the cp / ri / val arrays of the matrix) against t,
@@ -25,6 +27,13 @@
 //             u_k = coef_k w_k (k_lr_totals: ONE workgroup sums the partials with block_totals, in index order, and
 //             leaves u in the handle's buffer behind them).  Like t = J_r x both write nothing but those buffers of the
 //             handle and are queued unconditionally.
+// A queued product of the caller's (hipfact_device_prod: a HIP kernel of its own, an autodiff Hessian-vector product on
+// the same GPU) adds IN FRONT of stage 1
+//   stage 0   e = H_user x: the callback queues it on the handle's stream into an n-vector of the handle (hess_op_dprod).
+//             In front, because a callback may form its product with this handle's own products, which write t and the
+//             low-rank sums: stage 1 then fills them for stage 2 afterwards.  With queue_only set the device loops call it
+//             wherever they queue stage 1 - also behind a `stop`, where x is the unchanged result of the last projection
+//             that ran and e is not read.
 // The same handle state gives the same bits on every call, and the host-driven loops (apply_hess), the device-controlled
 // loops and hipfact_hess_op_apply_device form the product of one vector with the same bits: same stage 1, same row
 // function, same lane count.  An operator that is an explicit Hessian and nothing else does not come here: it runs the
@@ -35,7 +44,7 @@ namespace hipfact {
 // row `row` of H x from the lane `sub` of its LANES lanes; valid in the row's lane 0
 template <int LANES>
 __device__ __forceinline__ double hess_op_row(const HessRows& o, int row, int sub, const double* __restrict__ x) {
-  double s = 0.0;
+  double s = (o.e && sub == 0) ? o.e[row] : 0.0;
   if (o.hp) {
     s = csr_row_add<LANES>(s, row, sub, o.hp, o.hi, o.hv, x);
     s = csr_offdiag_add<LANES>(s, row, sub, o.hp2, o.hi2, o.hv2, x);
@@ -191,8 +200,16 @@ struct HessOp {
   long long lld = 0;
   int lrank = 0;
   LrCoef lcoef = {};
+  // the caller's queued product (hipfact_device_prod; dhave false: none): dfn queues e = H_user x on the handle's stream,
+  // dqueue: it does nothing else, so the device-controlled loops may call it
+  bool dhave = false;
+  hipfact_hess_prod_device_fn dfn = nullptr;
+  void* duser = nullptr;
+  bool dqueue = false;
   // an explicit Hessian and nothing else: the kernels of krylov_device.inc and the symmetric product of the matrix
-  bool plain() const { return hess && !gn_jac && shift == 0.0 && !prod && lrank == 0; }
+  bool plain() const { return hess && !gn_jac && shift == 0.0 && !prod && lrank == 0 && !dhave; }
+  // a product that needs the host in every iteration: the device-controlled loops stay out
+  bool host_driven() const { return prod || (dhave && !dqueue); }
 };
 
 // lanes per row of the products with the symmetric Hessian (both triangles from lower storage)
@@ -206,13 +223,18 @@ static int hess_op_lanes(const HessOp& op, int n) {
 static int lr_blocks(long long n) { return (int)std::max(1LL, std::min<long long>(LR_BLOCKS, (n + FB - 1) / FB)); }
 
 // The caller's hipfact_hess_op as a HessOp, or HIPFACT_EINVAL (what needs n is left to tr_args_ok)
+// (dp: the queued product of the device entry points beside it - there `in` may be NULL when dp or the term stands for
+// the operator, and a host `prod` is refused behind everything else: that caller uses the host entry points)
 static int hess_op_from_abi(hipfact_handle* h, const hipfact_hess_op* in, const char* who, HessOp* op,
-                            const hipfact_low_rank* lr = nullptr) {
+                            const hipfact_low_rank* lr = nullptr, const hipfact_device_prod* dp = nullptr,
+                            bool device_entry = false) {
   const char* bad = nullptr;
   const bool term = lr && lr->rank != 0;
+  static const hipfact_hess_op nothing = {nullptr, nullptr, 0.0, nullptr, nullptr};
+  if (!in && device_entry && (dp || term)) in = &nothing;
   if (!in)
     bad = "no operator";
-  else if (!in->hess && !in->gn_jac && in->shift == 0.0 && !in->prod && !term)
+  else if (!in->hess && !in->gn_jac && in->shift == 0.0 && !in->prod && !term && !dp)
     bad = "an operator with nothing in it";
   else if (!std::isfinite(in->shift))
     bad = "non-finite shift";
@@ -231,6 +253,8 @@ static int hess_op_from_abi(hipfact_handle* h, const hipfact_hess_op* in, const 
       for (int k = 0; k < lr->rank; ++k)
         if (!std::isfinite(lr->coef[k])) bad = "non-finite coefficient of the low-rank term";
   }
+  if (!bad && device_entry && in->prod)
+    bad = dp ? "a host product callback beside a device product" : "a host product callback: use the host entry points";
   if (bad) {
     h->error = std::string(who) + ": " + bad;
     return HIPFACT_EINVAL;
@@ -242,6 +266,38 @@ static int hess_op_from_abi(hipfact_handle* h, const hipfact_hess_op* in, const 
     op->lrank = lr->rank;
     for (int k = 0; k < lr->rank; ++k) op->lcoef.c[k] = lr->coef[k];
   }
+  if (dp) {
+    op->dhave = true;
+    op->dfn = dp->fn;
+    op->duser = dp->user;
+    op->dqueue = dp->queue_only != 0;
+  }
+  return HIPFACT_OK;
+}
+
+// The caller's queued product of x, e = H_user x in the handle's n-vector for it (allocated on first use, kept with the
+// plan; HIPFACT_ENOMEM leaves the handle usable).  The callback may call the products of this handle (hipfact_spmat_mult_device,
+// hipfact_hess_op_apply_device, hipfact_hess_lr_apply_device): they see dprod_depth > 0, leave the flag of the counting call
+// alone and count nothing - their launches are part of THIS product.  A non-zero return ends the call, behind a wait for
+// what has been queued.
+static int hess_op_dprod(hipfact_handle* h, const HessOp& op, int n, const double* x, const double** e) {
+  if (h->d_hess_e.ensure(std::max<size_t>((size_t)n * sizeof(double), 16)) != hipSuccess) {
+    (void)hipGetLastError();
+    h->error = "Hessian operator: out of device memory for the vector of the device product";
+    return HIPFACT_ENOMEM;
+  }
+  double* out = h->d_hess_e.as<double>();
+  ++h->dprod_calls;
+  ++h->dprod_depth;
+  const int ret = op.dfn(op.duser, (void*)h->stream, n, x, out);
+  --h->dprod_depth;
+  if (ret != 0) {
+    (void)hipSetDevice(h->device);
+    (void)hipStreamSynchronize(h->stream);
+    h->error = "device product callback failed";
+    return HIPFACT_EINTERNAL;
+  }
+  *e = out;
   return HIPFACT_OK;
 }
 
@@ -267,6 +323,14 @@ static int hess_op_jx(hipfact_handle* h, hipfact_spmat* J, const double* x, doub
 static int hess_op_stage1(hipfact_handle* h, const HessOp& op, int n, const double* x, HessRows* R) {
   memset(R, 0, sizeof(*R));
   R->shift = op.shift;
+  // (the caller's product FIRST: a callback that forms it with this handle's own products writes t and the low-rank sums,
+  // and must be through with them before the operator's stage 1 fills them for stage 2)
+  if (op.dhave) {
+    const double* e = nullptr;
+    int rc_e;
+    if ((rc_e = hess_op_dprod(h, op, n, x, &e))) return rc_e;
+    R->e = e;
+  }
   if (op.hess) {
     hipfact_spmat* M = op.hess;
     R->hp = M->tp.as<int>(), R->hi = M->ti.as<int>(), R->hv = M->tval.as<double>();
@@ -313,7 +377,7 @@ static int hess_op_stage1(hipfact_handle* h, const HessOp& op, int n, const doub
 // `products` more products under a call that counts them (info "hess_op_products"; with a term also "hess_lr_products",
 // and "hess_lr_rank" is the rank of the last one)
 static void hess_op_count(hipfact_handle* h, const HessOp& op, long products) {
-  if (!h->hess_op_call) return;
+  if (!h->hess_op_call || h->dprod_depth > 0) return;  // (inside a device product callback: part of the product in flight)
   h->hess_op_products += products;
   if (op.lrank > 0 && products > 0) {
     h->hess_lr_products += products;
@@ -353,7 +417,7 @@ static int tr_args_ok(hipfact_handle* h, const HessOp& op, const double* gradien
                       double trust_radius, const char* who) {
   const Plan& P = h->plan;
   const int n = P.saddle ? P.n : 0;
-  bool hess_ok = op.hess || op.gn_jac || op.shift != 0.0 || op.prod != nullptr || op.lrank > 0;
+  bool hess_ok = op.hess || op.gn_jac || op.shift != 0.0 || op.prod != nullptr || op.lrank > 0 || op.dhave;
   if (op.hess) hess_ok = hess_ok && op.hess->h == h && op.hess->rows == n && op.hess->cols == n;
   if (op.gn_jac) hess_ok = hess_ok && op.gn_jac->h == h && op.gn_jac->cols == n;
   if (!P.saddle || !hess_ok || !gradient || !newton_step || !(trust_radius > 0.0)) {

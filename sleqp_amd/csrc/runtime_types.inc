@@ -487,6 +487,12 @@ struct hipfact_handle : PlanState, SingleSolveMemo {
   int hess_lr_rank = 0;
   long hess_op_solves = 0, hess_op_products = 0;
   bool hess_op_call = false;
+  // ... e = H_user x of the caller's queued product (hipfact_device_prod), n doubles, allocated on first use; calls of
+  // hipfact_tr_solve_device with one that passed the checks, invocations of the callback, and how deep the handle is
+  // inside one (the products a callback calls count nothing and leave hess_op_call alone)
+  DevBuf d_hess_e;
+  long dprod_solves = 0, dprod_calls = 0;
+  int dprod_depth = 0;
   // the trust-region solve in progress (hipfact_tr_solve_ex): the caller's time limit (tr/tr_types.h:9-16: seconds,
   // < 0 = SLEQP_NONE) against a clock started at the entry point, whether it ended the iteration, and the Rayleigh
   // quotients the loop has seen (tr/tr_types.h:18-20)

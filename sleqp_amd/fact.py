@@ -611,6 +611,82 @@ class HipFact:
             return out[:n].copy(), out[n:].copy(), (after, cols)
         return out[:n].copy()
 
+    def _device_prod(self, dprod, queue_only):
+        """hipfact_device_prod from a callable (stream_ptr, n, d_x_ptr, d_y_ptr) -> int that queues d_y = H_user d_x on
+        the stream; returns (struct or None, keepalive)."""
+        if dprod is None:
+            return None, None
+
+        def _fn(_user, stream, n, d_x, d_y):
+            try:
+                return int(dprod(stream or 0, n, d_x or 0, d_y or 0))
+            except Exception:  # noqa: BLE001
+                return -1
+
+        cb = DEVICE_PROD(_fn)
+        return DeviceProdStruct(cb, None, 1 if queue_only else 0), cb
+
+    def _device_call(self, call, dprod, queue_only, hess, gn_jac, shift, V, coef, ld, n):
+        """Runs call(op_ref, lr_ref, dprod_ref) with the operator's parts as the device entry points take them; V is
+        uploaded for the call and the callback wrapper is kept alive until it returns."""
+        if hess is not None and not isinstance(hess, SpMat):
+            raise TypeError("a host product callback belongs to tr_solve_op; the device entry points take `dprod`")
+        op, _ = self._hess_op(hess, gn_jac, shift, n)
+        dp, keep = self._device_prod(dprod, queue_only)
+        hip = C.CDLL("libamdhip64.so")
+        buf = C.c_void_p()
+        lr_ref = None
+        try:
+            if V is not None:
+                cols, coef, rank, ld = self._low_rank(V, coef, ld, n, 0.0)
+                if hip.hipMalloc(C.byref(buf), C.c_size_t(max(cols.nbytes, 16))) != 0:
+                    raise MemoryError("hipMalloc")
+                if cols.nbytes and hip.hipMemcpy(buf, _ptr(cols), C.c_size_t(cols.nbytes), 1) != 0:
+                    raise RuntimeError("hipMemcpy")
+                lr = LowRankStruct(rank, ld, buf.value, coef.ctypes.data_as(C.c_void_p))
+                lr_ref = C.byref(lr)
+            self._check(call(C.byref(op), lr_ref, C.byref(dp) if dp is not None else None))
+        finally:
+            if buf:
+                self._lib.hipfact_synchronize(self._h)  # (a queued product may still read V)
+                hip.hipFree(buf)
+            del keep
+
+    def tr_solve_device(self, d_gradient_ptr: int, trust_radius: float, d_step_ptr: int, dprod=None,
+                        queue_only: bool = True, hess=None, gn_jac=None, shift: float = 0.0, V=None, coef=None, ld=None,
+                        method: int = 0, stat_tol: float = 1e-6, max_iter: int = 100, extra=None):
+        """hipfact_tr_solve_device: tr_solve_lr with the gradient read from and the step written to device memory (n
+        doubles each), and optionally a matrix-free product that stays on the device beside the operator:
+        H = dprod + sym(hess) + gn_jac' gn_jac + shift I + V diag(coef) V'.  `dprod` is a callable (stream_ptr, n, d_x_ptr,
+        d_y_ptr) -> int that QUEUES d_y = H_user d_x on the stream (0: fine); queue_only=True promises that it does
+        nothing else, which lets the device-controlled loops call it.  `extra`: a dict whose "time_limit" is read
+        (seconds, absent or < 0: none) and which receives timed_out, min_rayleigh, max_rayleigh - as `self.last_tr`
+        does.  Returns (tr_dual, iterations)."""
+        n = int(self.info("n"))
+        dual, its = C.c_double(), C.c_int()
+        ex = TrExtra(float(extra.get("time_limit", -1.0)) if extra else -1.0, 0, 1.0, 1.0)
+        self._device_call(
+            lambda op, lr, dp: self._lib.hipfact_tr_solve_device(
+                self._h, int(method), op, lr, dp, C.c_void_p(d_gradient_ptr or None), float(trust_radius),
+                stat_tol * 1e-2, int(max_iter), C.c_void_p(d_step_ptr or None), C.byref(dual), C.byref(its),
+                C.byref(ex)),
+            dprod, queue_only, hess, gn_jac, shift, V, coef, ld, n)
+        self.last_tr = {"timed_out": bool(ex.timed_out), "min_rayleigh": ex.min_rayleigh,
+                        "max_rayleigh": ex.max_rayleigh}
+        if extra is not None:
+            extra.update(self.last_tr)
+        return dual.value, its.value
+
+    def hess_apply_device_ex(self, d_x_ptr: int, d_y_ptr: int, dprod=None, queue_only: bool = True, hess=None,
+                             gn_jac=None, shift: float = 0.0, V=None, coef=None, ld=None):
+        """hipfact_hess_apply_device_ex: d_y = H d_x for device vectors of n doubles, H as in tr_solve_device, queued on
+        the handle's stream (synchronize() before the result is read on another stream)."""
+        n = int(self.info("n"))
+        self._device_call(
+            lambda op, lr, dp: self._lib.hipfact_hess_apply_device_ex(
+                self._h, op, lr, dp, C.c_void_p(d_x_ptr or None), C.c_void_p(d_y_ptr or None)),
+            dprod, queue_only, hess, gn_jac, shift, V, coef, ld, n)
+
     def projected_eig(self, which: int = -1, hess=None, gn_jac=None, shift: float = 0.0, V=None, coef=None, ld=None,
                       prod=None, start=None, want_vec: bool = True, rel_tol: float = 0.0, basis: int = 0,
                       max_restarts: int = -1, time_limit: float = -1.0, device=None):
@@ -1001,6 +1077,14 @@ class HessOpStruct(C.Structure):
 class LowRankStruct(C.Structure):
     """hipfact_low_rank (include/hipfact.h)"""
     _fields_ = [("rank", C.c_int), ("ld", C.c_longlong), ("d_V", C.c_void_p), ("coef", C.c_void_p)]
+
+
+DEVICE_PROD = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p)
+
+
+class DeviceProdStruct(C.Structure):
+    """hipfact_device_prod (include/hipfact.h)"""
+    _fields_ = [("fn", DEVICE_PROD), ("user", C.c_void_p), ("queue_only", C.c_int)]
 
 
 QN_SR1, QN_BFGS, QN_DAMPED_BFGS = 0, 1, 2
