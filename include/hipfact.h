@@ -977,6 +977,86 @@ int hipfact_debug_lr_dots_blocks(long long n);
 int hipfact_debug_qn_terms(int kind, int n, int npairs, int memory, const double* S, const double* Y, double* scale,
                            double* V, double* coef, int* rank, unsigned* damped);
 
+/* ---- block-diagonal quasi-Newton term --------------------------------------- */
+
+/* The reference's quasi-Newton matrices are block-diagonal over the Hessian structure of the function
+ * (sleqp_hess_struct_push_block; quasi_newton/bfgs.c, sr1.c: one ring of pairs and one initial scale per block, the
+ * trailing linear range without curvature).  That shape beside the operator:
+ *   H = H_user + sym(hess) + gn_jac' gn_jac + shift I + blockdiag_b(scale_b I + V_b diag(c_b) V_b')  (+) 0_lin.
+ * The term is an object of the handle, like hipfact_spmat: the structure is fixed for a problem, the values change once
+ * per SQP iteration, solves take a pointer.
+ * _create: block b covers rows [block_end[b-1], block_end[b]) (block_end[-1] = 0), strictly ascending,
+ * block_end[nblocks-1] <= n; rows behind the last end are the linear range: the term adds nothing there.
+ * 1 <= nblocks <= n.  A new term is scale_b = 1, rank 0 in every block (the reference's block without pairs).
+ * _set: rank: columns of V, 0 .. 32; block_rank[b] in 0 .. rank; scale[b] finite; coef[b * rank + k] finite for
+ * k < block_rank[b] (the others are not read); d_V: device, column-major n x rank, ld >= n, caller-owned, read by the calls
+ * until the next _set / _free; column k of block b lives in rows [begin_b, end_b) of column k.  Rows of column k in a
+ * block with block_rank[b] <= k, and rows of the linear range, are NEVER read.  Host arrays are copied: they are the
+ * caller's again when the call returns.  The upload is ordered behind the products already queued on the handle's
+ * stream, and the call waits for it.
+ * _free: the lifetime rules of hipfact_spmat_free (it waits for the handle's stream; the term holds a reference to its
+ * handle).
+ * Both validate their own arguments - non-ascending ends, an end above n, a rank outside 0 .. 32, block_rank[b] > rank,
+ * non-finite scale / coef, ld < n, a NULL d_V with rank > 0: HIPFACT_EINVAL with a message in hipfact_last_error.
+ * HIPFACT_ENOMEM leaves the handle and the term (with its old values) usable.
+ *
+ * A product gains stage 1b' behind the dense term's sums: u[b][k] = c_bk (V_bk . x_b), a segmented multi-column dot in ONE
+ * launch over a work list that follows from block_end alone (hipfact_debug_block_items: a block of at most BT_SHORT rows
+ * is summed by one thread, one of at most BT_WAVE rows by one wave, a longer one in segments of BT_SEG rows by a
+ * workgroup each, added up by a second launch that is queued only when there is such a block), and two steps of the row
+ * sweep: after the dense term's columns, lane `sub` of a row of block b adds V_ik u_bk for k = sub, sub + lanes, ... <
+ * block_rank[b], fused; after the shuffle tree, fma(scale_b, x_i, .).  The lanes per row count `rank` more entries per
+ * row.  The summation order of every sum is a function of block_end and the rank ceiling (8 / 16 / 32) alone: the
+ * determinism contract of hipfact_hess_op holds, and the host-driven loops, the device-controlled loops and
+ * hipfact_hess_apply_device_blocks form the product of one vector with the same bits.
+ *
+ * hipfact_tr_solve_device_blocks is hipfact_tr_solve_device with the block term in the place of `lr`, and
+ * hipfact_tr_solve_blocks the same call with the two host copies; everything else - time limit, Rayleigh bounds, tr_dual,
+ * Steihaug's zero step at the cap, the counted projections, the fall-back to the host loop, the device-controlled phases
+ * and queue_only - carries over.  T alone is a valid operator (op == NULL).  hipfact_hess_apply_device_blocks queues one
+ * product; it is NOT one of the calls a device product callback may make.
+ * Refused: everything hipfact_tr_solve_device refuses, with its codes and in its order (a host `op->prod` in the host form
+ * stands alone as ever); behind the checks of the operator HIPFACT_EINVAL for a T of another handle, a host `op->prod`
+ * beside T and a NULL T; behind HIPFACT_ESTATE before a factorisation, HIPFACT_EINVAL for a T whose n is not the plan's n.
+ * Info "hess_blk_products": products formed with a block term (counted where "hess_lr_products" is);
+ * "hess_blk_blocks": the nblocks of the last one.  "hess_op_solves" / "hess_op_products" count as for
+ * hipfact_tr_solve_lr.  Not built: hipfact_projected_eig* and hipfact_lsqr_solve with a block term. */
+typedef struct hipfact_block_term hipfact_block_term;
+int hipfact_block_term_create(hipfact_handle* h, int n, int nblocks, const int* block_end, hipfact_block_term** out);
+int hipfact_block_term_set(hipfact_block_term* T, int rank, const int* block_rank, const double* scale,
+                           const double* coef, const double* d_V, long long ld);
+int hipfact_block_term_free(hipfact_block_term** T);
+
+int hipfact_tr_solve_blocks(hipfact_handle* h, int method, const hipfact_hess_op* op /* nullable */,
+                            const hipfact_block_term* T, const double* gradient, double trust_radius, double rel_tol,
+                            int max_iter, double* newton_step, double* tr_dual, int* iterations,
+                            hipfact_tr_extra* extra /* nullable */);
+int hipfact_tr_solve_device_blocks(hipfact_handle* h, int method, const hipfact_hess_op* op /* nullable */,
+                                   const hipfact_block_term* T, const hipfact_device_prod* dprod /* nullable */,
+                                   const double* d_gradient, double trust_radius, double rel_tol, int max_iter,
+                                   double* d_step, double* tr_dual, int* iterations, hipfact_tr_extra* extra /* nullable */);
+int hipfact_hess_apply_device_blocks(hipfact_handle* h, const hipfact_hess_op* op /* nullable */,
+                                     const hipfact_block_term* T, const hipfact_device_prod* dprod /* nullable */,
+                                     const double* d_x, double* d_y);
+
+/* Pure host functions (no GPU needed).  The work list of the dot kernel for a structure: per item (class 0 short /
+ * 1 wave / 2 long, block, first row, rows) in items[4 q ..], at most `cap` items are written; row_blk (n ints, nullable):
+ * the block of every row, -1 in the linear range; constants (3 ints, nullable): BT_SHORT, BT_WAVE, BT_SEG (8, 256, 512:
+ * EXPERIMENTS.md, "Block term"; they are part of the summation order).  Returns the number of items, or HIPFACT_EINVAL for a structure _create refuses.
+ * hipfact_debug_block_values: the checks hipfact_block_term_set makes on its values (have_V: a d_V was given), HIPFACT_OK
+ * or HIPFACT_EINVAL with the message in hipfact_last_error(NULL) - where hipfact_block_term_create and _set leave theirs
+ * when they are called without a handle / a term.
+ * And hipfact_qn_block_terms of qn_terms.h on host arrays with leading dimension max(n, 1): hipfact_debug_qn_terms per
+ * block on the row slices, block b with its own npairs[b] pairs in the columns 0 .. npairs[b] - 1 of its rows; coef has
+ * the stride (kind == 0 ? 1 : 2) * memory, V that many columns. */
+int hipfact_debug_block_items(int n, int nblocks, const int* block_end, int* items, int cap, int* row_blk,
+                              int* constants);
+int hipfact_debug_block_values(int n, int nblocks, int rank, const int* block_rank, const double* scale,
+                               const double* coef, int have_V, long long ld);
+int hipfact_debug_qn_block_terms(int kind, int n, int nblocks, const int* block_end, const int* npairs, int memory,
+                                 const double* S, const double* Y, double* scale, double* V, double* coef,
+                                 int* block_rank);
+
 /* ---- extreme eigenpairs of the projected Hessian (Lanczos) ---------------- */
 
 /* The extreme eigenpair of the reduced Hessian Z' H Z on the null space of the working set, Z an orthonormal basis of

@@ -121,4 +121,45 @@ static inline int hipfact_qn_terms(int kind, int n, int npairs, int memory, cons
   return 0;
 }
 
+/* The reference's quasi-Newton matrices are block-diagonal over the Hessian structure of the function
+ * (quasi_newton/bfgs.c, sr1.c: one ring of pairs and one initial scale per block, a block whose slice of the step is
+ * zero skips the push, a block without pairs is the identity, the trailing linear range has no curvature):
+ *   B = blockdiag_b(scale_b I + V_b diag(coef_b) V_b^T)  (+) 0 on the rows behind the last block end.
+ * hipfact_qn_block_terms is hipfact_qn_terms on the row slices: block b covers the rows [block_end[b-1], block_end[b])
+ * (block_end[-1] = 0; strictly ascending, the last one <= n) and owns npairs[b] pairs, oldest first, in the columns
+ * 0 .. npairs[b] - 1 of ITS ROWS of S and Y (n x max_b npairs[b], shared by the blocks).  Out: scale[b]; the columns of
+ * block b in its rows of V (n x hipfact_qn_block_cols(kind, memory) at most; rows of a column that the block does not
+ * use, and rows of no block, are not written); coef[b * hipfact_qn_block_cols(kind, memory) + k]; block_rank[b].  A block
+ * without pairs gets scale 1, rank 0.  work: max block length doubles (n always suffice).  Returns 0, or -1 for bad
+ * arguments.  The result for a block is, bit for bit, what hipfact_qn_terms gives on the slices. */
+static inline int hipfact_qn_block_cols(int kind, int memory) { return (kind == HIPFACT_QN_SR1 ? 1 : 2) * memory; }
+
+static inline int hipfact_qn_block_terms(int kind, int n, int nblocks, const int* block_end, const int* npairs,
+                                         int memory, const double* S, long long lds, const double* Y, long long ldy,
+                                         double* scale, double* V, long long ldv, double* coef, int* block_rank,
+                                         double* work)
+{
+  if (n < 1 || nblocks < 1 || nblocks > n || !block_end || !npairs || !scale || !block_rank || memory < 1
+      || memory > HIPFACT_QN_MAX_PAIRS || lds < n || ldy < n || ldv < n)
+    return -1;
+  const int cols = hipfact_qn_block_cols(kind, memory);
+  int begin      = 0;
+  for (int b = 0; b < nblocks; ++b)
+  {
+    if (block_end[b] <= begin || block_end[b] > n || npairs[b] < 0) return -1;
+    begin = block_end[b];
+  }
+  begin = 0;
+  for (int b = 0; b < nblocks; ++b)
+  {
+    const int end = block_end[b];
+    if (hipfact_qn_terms(kind, end - begin, npairs[b], memory, S ? S + begin : S, lds, Y ? Y + begin : Y, ldy, &scale[b],
+                         V ? V + begin : V, ldv, coef ? coef + (long long)b * cols : coef, &block_rank[b], 0, work)
+        != 0)
+      return -1;
+    begin = end;
+  }
+  return 0;
+}
+
 #endif /* SLEQP_AMD_QN_TERMS_H */

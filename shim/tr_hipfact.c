@@ -16,7 +16,9 @@
  * (sleqp_hipfact_tr_set_gauss_newton) the product is a device operator, hipfact_tr_solve_op.  A quasi-Newton
  * Hessian (SLEQP_HESS_EVAL_SR1 / SIMPLE_BFGS / DAMPED_BFGS) is scale I + V diag(coef) V' on a few dense vectors: with
  * sleqp_hipfact_tr_set_low_rank, or sleqp_hipfact_tr_push_pair on the accepted steps, its product stays on the device
- * as well (hipfact_tr_solve_lr).
+ * as well (hipfact_tr_solve_lr).  With the block structure of the function's Hessian (sleqp_hipfact_tr_set_hess_struct)
+ * the pairs are kept per block, as the reference's quasi-Newton objects keep them, and the Hessian is the block-diagonal
+ * term of hipfact_tr_solve_blocks.
  *
  * The projection comes from the factorisation inside the hipfact handle of the augmented Jacobian
  * (aug_jac_hipfact.c); the solver holds its own reference to that handle (sleqp_hipfact_tr_bind) —
@@ -72,6 +74,19 @@ struct SleqpHipfactTR
   double* qn_V;    /* num_variables x 2 QN_MEMORY */
   double* qn_work; /* num_variables */
 
+  /* the block structure of sleqp_hipfact_tr_set_hess_struct (hs_blocks 0: none): one ring of pairs per block inside the
+   * rows of qn_S / qn_Y, the terms per block and the block term of the handle with its V on the device (owned) */
+  int hs_blocks;
+  int* hs_ends;
+  int* hs_len;
+  int* hs_rank;
+  double* hs_scale;
+  double* hs_coef; /* hs_blocks x 2 QN_MEMORY */
+  hipfact_block_term* blk;
+  int blk_active;
+  void* blk_dev_V;
+  double eps;
+
   int method; /* HIPFACT_TR_GLTR / HIPFACT_TR_STEIHAUG */
   int max_iter;
   double rel_tol; /* stat_eps * tolerance_factor (steihaug_solver.c:21,241; trlib_solver.c:265) */
@@ -111,6 +126,21 @@ pattern_hash(const SleqpMat* matrix)
   return h;
 }
 
+/* the block term and its V live on the bound handle */
+static void
+block_term_drop(SleqpHipfactTR* solver)
+{
+  if (solver->blk)
+  {
+    hipfact_block_term_free(&solver->blk);
+  }
+  if (solver->blk_dev_V)
+  {
+    hipfact_device_release(solver->handle, &solver->blk_dev_V);
+  }
+  solver->blk_active = 0;
+}
+
 static SLEQP_RETCODE
 hipfact_tr_free(void** star)
 {
@@ -130,6 +160,13 @@ hipfact_tr_free(void** star)
   {
     hipfact_device_release(solver->handle, &solver->lr_dev_V);
   }
+
+  block_term_drop(solver);
+  sleqp_free(&solver->hs_coef);
+  sleqp_free(&solver->hs_scale);
+  sleqp_free(&solver->hs_rank);
+  sleqp_free(&solver->hs_len);
+  sleqp_free(&solver->hs_ends);
 
   hipfact_free(&solver->handle); /* our reference */
 
@@ -226,7 +263,31 @@ tr_callback_solve(SleqpAugJac* jacobian,
   hipfact_tr_extra extra = {.time_limit = time_limit, .timed_out = 0, .min_rayleigh = 1., .max_rayleigh = 1.};
   int status;
 
-  if (solver->lsq_jac || solver->lr_active)
+  if (solver->blk_active)
+  {
+    /* the block-diagonal quasi-Newton Hessian of the pairs pushed per block, beside what else is set */
+    const hipfact_hess_op op = {.hess   = solver->hessian,
+                                .gn_jac = solver->lsq_jac,
+                                .shift  = solver->lm_factor,
+                                .prod   = NULL,
+                                .user   = NULL};
+
+    const int beside = solver->hessian || solver->lsq_jac || solver->lm_factor != 0.;
+
+    status = hipfact_tr_solve_blocks(solver->handle,
+                                     solver->method,
+                                     beside ? &op : NULL,
+                                     solver->blk,
+                                     solver->dense_gradient,
+                                     trust_radius,
+                                     solver->rel_tol,
+                                     solver->max_iter,
+                                     solver->dense_step,
+                                     tr_dual,
+                                     &iterations,
+                                     &extra);
+  }
+  else if (solver->lsq_jac || solver->lr_active)
   {
     /* lsq_func_hess_product (lsq.c:211-263) as a device operator, on top of the explicit Hessian if one is set - and / or
      * a quasi-Newton Hessian scale I + V diag(coef) V' (without a term: hipfact_tr_solve_op itself) */
@@ -496,9 +557,172 @@ sleqp_hipfact_tr_set_low_rank(SleqpHipfactTR* solver,
 }
 
 SLEQP_RETCODE
+sleqp_hipfact_tr_set_hess_struct(SleqpHipfactTR* solver, int num_blocks, const int* block_ends)
+{
+  const int num_variables = sleqp_problem_num_vars(solver->problem);
+
+  /* the pairs kept so far belong to the old structure */
+  SLEQP_CALL(sleqp_hipfact_tr_reset_pairs(solver));
+
+  sleqp_free(&solver->hs_coef);
+  sleqp_free(&solver->hs_scale);
+  sleqp_free(&solver->hs_rank);
+  sleqp_free(&solver->hs_len);
+  sleqp_free(&solver->hs_ends);
+  solver->hs_blocks = 0;
+
+  if (num_blocks == 0)
+  {
+    return SLEQP_OKAY;
+  }
+
+  int prev = 0;
+  int bad  = num_blocks < 0 || num_blocks > num_variables || !block_ends;
+  for (int b = 0; !bad && b < num_blocks; ++b)
+  {
+    bad  = block_ends[b] <= prev || block_ends[b] > num_variables;
+    prev = block_ends[b];
+  }
+  if (bad)
+  {
+    sleqp_raise(SLEQP_ILLEGAL_ARGUMENT,
+                "hipfact TR solver: %d blocks need strictly ascending ends in 1 .. %d",
+                num_blocks,
+                num_variables);
+  }
+
+  SLEQP_CALL(sleqp_alloc_array(&solver->hs_ends, num_blocks));
+  SLEQP_CALL(sleqp_alloc_array(&solver->hs_len, num_blocks));
+  SLEQP_CALL(sleqp_alloc_array(&solver->hs_rank, num_blocks));
+  SLEQP_CALL(sleqp_alloc_array(&solver->hs_scale, num_blocks));
+  SLEQP_CALL(sleqp_alloc_array(&solver->hs_coef, (size_t)num_blocks * 2 * QN_MEMORY));
+  for (int b = 0; b < num_blocks; ++b)
+  {
+    solver->hs_ends[b] = block_ends[b];
+    solver->hs_len[b]  = 0;
+  }
+  solver->hs_blocks = num_blocks;
+
+  return SLEQP_OKAY;
+}
+
+/* a pair into the rings of the blocks (bfgs.c:640-691: a block whose slice of the step is zero keeps its ring), the
+ * terms of every block and the block term of the handle */
+static SLEQP_RETCODE
+push_pair_blocks(SleqpHipfactTR* solver, int kind, const SleqpVec* step_diff, const SleqpVec* grad_diff)
+{
+  const int num_variables = sleqp_problem_num_vars(solver->problem);
+  const size_t n          = (size_t)num_variables;
+  double* S               = solver->qn_S;
+  double* Y               = solver->qn_Y;
+  double* s               = solver->dense_gradient; /* (free between two solves) */
+  double* y               = solver->dense_step;
+
+  SLEQP_CALL(sleqp_vec_to_raw(step_diff, s));
+  SLEQP_CALL(sleqp_vec_to_raw(grad_diff, y));
+
+  int begin = 0;
+  for (int b = 0; b < solver->hs_blocks; ++b)
+  {
+    const int end    = solver->hs_ends[b];
+    const size_t len = (size_t)(end - begin);
+    double normsq    = 0.;
+    for (int i = begin; i < end; ++i)
+    {
+      normsq += s[i] * s[i];
+    }
+    if (normsq > solver->eps)
+    {
+      if (solver->hs_len[b] == QN_MEMORY)
+      {
+        /* the block's oldest pair leaves */
+        for (int j = 0; j + 1 < QN_MEMORY; ++j)
+        {
+          memcpy(S + n * (size_t)j + begin, S + n * (size_t)(j + 1) + begin, len * sizeof(double));
+          memcpy(Y + n * (size_t)j + begin, Y + n * (size_t)(j + 1) + begin, len * sizeof(double));
+        }
+        --solver->hs_len[b];
+      }
+      memcpy(S + n * (size_t)solver->hs_len[b] + begin, s + begin, len * sizeof(double));
+      memcpy(Y + n * (size_t)solver->hs_len[b] + begin, y + begin, len * sizeof(double));
+      ++solver->hs_len[b];
+    }
+    begin = end;
+  }
+
+  const long long ld = num_variables;
+  if (hipfact_qn_block_terms(kind,
+                             num_variables,
+                             solver->hs_blocks,
+                             solver->hs_ends,
+                             solver->hs_len,
+                             QN_MEMORY,
+                             S,
+                             ld,
+                             Y,
+                             ld,
+                             solver->hs_scale,
+                             solver->qn_V,
+                             ld,
+                             solver->hs_coef,
+                             solver->hs_rank,
+                             solver->qn_work)
+      != 0)
+  {
+    sleqp_raise(SLEQP_INTERNAL_ERROR, "hipfact TR solver: quasi-Newton terms per block");
+  }
+
+  int status = HIPFACT_OK;
+  if (!solver->blk)
+  {
+    status = hipfact_block_term_create(solver->handle, num_variables, solver->hs_blocks, solver->hs_ends, &solver->blk);
+  }
+
+  void* fresh    = NULL;
+  const int cols = hipfact_qn_block_cols(kind, QN_MEMORY);
+  if (status == HIPFACT_OK)
+  {
+    /* (the last column ends behind its n-th entry) */
+    const size_t count = (size_t)(cols - 1) * n + n;
+    status             = hipfact_device_upload(solver->handle, solver->qn_V, count * sizeof(double), &fresh);
+  }
+  if (status == HIPFACT_OK)
+  {
+    status = hipfact_block_term_set(solver->blk,
+                                    cols,
+                                    solver->hs_rank,
+                                    solver->hs_scale,
+                                    solver->hs_coef,
+                                    (const double*)fresh,
+                                    ld);
+  }
+  if (status != HIPFACT_OK)
+  {
+    if (fresh)
+    {
+      hipfact_device_release(solver->handle, &fresh);
+    }
+    sleqp_raise(SLEQP_INTERNAL_ERROR, "Caught hipfact error <%d> (%s)", status, hipfact_last_error(solver->handle));
+  }
+  if (solver->blk_dev_V)
+  {
+    hipfact_device_release(solver->handle, &solver->blk_dev_V); /* the term reads the new one from here on */
+  }
+  solver->blk_dev_V  = fresh;
+  solver->blk_active = 1;
+
+  return SLEQP_OKAY;
+}
+
+SLEQP_RETCODE
 sleqp_hipfact_tr_reset_pairs(SleqpHipfactTR* solver)
 {
   solver->qn_len = 0;
+  for (int b = 0; b < solver->hs_blocks; ++b)
+  {
+    solver->hs_len[b] = 0;
+  }
+  block_term_drop(solver);
   return sleqp_hipfact_tr_set_low_rank(solver, 0, NULL, 0, NULL, 0.);
 }
 
@@ -525,6 +749,12 @@ sleqp_hipfact_tr_push_pair(SleqpHipfactTR* solver, int kind, const SleqpVec* ste
     SLEQP_CALL(sleqp_alloc_array(&solver->qn_Y, n * QN_MEMORY + 1));
     SLEQP_CALL(sleqp_alloc_array(&solver->qn_V, n * 2 * QN_MEMORY + 1));
     SLEQP_CALL(sleqp_alloc_array(&solver->qn_work, n + 1));
+    memset(solver->qn_V, 0, (n * 2 * QN_MEMORY + 1) * sizeof(double)); /* (cells no block writes are uploaded too) */
+  }
+
+  if (solver->hs_blocks > 0)
+  {
+    return push_pair_blocks(solver, kind, step_diff, grad_diff);
   }
 
   if (solver->qn_len == QN_MEMORY)
@@ -573,6 +803,12 @@ sleqp_hipfact_tr_spectrum(SleqpHipfactTR* solver, int which, double rel_tol, dou
   if (!solver->handle)
   {
     sleqp_raise(SLEQP_INTERNAL_ERROR, "hipfact TR solver: no factorisation bound (sleqp_hipfact_tr_bind)");
+  }
+
+  if (solver->blk_active)
+  {
+    sleqp_raise(SLEQP_ILLEGAL_ARGUMENT,
+                "hipfact TR solver: the spectrum of a Hessian with a block-diagonal quasi-Newton term is not built");
   }
 
   if (!solver->hessian && !solver->lsq_jac && !solver->lr_active)
@@ -656,6 +892,9 @@ sleqp_hipfact_tr_bind(SleqpHipfactTR* solver, struct hipfact_handle* handle)
     solver->lr_rank   = 0;
   }
 
+  /* likewise the block term: the rings stay, the next push builds it on the new handle */
+  block_term_drop(solver);
+
   if (solver->handle)
   {
     hipfact_free(&solver->handle);
@@ -698,11 +937,13 @@ sleqp_hipfact_tr_solver_create(SleqpTRSolver** star,
   solver->max_iter                 = sleqp_settings_max_newton_iterations(settings);
   solver->rel_tol                  = sleqp_settings_stat_tol(settings) * 1e-2;
   solver->zero_eps                 = sleqp_settings_zero_eps(settings);
+  solver->eps                      = sleqp_settings_eps(settings);
   const SLEQP_TR_SOLVER tr_solver = sleqp_settings_tr_solver(settings);
 #else
   solver->max_iter = sleqp_settings_int_value(settings, SLEQP_SETTINGS_INT_MAX_NEWTON_ITERATIONS);
   solver->rel_tol  = sleqp_settings_real_value(settings, SLEQP_SETTINGS_REAL_STAT_TOL) * 1e-2;
   solver->zero_eps = sleqp_settings_real_value(settings, SLEQP_SETTINGS_REAL_ZERO_EPS);
+  solver->eps      = sleqp_settings_real_value(settings, SLEQP_SETTINGS_REAL_EPS);
   const SLEQP_TR_SOLVER tr_solver
     = (SLEQP_TR_SOLVER)sleqp_settings_enum_value(settings, SLEQP_SETTINGS_ENUM_TR_SOLVER);
 #endif

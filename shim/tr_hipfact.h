@@ -80,6 +80,19 @@ SLEQP_WARNUNUSED
 SLEQP_RETCODE
 sleqp_hipfact_tr_reset_pairs(SleqpHipfactTR* ctl);
 
+/* Optional: the block structure of the function's Hessian, as plain ints - what sleqp_hess_struct_num_blocks and
+ * sleqp_hess_struct_block_range hand a caller: block b covers the variables [block_ends[b-1], block_ends[b]), the ends
+ * strictly ascending, the variables behind the last end are the linear range.  From then on sleqp_hipfact_tr_push_pair
+ * keeps one ring of five pairs PER BLOCK, as the reference's quasi-Newton objects do (quasi_newton/bfgs.c, sr1.c): a
+ * block whose slice of step_diff has a squared norm of at most SLEQP_SETTINGS_REAL_EPS keeps its ring, a block without
+ * pairs is the identity, the linear range has no curvature.  The Hessian of the solve is then [explicit Hessian if set]
+ * + [Gauss-Newton term if set] + blockdiag_b(scale_b I + V_b diag(coef_b) V_b') (hipfact_tr_solve_blocks).  The call
+ * drops the pairs kept so far; num_blocks = 0 returns to one quasi-Newton matrix over all variables.
+ * sleqp_hipfact_tr_reset_pairs empties every ring.  Without this call nothing changes. */
+SLEQP_WARNUNUSED
+SLEQP_RETCODE
+sleqp_hipfact_tr_set_hess_struct(SleqpHipfactTR* ctl, int num_blocks, const int* block_ends);
+
 /* The extreme eigenvalue of the reduced Hessian Z' H Z on the null space of the bound factorisation's working set
  * (hipfact_projected_eig): what check_spectrum (newton.c:318-346) can only bound from the inside with the Rayleigh
  * quotients of one Krylov run (SLEQP_SOLVER_STATE_REAL_MIN_RAYLEIGH / _MAX_RAYLEIGH, problem_solver/state.c:46-51).  H is

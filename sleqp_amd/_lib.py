@@ -47,6 +47,9 @@ SYMBOLS = [
     "hipfact_debug_spmat_row_blocks", "hipfact_debug_spmv_lanes", "hipfact_debug_lr_dots_blocks", "hipfact_debug_qn_terms", "hipfact_device_upload", "hipfact_device_release",
     "hipfact_projected_eig_device", "hipfact_projected_eig", "hipfact_debug_ritz_dense", "hipfact_debug_ritz_tridiag",
     "hipfact_tr_solve_device", "hipfact_hess_apply_device_ex", "hipfact_debug_sizeof",
+    "hipfact_block_term_create", "hipfact_block_term_set", "hipfact_block_term_free", "hipfact_tr_solve_blocks",
+    "hipfact_tr_solve_device_blocks", "hipfact_hess_apply_device_blocks", "hipfact_debug_block_items",
+    "hipfact_debug_qn_block_terms", "hipfact_debug_block_values",
     "hipfact_plan_free", "hipfact_plan_error", "hipfact_plan_array", "hipfact_plan_scalar",
 ]
 
@@ -161,6 +164,17 @@ def load() -> C.CDLL:
         lib.hipfact_device_release.argtypes = [vp, C.POINTER(vp)]
         lib.hipfact_debug_qn_terms.argtypes = [ci, ci, ci, ci, vp, vp, C.POINTER(cd), vp, vp, C.POINTER(ci),
                                                C.POINTER(C.c_uint)]
+    if hasattr(lib, "hipfact_block_term_create"):
+        lib.hipfact_block_term_create.argtypes = [vp, ci, ci, vp, C.POINTER(vp)]
+        lib.hipfact_block_term_set.argtypes = [vp, ci, vp, vp, vp, vp, C.c_longlong]
+        lib.hipfact_block_term_free.argtypes = [C.POINTER(vp)]
+        lib.hipfact_tr_solve_blocks.argtypes = [vp, ci, vp, vp, vp, cd, cd, ci, vp, C.POINTER(cd), C.POINTER(ci), vp]
+        lib.hipfact_tr_solve_device_blocks.argtypes = [vp, ci, vp, vp, vp, vp, cd, cd, ci, vp, C.POINTER(cd),
+                                                       C.POINTER(ci), vp]
+        lib.hipfact_hess_apply_device_blocks.argtypes = [vp, vp, vp, vp, vp, vp]
+        lib.hipfact_debug_block_items.argtypes = [ci, ci, vp, vp, ci, vp, vp]
+        lib.hipfact_debug_block_values.argtypes = [ci, ci, ci, vp, vp, vp, ci, C.c_longlong]
+        lib.hipfact_debug_qn_block_terms.argtypes = [ci, ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp]
     if hasattr(lib, "hipfact_projected_eig"):
         lib.hipfact_projected_eig_device.argtypes = [vp, vp, vp, ci, vp, vp, vp]
         lib.hipfact_projected_eig.argtypes = [vp, vp, vp, ci, vp, vp, vp]

@@ -684,12 +684,19 @@ int hipfact_tr_solve_ex(hipfact_handle* h, int method, hipfact_spmat* hess, hipf
 // hipfact_tr_solve_op / hipfact_tr_solve_lr, and hipfact_hess_op_apply_device / hipfact_hess_lr_apply_device: one body
 // each, the low-rank term `lr` beside the operator or NULL (NULL or rank 0: no term - the launches and the bits of the
 // operator alone)
+// (T, blocks: the entry points of abi_block_term.inc - a block-diagonal term beside the operator, required there)
+static int no_block_term(hipfact_handle* h, const char* who) {
+  h->error = std::string(who) + ": no block term";
+  return HIPFACT_EINVAL;
+}
 static int tr_solve_op_lr(hipfact_handle* h, const char* who, int method, const hipfact_hess_op* op_in,
                           const hipfact_low_rank* lr, const double* gradient, double trust_radius, double rel_tol,
-                          int max_iter, double* newton_step, double* tr_dual, int* iterations, hipfact_tr_extra* extra) {
+                          int max_iter, double* newton_step, double* tr_dual, int* iterations, hipfact_tr_extra* extra,
+                          const hipfact_block_term* T = nullptr, bool blocks = false) {
   if (!h) return HIPFACT_EINVAL;
   HessOp op;
-  int rc = hess_op_from_abi(h, op_in, who, &op, lr);  // (in front of the device: a NULL op touches none)
+  int rc = hess_op_from_abi(h, op_in, who, &op, lr, nullptr, false, T);  // (in front of the device: a NULL op touches none)
+  if (!rc && blocks && !T) rc = no_block_term(h, who);
   if (rc || (rc = enter(h))) return rc;
   ++h->hess_op_solves;
   h->hess_op_call = true;
@@ -703,10 +710,11 @@ static int tr_solve_op_lr(hipfact_handle* h, const char* who, int method, const 
 // counting call as it is.)
 static int hess_op_lr_apply(hipfact_handle* h, const char* who, const hipfact_hess_op* op_in, const hipfact_low_rank* lr,
                             const double* d_x, double* d_y, const hipfact_device_prod* dp = nullptr,
-                            bool device_entry = false) {
+                            bool device_entry = false, const hipfact_block_term* T = nullptr, bool blocks = false) {
   if (!h) return HIPFACT_EINVAL;
   HessOp op;
-  int rc = hess_op_from_abi(h, op_in, who, &op, lr, dp, device_entry);  // (in front of the device: a NULL op touches none)
+  int rc = hess_op_from_abi(h, op_in, who, &op, lr, dp, device_entry, T);  // (in front of the device: a NULL op touches none)
+  if (!rc && blocks && !T) rc = no_block_term(h, who);
   if (rc || (rc = enter(h))) return rc;
   if ((rc = require_factor(h, who))) return rc;
   // (n from the factorisation, as in the loops, whose check it shares: the vectors stand in for gradient and step)
@@ -732,11 +740,12 @@ static int hess_op_lr_apply(hipfact_handle* h, const char* who, const hipfact_he
 static int tr_solve_device_impl(hipfact_handle* h, int method, const hipfact_hess_op* op_in, const hipfact_low_rank* lr,
                                 const hipfact_device_prod* dp, const double* d_gradient, double trust_radius,
                                 double rel_tol, int max_iter, double* d_step, double* tr_dual, int* iterations,
-                                hipfact_tr_extra* extra) {
-  const char* who = "hipfact_tr_solve_device";
+                                hipfact_tr_extra* extra, const char* who = "hipfact_tr_solve_device",
+                                const hipfact_block_term* T = nullptr, bool blocks = false) {
   if (!h) return HIPFACT_EINVAL;
   HessOp op;
-  int rc = hess_op_from_abi(h, op_in, who, &op, lr, dp, true);
+  int rc = hess_op_from_abi(h, op_in, who, &op, lr, dp, true, T);
+  if (!rc && blocks && !T) rc = no_block_term(h, who);
   if (rc || (rc = enter(h))) return rc;
   ++h->hess_op_solves;
   // what the loops refuse, here in their order, so that the checks of the device form stand behind it

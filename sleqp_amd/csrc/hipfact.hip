@@ -24,6 +24,7 @@
 //   runtime_border.inc  bordered solve [K B; B^T C] on the factor of K (border_rule.h) abi_border.inc hipfact_border_set / _clear, hipfact_solve[_device]_bordered, _debug_border_*
 //   runtime_ritz.inc    extreme eigenpairs of the projected Hessian, restarted Lanczos (ritz_rule.h) abi_ritz.inc hipfact_projected_eig[_device], _debug_ritz_*
 //                       (included by abi_ritz.inc behind abi_krylov.inc: it runs on that file's operator product)
+//   runtime_block_term.inc block-diagonal quasi-Newton term of the operator (block_term_items.h) abi_block_term.inc hipfact_block_term_*, hipfact_tr_solve[_device]_blocks, hipfact_hess_apply_device_blocks
 //   refine_cadence.h    refinement cadence of the single solve: passes in the graph, residual checks, deferred verdicts
 //                       (pure host rules, like xcd_place.h and multi_slices.h)
 #include <hip/hip_runtime.h>
@@ -64,6 +65,7 @@
 #include "gmres_rule.h"
 #include "border_rule.h"
 #include "ritz_rule.h"
+#include "block_term_items.h"
 #include "selinv_types.h"
 #include "selinv_host.h"
 #include "dd_arith.h"
@@ -80,6 +82,7 @@
 #include "runtime_selinv.inc"
 #include "runtime_gmres.inc"
 #include "runtime_border.inc"
+#include "runtime_block_term.inc"
 
 extern "C" {
 #include "abi_core.inc"
@@ -93,6 +96,7 @@ extern "C" {
 #include "abi_border.inc"
 #include "abi_working_set.inc"
 #include "abi_krylov.inc"
+#include "abi_block_term.inc"
 #include "abi_ritz.inc"
 #include "abi_options.inc"
 }  // extern "C"

@@ -125,7 +125,10 @@ struct XupdIn {
 // the lower triangle of H0 by rows (hp, hi, hv) and by columns (hp2, hi2, hv2), null without H0; J_r^T by rows (jp, ji,
 // jv: the column arrays of J_r) against t = J_r x, null without J_r; the low-rank term V diag(coef) V^T as lv (column-major,
 // leading dimension lld), lrank columns and lu[k] = coef_k (V_k . x), null / 0 without a term; e = H_user x, the product the
-// caller queued in front of stage 1 (hipfact_device_prod), null without one
+// caller queued in front of stage 1 (hipfact_device_prod), null without one; the block-diagonal term
+// blockdiag_b(scale_b I + V_b diag(c_b) V_b^T) (hipfact_block_term) as bmap (the row's block, -1 in the linear range), bv
+// (column-major, leading dimension bld), brank / bscale per block and bu[bstride b + k] = c_bk (V_bk . x_b), all null / 0
+// without one
 constexpr int LR_MAX_RANK = 32;  // most columns of the low-rank term
 constexpr int LR_BLOCKS = 256;   // most blocks (= partial sums per column) of k_lr_dots
 struct LrCoef {
@@ -148,6 +151,13 @@ struct HessRows {
   int lrank;
   long long lld;
   const double* __restrict__ e;
+  const int* __restrict__ bmap;
+  const double* __restrict__ bu;
+  const int* __restrict__ brank;
+  const double* __restrict__ bscale;
+  const double* __restrict__ bv;
+  long long bld;
+  int bstride;
 };
 struct CgCtl {
   double rg, z_nrm_sq, rel_tol_sq, rad_sq, alpha, beta, tau;

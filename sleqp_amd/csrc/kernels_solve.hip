@@ -35,6 +35,7 @@
 
 #include "device_types.h"
 #include "kernel_types.h"
+#include "block_term_items.h"
 
 namespace hipfact {
 #include "kernels_common.inc"
@@ -56,6 +57,9 @@ namespace hipfact {
 #define KRYLOV_HESS_OP_KERNELS
 #include "krylov_hess_op.inc"
 #undef KRYLOV_HESS_OP_KERNELS
+namespace hipfact {
+#include "kernels_block_term.inc"
+}  // namespace hipfact
 #define KRYLOV_LSQR_KERNELS
 #include "krylov_lsqr.inc"
 #undef KRYLOV_LSQR_KERNELS
@@ -107,6 +111,14 @@ INST_LR(8)
 INST_LR(16)
 INST_LR(32)
 #undef INST_LR
+#define INST_BLK(RC)                                                                                                  \
+  template __global__ void k_blk_dots<RC>(int, int, int, const int4*, const int*, const double*, const double*,       \
+                                          long long, const double*, double*, double*);                                \
+  template __global__ void k_blk_totals<RC>(const int*, const int*, const double*, const double*, double*);
+INST_BLK(8)
+INST_BLK(16)
+INST_BLK(32)
+#undef INST_BLK
 #define INST_LSQR(L)                                                                                                  \
   template __global__ void k_lsqr_forward<L>(int, int, const int*, const int*, const double*, const double*,         \
                                              const int*, const int*, const double*, const double*, double, double,   \

@@ -17,7 +17,10 @@
 //               2. onto it the lane's share of row i of J_r^T (the cp / ri / val arrays of the matrix) against t,
 //               2b. onto it the lane's share of row i of V against u, fma(V_ik, u_k, .) for k = sub, sub + LANES, ...
 //                  ascending, if a low-rank term is present (below),
+//               2c. onto it the lane's share of the row's block of a block-diagonal term: fma(V_ik, u_bk, .) for k = sub,
+//                  sub + LANES, ... < block_rank[b] ascending, b the row's block (none in the linear range) (below),
 //               3. the shuffle tree over the row's lanes (lanes_sum),
+//               3b. fma(scale_b, x_i, .) in the row's lane 0, if the row lies in a block of a block-diagonal term,
 //               4. fma(shift, x_i, .) in the row's lane 0.
 // A low-rank term V diag(coef) V^T (hipfact_low_rank: the outer products of a BFGS / SR1 Hessian, qn_terms.h; rank <= 32,
 // V dense, column-major, on the device) adds to stage 1
@@ -27,6 +30,13 @@
 //             u_k = coef_k w_k (k_lr_totals: ONE workgroup sums the partials with block_totals, in index order, and
 //             leaves u in the handle's buffer behind them).  Like t = J_r x both write nothing but those buffers of the
 //             handle and are queued unconditionally.
+// A block-diagonal term blockdiag_b(scale_b I + V_b diag(c_b) V_b^T) (+) 0 (hipfact_block_term: the reference's
+// quasi-Newton matrices over the blocks of a SleqpHessStruct; an object of the handle, runtime_block_term.inc) adds
+//   stage 1b' u_bk = c_bk (V_bk . x_b) for every block in ONE launch over a work list that follows from the block ends
+//             alone (k_blk_dots of kernels_block_term.inc over the items of block_term_items.h: a thread, a wave or
+//             segments of a workgroup each per block, by its length; k_blk_totals adds the segments of the long blocks and
+//             is queued only when there is one).  They write nothing but buffers of the TERM and are queued
+//             unconditionally.
 // A queued product of the caller's (hipfact_device_prod: a HIP kernel of its own, an autodiff Hessian-vector product on
 // the same GPU) adds IN FRONT of stage 1
 //   stage 0   e = H_user x: the callback queues it on the handle's stream into an n-vector of the handle (hess_op_dprod).
@@ -52,7 +62,14 @@ __device__ __forceinline__ double hess_op_row(const HessRows& o, int row, int su
   if (o.jp) s = csr_row_add<LANES>(s, row, sub, o.jp, o.ji, o.jv, o.t);
   if (o.lv)
     for (int k = sub; k < o.lrank; k += LANES) s = fma(o.lv[row + k * o.lld], o.lu[k], s);
+  const int blk = o.bmap ? o.bmap[row] : -1;
+  if (blk >= 0) {
+    const int r = o.brank[blk];
+    const double* __restrict__ ub = o.bu + (long long)blk * o.bstride;
+    for (int k = sub; k < r; k += LANES) s = fma(o.bv[row + k * o.bld], ub[k], s);
+  }
   s = lanes_sum<LANES>(s);
+  if (blk >= 0) s = fma(o.bscale[blk], x[row], s);
   return fma(o.shift, x[row], s);
 }
 
@@ -206,8 +223,11 @@ struct HessOp {
   hipfact_hess_prod_device_fn dfn = nullptr;
   void* duser = nullptr;
   bool dqueue = false;
+  // the block-diagonal term blockdiag_b(scale_b I + V_b diag(c_b) V_b^T) (hipfact_block_term; null: none): an object of
+  // the handle, its values on the device
+  const hipfact_block_term* blk = nullptr;
   // an explicit Hessian and nothing else: the kernels of krylov_device.inc and the symmetric product of the matrix
-  bool plain() const { return hess && !gn_jac && shift == 0.0 && !prod && lrank == 0 && !dhave; }
+  bool plain() const { return hess && !gn_jac && shift == 0.0 && !prod && lrank == 0 && !dhave && !blk; }
   // a product that needs the host in every iteration: the device-controlled loops stay out
   bool host_driven() const { return prod || (dhave && !dqueue); }
 };
@@ -217,7 +237,8 @@ static int hess_lanes(const hipfact_spmat* hess, int n) { return spmv_lanes(2.0 
 // ... and of stage 2 of the operator: its entries per row (hess_lanes for an explicit Hessian alone)
 static int hess_op_lanes(const HessOp& op, int n) {
   const double ent = (op.hess ? 2.0 * (double)op.hess->nnz : 0.0) + (op.gn_jac ? (double)op.gn_jac->nnz : 0.0);
-  return spmv_lanes(ent / std::max(n, 1) + op.lrank);  // (the term: `rank` more entries in every row)
+  // (the terms: `rank` more entries in every row, the dense one and the block-diagonal one alike)
+  return spmv_lanes(ent / std::max(n, 1) + op.lrank + (op.blk ? op.blk->rank : 0));
 }
 // blocks of k_lr_dots (= partials per column of the low-rank term): from n alone
 static int lr_blocks(long long n) { return (int)std::max(1LL, std::min<long long>(LR_BLOCKS, (n + FB - 1) / FB)); }
@@ -227,14 +248,15 @@ static int lr_blocks(long long n) { return (int)std::max(1LL, std::min<long long
 // the operator, and a host `prod` is refused behind everything else: that caller uses the host entry points)
 static int hess_op_from_abi(hipfact_handle* h, const hipfact_hess_op* in, const char* who, HessOp* op,
                             const hipfact_low_rank* lr = nullptr, const hipfact_device_prod* dp = nullptr,
-                            bool device_entry = false) {
+                            bool device_entry = false, const hipfact_block_term* T = nullptr) {
   const char* bad = nullptr;
   const bool term = lr && lr->rank != 0;
   static const hipfact_hess_op nothing = {nullptr, nullptr, 0.0, nullptr, nullptr};
-  if (!in && device_entry && (dp || term)) in = &nothing;
+  // (a block term stands for the operator in the host form too)
+  if (!in && ((device_entry && (dp || term)) || T)) in = &nothing;
   if (!in)
     bad = "no operator";
-  else if (!in->hess && !in->gn_jac && in->shift == 0.0 && !in->prod && !term && !dp)
+  else if (!in->hess && !in->gn_jac && in->shift == 0.0 && !in->prod && !term && !dp && !T)
     bad = "an operator with nothing in it";
   else if (!std::isfinite(in->shift))
     bad = "non-finite shift";
@@ -265,6 +287,18 @@ static int hess_op_from_abi(hipfact_handle* h, const hipfact_hess_op* in, const 
     op->lld = lr->ld;
     op->lrank = lr->rank;
     for (int k = 0; k < lr->rank; ++k) op->lcoef.c[k] = lr->coef[k];
+  }
+  if (T) {
+    // behind everything the entry points without a block term refuse: the term itself
+    if (T->h != h)
+      bad = "a block term of another handle";
+    else if (in->prod)
+      bad = "a block term beside a product callback";
+    if (bad) {
+      h->error = std::string(who) + ": " + bad;
+      return HIPFACT_EINVAL;
+    }
+    op->blk = T;
   }
   if (dp) {
     op->dhave = true;
@@ -371,6 +405,11 @@ static int hess_op_stage1(hipfact_handle* h, const HessOp& op, int n, const doub
     R->lrank = op.lrank;
     R->lld = op.lld;
   }
+  // stage 1b': u_bk = c_bk (V_bk . x_b) of the block-diagonal term, into the term's own buffer
+  if (op.blk) {
+    int rc;
+    if ((rc = block_term_stage1(h, op.blk, x, R))) return rc;
+  }
   return HIPFACT_OK;
 }
 
@@ -382,6 +421,10 @@ static void hess_op_count(hipfact_handle* h, const HessOp& op, long products) {
   if (op.lrank > 0 && products > 0) {
     h->hess_lr_products += products;
     h->hess_lr_rank = op.lrank;
+  }
+  if (op.blk && products > 0) {
+    h->hess_blk_products += products;
+    h->hess_blk_blocks = op.blk->nblocks;
   }
 }
 
@@ -417,12 +460,16 @@ static int tr_args_ok(hipfact_handle* h, const HessOp& op, const double* gradien
                       double trust_radius, const char* who) {
   const Plan& P = h->plan;
   const int n = P.saddle ? P.n : 0;
-  bool hess_ok = op.hess || op.gn_jac || op.shift != 0.0 || op.prod != nullptr || op.lrank > 0 || op.dhave;
+  bool hess_ok = op.hess || op.gn_jac || op.shift != 0.0 || op.prod != nullptr || op.lrank > 0 || op.dhave || op.blk;
   if (op.hess) hess_ok = hess_ok && op.hess->h == h && op.hess->rows == n && op.hess->cols == n;
   if (op.gn_jac) hess_ok = hess_ok && op.gn_jac->h == h && op.gn_jac->cols == n;
   if (!P.saddle || !hess_ok || !gradient || !newton_step || !(trust_radius > 0.0)) {
     h->error = std::string(who) + ": needs a factorised saddle matrix and an n x n Hessian (explicit, on the same "
                                   "handle, a residual Jacobian with n columns, or a product callback)";
+    return HIPFACT_EINVAL;
+  }
+  if (op.blk && op.blk->n != n) {
+    h->error = std::string(who) + ": the block term was created for another n";
     return HIPFACT_EINVAL;
   }
   if (op.lrank > 0 && op.lld < n) {

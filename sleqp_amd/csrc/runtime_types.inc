@@ -485,6 +485,10 @@ struct hipfact_handle : PlanState, SingleSolveMemo {
   DevBuf d_hess_lr;
   long hess_lr_products = 0;
   int hess_lr_rank = 0;
+  // ... the products formed with a block-diagonal term (hipfact_block_term: its sums live in the term) and the number of
+  // blocks of the last one
+  long hess_blk_products = 0;
+  int hess_blk_blocks = 0;
   long hess_op_solves = 0, hess_op_products = 0;
   bool hess_op_call = false;
   // ... e = H_user x of the caller's queued product (hipfact_device_prod), n doubles, allocated on first use; calls of

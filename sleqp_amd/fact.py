@@ -687,6 +687,95 @@ class HipFact:
                 self._h, op, lr, dp, C.c_void_p(d_x_ptr or None), C.c_void_p(d_y_ptr or None)),
             dprod, queue_only, hess, gn_jac, shift, V, coef, ld, n)
 
+    def block_term(self, block_end, n=None):
+        """hipfact_block_term_create: a block-diagonal quasi-Newton term blockdiag_b(scale_b I + V_b diag(c_b) V_b') for
+        the structure block_end (ascending block ends; rows behind the last one are the linear range).  n: the number of
+        variables (default: that of the factorised saddle matrix).  A new term is the identity on its blocks."""
+        return BlockTerm(self, block_end, int(self.info("n")) if n is None else int(n))
+
+    def _blocks_op(self, hess, gn_jac, shift, n):
+        """the operator beside a block term: NULL when nothing stands beside it"""
+        if hess is None and gn_jac is None and shift == 0.0:
+            return None, None
+        op, keep = self._hess_op(hess, gn_jac, shift, n)
+        return C.byref(op), (op, keep)
+
+    def hess_blocks_apply(self, x, term, hess=None, gn_jac=None, shift: float = 0.0, dprod=None,
+                          queue_only: bool = True, witness: bool = False):
+        """hipfact_hess_apply_device_blocks around a host vector: y = (dprod + sym(hess) + gn_jac' gn_jac + shift I +
+        term) x.  witness: returns (y, guard) - eight doubles behind y that were set to a pattern before the call."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        n = x.size
+        if n != int(self.info("n")):  # (the library trusts the length of a device vector)
+            raise ValueError(f"hess_blocks_apply: {n} entries for n = {int(self.info('n'))}")
+        op_ref, _keep = self._blocks_op(hess, gn_jac, shift, n)
+        dp, _cb = self._device_prod(dprod, queue_only)
+        G = 8
+        out = np.full(n + G, -7.25, dtype=np.float64)
+        hip = C.CDLL("libamdhip64.so")
+        buf = C.c_void_p()  # x | y | guard
+        if hip.hipMalloc(C.byref(buf), C.c_size_t(16 * n + 8 * G + 16)) != 0:
+            raise MemoryError("hipMalloc")
+        try:
+            d_x, d_y = buf.value, buf.value + 8 * n
+            if n and hip.hipMemcpy(C.c_void_p(d_x), _ptr(x), C.c_size_t(x.nbytes), 1) != 0:
+                raise RuntimeError("hipMemcpy")
+            if hip.hipMemcpy(C.c_void_p(d_y), _ptr(out), C.c_size_t(out.nbytes), 1) != 0:
+                raise RuntimeError("hipMemcpy")
+            self._check(self._lib.hipfact_hess_apply_device_blocks(
+                self._h, op_ref, term._t if term is not None else None, C.byref(dp) if dp is not None else None,
+                C.c_void_p(d_x), C.c_void_p(d_y)))
+            self._check(self._lib.hipfact_synchronize(self._h))
+            if hip.hipMemcpy(_ptr(out), C.c_void_p(d_y), C.c_size_t(out.nbytes), 2) != 0:
+                raise RuntimeError("hipMemcpy")
+        finally:
+            self._lib.hipfact_synchronize(self._h)
+            hip.hipFree(buf)
+        if witness:
+            return out[:n].copy(), out[n:].copy()
+        return out[:n].copy()
+
+    def tr_solve_blocks(self, gradient, trust_radius: float, term, hess=None, gn_jac=None, shift: float = 0.0,
+                        method: int = 0, stat_tol: float = 1e-6, max_iter: int = 100, time_limit: float = -1.0,
+                        device: bool = False, dprod=None, queue_only: bool = True):
+        """hipfact_tr_solve_blocks: tr_solve_op on H = sym(hess) + gn_jac' gn_jac + shift I + term, `term` a BlockTerm of
+        this handle (it may stand alone).  device=True: hipfact_tr_solve_device_blocks on device copies of the gradient
+        and the step, optionally with the queued product `dprod` beside the operator (tr_solve_device).  Returns (step,
+        tr_dual, iterations); `self.last_tr` as tr_solve leaves it."""
+        g = np.ascontiguousarray(gradient, dtype=np.float64)
+        n = g.size
+        step = np.empty_like(g)
+        dual, its = C.c_double(), C.c_int()
+        op_ref, _keep = self._blocks_op(hess, gn_jac, shift, n)
+        extra = TrExtra(float(time_limit), 0, 1.0, 1.0)
+        t = term._t if term is not None else None
+        if not device:
+            self._check(self._lib.hipfact_tr_solve_blocks(self._h, int(method), op_ref, t, _ptr(g), float(trust_radius),
+                                                          stat_tol * 1e-2, int(max_iter), _ptr(step), C.byref(dual),
+                                                          C.byref(its), C.byref(extra)))
+        else:
+            dp, _cb = self._device_prod(dprod, queue_only)
+            hip = C.CDLL("libamdhip64.so")
+            buf = C.c_void_p()  # gradient | step
+            if hip.hipMalloc(C.byref(buf), C.c_size_t(max(16 * n, 16))) != 0:
+                raise MemoryError("hipMalloc")
+            try:
+                d_g, d_s = buf.value, buf.value + 8 * n
+                if n and hip.hipMemcpy(C.c_void_p(d_g), _ptr(g), C.c_size_t(g.nbytes), 1) != 0:
+                    raise RuntimeError("hipMemcpy")
+                self._check(self._lib.hipfact_tr_solve_device_blocks(
+                    self._h, int(method), op_ref, t, C.byref(dp) if dp is not None else None, C.c_void_p(d_g),
+                    float(trust_radius), stat_tol * 1e-2, int(max_iter), C.c_void_p(d_s), C.byref(dual), C.byref(its),
+                    C.byref(extra)))
+                if n and hip.hipMemcpy(_ptr(step), C.c_void_p(d_s), C.c_size_t(step.nbytes), 2) != 0:
+                    raise RuntimeError("hipMemcpy")
+            finally:
+                self._lib.hipfact_synchronize(self._h)
+                hip.hipFree(buf)
+        self.last_tr = {"timed_out": bool(extra.timed_out), "min_rayleigh": extra.min_rayleigh,
+                        "max_rayleigh": extra.max_rayleigh}
+        return step, dual.value, its.value
+
     def projected_eig(self, which: int = -1, hess=None, gn_jac=None, shift: float = 0.0, V=None, coef=None, ld=None,
                       prod=None, start=None, want_vec: bool = True, rel_tol: float = 0.0, basis: int = 0,
                       max_restarts: int = -1, time_limit: float = -1.0, device=None):
@@ -1112,6 +1201,127 @@ def qn_terms(kind: int, S, Y, memory: int = 5):
         raise ValueError(f"hipfact_debug_qn_terms: {rc}")
     r = rank.value
     return scale.value, np.ascontiguousarray(V[:n, :r]), coef[:r].copy(), [bool(damped.value >> j & 1) for j in range(used)]
+
+
+def qn_block_terms(kind: int, block_end, S, Y, npairs, memory: int = 5):
+    """hipfact_debug_qn_block_terms (no GPU): the block-diagonal quasi-Newton Hessian of per-block pairs.  block_end:
+    ascending block ends (rows behind the last one: the linear range); S, Y: n x max(npairs), block b's pairs oldest
+    first in the columns 0 .. npairs[b] - 1 of its rows.  Returns (scale (nblocks), V (n x cols, rows of unused columns
+    and of the linear range zero), coef (nblocks x cols), block_rank (nblocks)) with cols = (1 or 2) * memory - the
+    arguments of BlockTerm.set."""
+    from . import _lib
+
+    lib = _lib.load()
+    be = np.ascontiguousarray(block_end, dtype=np.int32)
+    npairs = np.ascontiguousarray(npairs, dtype=np.int32)
+    S = np.asfortranarray(S, dtype=np.float64)
+    Y = np.asfortranarray(Y, dtype=np.float64)
+    if S.ndim != 2 or S.shape != Y.shape or npairs.size != be.size or (npairs.size and npairs.max() > S.shape[1]):
+        raise ValueError("qn_block_terms: S and Y must be n x max(npairs), one pair count per block")
+    n = S.shape[0]
+    cols = (1 if kind == QN_SR1 else 2) * int(memory)
+    V = np.zeros((max(n, 1), cols), order="F")
+    coef = np.zeros((be.size, cols))
+    scale = np.zeros(be.size)
+    block_rank = np.zeros(be.size, dtype=np.int32)
+    rc = lib.hipfact_debug_qn_block_terms(int(kind), n, be.size, _ptr(be), _ptr(npairs), int(memory), _ptr(S), _ptr(Y),
+                                          _ptr(scale), _ptr(V), _ptr(coef), _ptr(block_rank))
+    if rc != 0:
+        raise ValueError(f"hipfact_debug_qn_block_terms: {rc}")
+    return scale, np.ascontiguousarray(V[:n]), coef, block_rank
+
+
+def block_items(n: int, block_end):
+    """hipfact_debug_block_items (no GPU): the work list of the block term's dot kernel for a structure.  Returns
+    (items (count x 4: class, block, first row, rows), row_blk (n), {"short": BT_SHORT, "wave": BT_WAVE, "seg": BT_SEG})."""
+    from . import _lib
+
+    lib = _lib.load()
+    be = np.ascontiguousarray(block_end, dtype=np.int32)
+    consts = np.zeros(3, dtype=np.int32)
+    count = lib.hipfact_debug_block_items(int(n), be.size, _ptr(be), None, 0, None, _ptr(consts))
+    if count < 0:
+        raise ValueError(f"hipfact_debug_block_items: {count}")
+    items = np.zeros((count, 4), dtype=np.int32)
+    row_blk = np.full(n, -2, dtype=np.int32)
+    assert lib.hipfact_debug_block_items(int(n), be.size, _ptr(be), _ptr(items), count, _ptr(row_blk), None) == count
+    return items, row_blk, {"short": int(consts[0]), "wave": int(consts[1]), "seg": int(consts[2])}
+
+
+class BlockTerm:
+    """hipfact_block_term (include/hipfact.h): a block-diagonal quasi-Newton term of one HipFact handle.  `set` uploads
+    V and keeps the device copy until the next `set` / `free`."""
+
+    def __init__(self, fact, block_end, n: int):
+        self._fact = fact
+        self._lib = fact._lib
+        self.n = int(n)
+        self.block_end = np.ascontiguousarray(block_end, dtype=np.int32)
+        self.nblocks = int(self.block_end.size)
+        self._t = C.c_void_p()
+        self._dV = C.c_void_p()
+        self._cols = np.empty(0)
+        fact._check(self._lib.hipfact_block_term_create(fact._h, self.n, self.nblocks, _ptr(self.block_end),
+                                                        C.byref(self._t)))
+
+    def set(self, block_rank, scale, coef=None, V=None, ld=None, pad_value: float = 0.0):
+        """hipfact_block_term_set: block_rank (nblocks), scale (nblocks), coef (nblocks x rank), V (n x rank, host: it
+        is uploaded column-major with leading dimension ld >= n, the rows n .. ld - 1 holding pad_value).  V = None:
+        rank 0."""
+        hip = C.CDLL("libamdhip64.so")
+        br = np.ascontiguousarray(block_rank, dtype=np.int32)
+        sc = np.ascontiguousarray(scale, dtype=np.float64)
+        if br.size != self.nblocks or sc.size != self.nblocks:
+            raise ValueError("BlockTerm.set: one block_rank and one scale per block")
+        rank, cf, cols, fresh = 0, None, np.empty(0), C.c_void_p()
+        ld = self.n if ld is None else int(ld)
+        if V is not None:
+            V = np.asarray(V, dtype=np.float64)
+            if V.ndim != 2 or V.shape[0] != self.n:
+                raise ValueError(f"BlockTerm.set: V must be n x rank with n = {self.n}")
+            rank = V.shape[1]
+            cf = np.ascontiguousarray(coef, dtype=np.float64)
+            if cf.size != self.nblocks * rank:
+                raise ValueError("BlockTerm.set: coef must be nblocks x rank")
+            cols = np.full((rank, max(ld, self.n)), pad_value, dtype=np.float64)
+            cols[:, :self.n] = V.T
+            if hip.hipMalloc(C.byref(fresh), C.c_size_t(max(cols.nbytes, 16))) != 0:
+                raise MemoryError("hipMalloc")
+            if cols.nbytes and hip.hipMemcpy(fresh, _ptr(cols), C.c_size_t(cols.nbytes), 1) != 0:
+                hip.hipFree(fresh)
+                raise RuntimeError("hipMemcpy")
+        rc = self._lib.hipfact_block_term_set(self._t, rank, _ptr(br), _ptr(sc), _ptr(cf), fresh, ld)
+        if rc != 0:
+            if fresh:
+                hip.hipFree(fresh)
+            self._fact._check(rc)
+        self._lib.hipfact_synchronize(self._fact._h)  # (a queued product may still read the old V)
+        if self._dV:
+            hip.hipFree(self._dV)
+        self._dV, self._cols = fresh, cols
+
+    def device_V(self):
+        """(V as it stands on the device, V as it was uploaded): rank x ld each"""
+        after = np.empty_like(self._cols)
+        if self._cols.nbytes:
+            self._lib.hipfact_synchronize(self._fact._h)
+            if C.CDLL("libamdhip64.so").hipMemcpy(_ptr(after), self._dV, C.c_size_t(after.nbytes), 2) != 0:
+                raise RuntimeError("hipMemcpy")
+        return after, self._cols
+
+    def free(self):
+        if self._t:
+            self._lib.hipfact_block_term_free(C.byref(self._t))
+            self._t = C.c_void_p()
+        if self._dV:
+            C.CDLL("libamdhip64.so").hipFree(self._dV)
+            self._dV = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 LSQR_PROD = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double))
