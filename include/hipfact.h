@@ -956,7 +956,7 @@ int hipfact_hess_apply_device_ex(hipfact_handle* h, const hipfact_hess_op* op /*
                                  const double* d_x, double* d_y);
 
 /* Pure host function: sizeof of a struct of this header by name ("hipfact_device_prod", "hipfact_hess_op",
- * "hipfact_low_rank", "hipfact_tr_extra"), for the mirrors of other languages; 0 for a name it does not know. */
+ * "hipfact_low_rank", "hipfact_tr_extra", "hipfact_qn_info"), for the mirrors of other languages; 0 for a name it does not know. */
 size_t hipfact_debug_sizeof(const char* name);
 
 /* For callers without a HIP runtime of their own (the shim keeps V of its quasi-Newton term this way): a device copy of
@@ -1056,6 +1056,87 @@ int hipfact_debug_block_values(int n, int nblocks, int rank, const int* block_ra
 int hipfact_debug_qn_block_terms(int kind, int n, int nblocks, const int* block_end, const int* npairs, int memory,
                                  const double* S, const double* Y, double* scale, double* V, double* coef,
                                  int* block_rank);
+
+/* ---- the quasi-Newton term built on the device from pairs kept in HBM ------ */
+
+/* hipfact_debug_qn_terms (qn_terms.h) turns the stored pairs (s_j, y_j) into scale, V and coef by a recursion on the
+ * host: O(pairs^2 n), every stored n-vector touched about `pairs` times, and V then goes up to the device.  The ring
+ * keeps the pairs in HBM and builds the same term there.  Every column of the recursion lies in the span of X = [S Y]
+ * (n x 2L, L <= 16 used pairs), so with the Gram matrix G = X' X every scalar of the recursion is a small product with
+ * G and every column is X c: the device forms G in one pass over the pairs (k_qn_gram on the f64 matrix cores, per-
+ * workgroup partials, k_qn_gram_totals), G (8 KB at most) comes down - the build's only synchronisation in front of its
+ * end -, the host runs the recursion in coefficient space (csrc/qn_gram_rule.h: the formulas, thresholds and leave-out
+ * rules of qn_terms.h), the coefficients C (2L x rank) go up and the device writes V = X C in a second pass
+ * (k_qn_combine).
+ * The ring is an object of the handle, like hipfact_block_term; no factorisation is needed.  It owns S and Y
+ * (n x memory) and V (n x 2 memory) in HBM, column-major with ld = n rounded up to even.  The slots are circular: a
+ * push overwrites the oldest pair, nothing is moved.
+ * _create: kind HIPFACT_QN_SR1 / _BFGS / _DAMPED_BFGS (qn_terms.h: 0 / 1 / 2), memory 1 .. 16, n >= 1.  HIPFACT_EINVAL
+ *   for a bad n, kind or memory and a NULL handle or out (message in hipfact_last_error, of NULL without a handle);
+ *   HIPFACT_ENOMEM when the buffers cannot be had - the handle stays usable.
+ * _push_device: the pair from device vectors of n doubles, queued on the handle's stream; it does not block, the
+ *   vectors must stay as they are until the stream has passed the copy.  _push: the pair from host vectors; the call
+ *   waits for the upload.  HIPFACT_EINVAL for a NULL ring or vector.  The values are not looked at: a non-finite pair
+ *   is found by the build.
+ * _reset: forgets the pairs.  HIPFACT_EINVAL for a NULL ring.
+ * _build: fills *lr with the ring's d_V, ld, the rank and coef pointing at a host array of the ring - valid until the
+ *   next _build, _reset or _free of this ring - and *info (nullable): the pairs used, the rank, bit j of damped /
+ *   skipped when used pair j (0 = oldest) was damped / left out, and the scale of B_0 = scale I, which the caller adds
+ *   to op.shift.  B = scale I + V diag(coef) V'.  hipfact_tr_solve_lr, hipfact_tr_solve_device,
+ *   hipfact_hess_lr_apply_device, hipfact_hess_apply_device_ex and hipfact_projected_eig* take lr unchanged (and check
+ *   n against the plan there, as ever).  Without pairs: scale 1, rank 0.  The build is ordered on the handle's stream
+ *   behind the solves already queued that read the old V, and it blocks.  HIPFACT_EINVAL for a NULL ring or lr, and for
+ *   a G that is not finite (an overflowing or non-finite pair): the pairs stay, the caller may _reset.
+ * _gram: the G of the last build (2 used x 2 used doubles, column-major; rows / columns 0 .. used - 1 are S, the others
+ *   Y).  HIPFACT_ESTATE when there was a push or reset since the last build, HIPFACT_EINVAL for a NULL ring or G.
+ * _free: the lifetime rules of hipfact_block_term_free (it waits for the handle's stream; the ring holds a reference to
+ *   its handle).
+ * Determinism: the workgroups of k_qn_gram and their row ranges follow from n alone (hipfact_debug_qn_gram_shape), a
+ * wave takes the 4-row steps of its tile in a fixed order, the waves and then the workgroups are added in a fixed order,
+ * G is mirrored (symmetric bit for bit), V = X C sums its columns in ascending order by fused multiply-adds: the same
+ * pushes in the same order give the same bits of G, V, coef and scale.
+ * Accuracy: entrywise |dG| <= n 2^-52 |X|' |X| and |dV| <= (2L + 1) 2^-52 |X| |C|.  Against a long-double recursion the
+ * dense B of the Gram route is as accurate as that of qn_terms.h (EXPERIMENTS.md, "Quasi-Newton ring").
+ * Info "qn_ring_pushes": pairs pushed into rings of the handle; "qn_ring_builds": builds; "qn_ring_rank": the rank of
+ * the last one.  There is no option.
+ * When it pays (scripts/qn_ring_probe.py, profiles/qn_ring_probe.txt; wall time of one update with a full ring, fresh
+ * processes, against hipfact_debug_qn_terms on the host + hipfact_device_upload of V): always, from n = 1e5 on.  At
+ * n = 1e5 the update is 0.06 - 0.10 ms with the pair in HBM (0.15 - 0.20 ms with the two host vectors uploaded) against
+ * 2.3 - 2.8 ms on the host route with 5 pairs and 11 - 19 ms with 16; at n = 1e6 0.13 - 0.32 ms (0.48 - 0.66 ms) against
+ * 23 - 31 ms and 147 - 239 ms.  On the host route the term cost as much as 20 to 150 CG iterations of the solve it
+ * feeds (0.12 ms each); on the device it costs less than three.  The two passes run at 2.6 TB/s at n = 1e6, memory 16. */
+typedef struct hipfact_qn_ring hipfact_qn_ring;
+typedef struct hipfact_qn_info
+{
+  int used, rank;           /* pairs used (<= memory), columns of V */
+  unsigned damped, skipped; /* bit j: used pair j (0 = oldest) was damped / left out */
+  double scale;             /* B_0 = scale I: the caller adds it to op.shift */
+} hipfact_qn_info;
+int hipfact_qn_ring_create(hipfact_handle* h, int n, int kind /* HIPFACT_QN_* */, int memory /* 1..16 */,
+                           hipfact_qn_ring** out);
+int hipfact_qn_ring_push_device(hipfact_qn_ring* R, const double* d_s, const double* d_y);
+int hipfact_qn_ring_push(hipfact_qn_ring* R, const double* s, const double* y);
+int hipfact_qn_ring_reset(hipfact_qn_ring* R);
+int hipfact_qn_ring_build(hipfact_qn_ring* R, hipfact_low_rank* lr /* out */, hipfact_qn_info* info /* nullable */);
+int hipfact_qn_ring_gram(hipfact_qn_ring* R, double* G /* host, 2 used x 2 used, column-major */);
+int hipfact_qn_ring_free(hipfact_qn_ring** R);
+
+/* Pure host functions (no GPU needed).  hipfact_debug_qn_gram_terms: the dense host executor of the route above, with
+ * the arguments of hipfact_debug_qn_terms and `skipped` beside `damped` (both nullable) - G by plain fp64 loops in index
+ * order, the rule, V = X C; HIPFACT_EINVAL for what hipfact_debug_qn_terms refuses and for a G that is not finite.
+ * hipfact_debug_qn_gram_rule: the rule alone on a caller's G (2L x 2L, column-major, leading dimension 2L; C likewise,
+ * column k = the coefficients of V_k); HIPFACT_EINVAL for an unknown kind, L outside 0 .. 16, a NULL array with L > 0 or
+ * a non-finite G.  hipfact_debug_qn_gram_shape: out[0] = the tile rows of k_qn_gram, out[1] = the rows per workgroup,
+ * out[2] = the workgroups for n rows - workgroup b owns the rows [b out[1], min((b + 1) out[1], n)); they are part of the
+ * summation order; HIPFACT_EINVAL for n < 0 or a NULL out.  hipfact_debug_qn_ring_buffers (tests): the ring's device
+ * buffers S, Y (ld x memory), V (ld x 2 memory), ld, and slots[j] = the column of used pair j, oldest first (memory
+ * ints, -1 behind the used ones); every out pointer is nullable. */
+int hipfact_debug_qn_gram_terms(int kind, int n, int npairs, int memory, const double* S, const double* Y, double* scale,
+                                double* V, double* coef, int* rank, unsigned* damped, unsigned* skipped);
+int hipfact_debug_qn_gram_rule(int kind, int L, const double* G, double* scale, double* C, double* coef, int* rank,
+                               unsigned* damped, unsigned* skipped);
+int hipfact_debug_qn_gram_shape(int n, int* out);
+int hipfact_debug_qn_ring_buffers(hipfact_qn_ring* R, void** d_S, void** d_Y, void** d_V, long long* ld, int* slots);
 
 /* ---- extreme eigenpairs of the projected Hessian (Lanczos) ---------------- */
 

@@ -64,8 +64,15 @@ struct SleqpHipfactTR
   int lr_rank;
   long long lr_ld;
   void* lr_dev_V;
+  int lr_dev_borrowed; /* lr_dev_V is the V of qn_ring, not a buffer of its own */
   double lr_coef[LR_MAX_RANK];
   double lr_scale;
+
+  /* sleqp_hipfact_tr_set_qn_device: the pairs of the single-block route live in a ring on the handle, which builds the
+   * term on the device (hipfact_qn_ring; created at the first push, for that push's kind) */
+  int qn_device;
+  hipfact_qn_ring* qn_ring;
+  int qn_ring_kind;
 
   /* the stored pairs (num_variables x QN_MEMORY each, column-major, oldest first) and the terms built from them */
   int qn_len;
@@ -126,6 +133,18 @@ pattern_hash(const SleqpMat* matrix)
   return h;
 }
 
+/* the device copy of V of the low-rank term: a buffer of the solver's, or the V of the ring (which stays) */
+static void
+low_rank_release(SleqpHipfactTR* solver)
+{
+  if (solver->lr_dev_V && !solver->lr_dev_borrowed)
+  {
+    hipfact_device_release(solver->handle, &solver->lr_dev_V);
+  }
+  solver->lr_dev_V        = NULL;
+  solver->lr_dev_borrowed = 0;
+}
+
 /* the block term and its V live on the bound handle */
 static void
 block_term_drop(SleqpHipfactTR* solver)
@@ -156,9 +175,10 @@ hipfact_tr_free(void** star)
     hipfact_spmat_free(&solver->lsq_jac);
   }
 
-  if (solver->lr_dev_V)
+  low_rank_release(solver);
+  if (solver->qn_ring)
   {
-    hipfact_device_release(solver->handle, &solver->lr_dev_V);
+    hipfact_qn_ring_free(&solver->qn_ring);
   }
 
   block_term_drop(solver);
@@ -487,10 +507,7 @@ low_rank_store(SleqpHipfactTR* solver, int rank, const double* V, long long ld, 
 {
   const int num_variables = sleqp_problem_num_vars(solver->problem);
 
-  if (solver->lr_dev_V)
-  {
-    hipfact_device_release(solver->handle, &solver->lr_dev_V);
-  }
+  low_rank_release(solver);
 
   solver->lr_active = 1;
   solver->lr_rank   = rank;
@@ -533,10 +550,7 @@ sleqp_hipfact_tr_set_low_rank(SleqpHipfactTR* solver,
 {
   if (rank == 0)
   {
-    if (solver->lr_dev_V)
-    {
-      hipfact_device_release(solver->handle, &solver->lr_dev_V);
-    }
+    low_rank_release(solver);
     solver->lr_active = 0;
     solver->lr_rank   = 0;
     solver->lr_scale  = 0.;
@@ -718,12 +732,110 @@ SLEQP_RETCODE
 sleqp_hipfact_tr_reset_pairs(SleqpHipfactTR* solver)
 {
   solver->qn_len = 0;
+  if (solver->qn_ring)
+  {
+    hipfact_qn_ring_reset(solver->qn_ring);
+  }
   for (int b = 0; b < solver->hs_blocks; ++b)
   {
     solver->hs_len[b] = 0;
   }
   block_term_drop(solver);
   return sleqp_hipfact_tr_set_low_rank(solver, 0, NULL, 0, NULL, 0.);
+}
+
+SLEQP_RETCODE
+sleqp_hipfact_tr_low_rank_term(SleqpHipfactTR* solver, hipfact_low_rank* lr, double* scale)
+{
+  if (!lr || !scale)
+  {
+    sleqp_raise(SLEQP_ILLEGAL_ARGUMENT, "hipfact TR solver: no place for the low-rank term");
+  }
+
+  lr->rank = solver->lr_active ? solver->lr_rank : 0;
+  lr->ld   = solver->lr_ld;
+  lr->d_V  = (const double*)solver->lr_dev_V;
+  lr->coef = solver->lr_coef;
+  *scale   = solver->lr_active ? solver->lr_scale : 0.;
+  return SLEQP_OKAY;
+}
+
+SLEQP_RETCODE
+sleqp_hipfact_tr_set_qn_device(SleqpHipfactTR* solver, int on)
+{
+  if ((on != 0) == (solver->qn_device != 0))
+  {
+    return SLEQP_OKAY;
+  }
+
+  /* the pairs of the one route are not those of the other */
+  SLEQP_CALL(sleqp_hipfact_tr_reset_pairs(solver));
+  if (solver->qn_ring)
+  {
+    hipfact_qn_ring_free(&solver->qn_ring);
+  }
+  solver->qn_device = on != 0;
+  return SLEQP_OKAY;
+}
+
+/* the single-block push with the pairs in a ring on the handle: the two n-vectors go up, the term is built there */
+static SLEQP_RETCODE
+push_pair_device(SleqpHipfactTR* solver, int kind, const SleqpVec* step_diff, const SleqpVec* grad_diff)
+{
+  const int num_variables = sleqp_problem_num_vars(solver->problem);
+
+  if (solver->qn_ring && solver->qn_ring_kind != kind)
+  {
+    /* (a ring is of one kind: the pairs pushed under the other kind leave with it) */
+    low_rank_release(solver);
+    solver->lr_active = 0;
+    solver->lr_rank   = 0;
+    hipfact_qn_ring_free(&solver->qn_ring);
+  }
+
+  int status = HIPFACT_OK;
+
+  if (!solver->qn_ring)
+  {
+    status               = hipfact_qn_ring_create(solver->handle, num_variables, kind, QN_MEMORY, &solver->qn_ring);
+    solver->qn_ring_kind = kind;
+  }
+
+  /* (the first column of the host arrays stages the dense vectors) */
+  SLEQP_CALL(sleqp_vec_to_raw(step_diff, solver->qn_S));
+  SLEQP_CALL(sleqp_vec_to_raw(grad_diff, solver->qn_Y));
+
+  hipfact_low_rank lr;
+  hipfact_qn_info info;
+
+  if (status == HIPFACT_OK)
+  {
+    status = hipfact_qn_ring_push(solver->qn_ring, solver->qn_S, solver->qn_Y);
+  }
+  if (status == HIPFACT_OK)
+  {
+    status = hipfact_qn_ring_build(solver->qn_ring, &lr, &info);
+  }
+  if (status != HIPFACT_OK)
+  {
+    sleqp_raise(SLEQP_INTERNAL_ERROR, "Caught hipfact error <%d> (%s)", status, hipfact_last_error(solver->handle));
+  }
+
+  low_rank_release(solver);
+  solver->lr_active = 1;
+  solver->lr_rank   = lr.rank;
+  solver->lr_ld     = lr.ld;
+  solver->lr_scale  = info.scale;
+  for (int k = 0; k < lr.rank; ++k)
+  {
+    solver->lr_coef[k] = lr.coef[k];
+  }
+  if (lr.rank > 0)
+  {
+    solver->lr_dev_V        = (void*)lr.d_V;
+    solver->lr_dev_borrowed = 1;
+  }
+  return SLEQP_OKAY;
 }
 
 SLEQP_RETCODE
@@ -755,6 +867,11 @@ sleqp_hipfact_tr_push_pair(SleqpHipfactTR* solver, int kind, const SleqpVec* ste
   if (solver->hs_blocks > 0)
   {
     return push_pair_blocks(solver, kind, step_diff, grad_diff);
+  }
+
+  if (solver->qn_device && num_variables > 0)
+  {
+    return push_pair_device(solver, kind, step_diff, grad_diff);
   }
 
   if (solver->qn_len == QN_MEMORY)
@@ -887,9 +1004,15 @@ sleqp_hipfact_tr_bind(SleqpHipfactTR* solver, struct hipfact_handle* handle)
   if (solver->lr_dev_V)
   {
     /* lives on the old handle's device; the pairs stay, the next push rebuilds the term */
-    hipfact_device_release(solver->handle, &solver->lr_dev_V);
+    low_rank_release(solver);
     solver->lr_active = 0;
     solver->lr_rank   = 0;
+  }
+
+  if (solver->qn_ring)
+  {
+    /* the ring lives on the old handle, and its pairs with it: the next push starts a new one */
+    hipfact_qn_ring_free(&solver->qn_ring);
   }
 
   /* likewise the block term: the rings stay, the next push builds it on the new handle */

@@ -11,6 +11,7 @@
 #endif
 
 struct hipfact_handle;
+struct hipfact_low_rank;
 
 /* Control block of the solver (owned by the SleqpTRSolver, valid until it is released). */
 typedef struct SleqpHipfactTR SleqpHipfactTR;
@@ -79,6 +80,24 @@ sleqp_hipfact_tr_push_pair(SleqpHipfactTR* ctl, int kind, const SleqpVec* step_d
 SLEQP_WARNUNUSED
 SLEQP_RETCODE
 sleqp_hipfact_tr_reset_pairs(SleqpHipfactTR* ctl);
+
+/* Opt-in: with on != 0 sleqp_hipfact_tr_push_pair keeps the pairs of ONE quasi-Newton matrix over all variables in a
+ * ring on the bound handle and builds the term there (hipfact_qn_ring: the two n-vectors go up, the Gram matrix of the
+ * pairs comes down, V is written on the device) instead of running qn_terms.h on the host and uploading V.  The term is
+ * the same up to rounding (the tests of the ring state the bound), not bit for bit.  A change of the switch drops the
+ * pairs kept so far; so does a push of another kind than the ring's, and binding another handle (the ring lives on the
+ * handle).  The block-structured route (sleqp_hipfact_tr_set_hess_struct) stays on the host either way.  Default: off -
+ * the bits of the host route. */
+SLEQP_WARNUNUSED
+SLEQP_RETCODE
+sleqp_hipfact_tr_set_qn_device(SleqpHipfactTR* ctl, int on);
+
+/* The low-rank term the solver holds - set explicitly or built from the pushed pairs on either route - as the C ABI takes
+ * it, and its scale (the part of the shift it stands for); rank 0 and scale 0 without one.  d_V and coef belong to the
+ * solver: valid until the next call that sets, pushes, resets or binds. */
+SLEQP_WARNUNUSED
+SLEQP_RETCODE
+sleqp_hipfact_tr_low_rank_term(SleqpHipfactTR* ctl, struct hipfact_low_rank* lr, double* scale);
 
 /* Optional: the block structure of the function's Hessian, as plain ints - what sleqp_hess_struct_num_blocks and
  * sleqp_hess_struct_block_range hand a caller: block b covers the variables [block_ends[b-1], block_ends[b]), the ends

@@ -50,6 +50,9 @@ SYMBOLS = [
     "hipfact_block_term_create", "hipfact_block_term_set", "hipfact_block_term_free", "hipfact_tr_solve_blocks",
     "hipfact_tr_solve_device_blocks", "hipfact_hess_apply_device_blocks", "hipfact_debug_block_items",
     "hipfact_debug_qn_block_terms", "hipfact_debug_block_values",
+    "hipfact_qn_ring_create", "hipfact_qn_ring_push_device", "hipfact_qn_ring_push", "hipfact_qn_ring_reset",
+    "hipfact_qn_ring_build", "hipfact_qn_ring_gram", "hipfact_qn_ring_free", "hipfact_debug_qn_gram_terms",
+    "hipfact_debug_qn_gram_rule", "hipfact_debug_qn_gram_shape", "hipfact_debug_qn_ring_buffers",
     "hipfact_plan_free", "hipfact_plan_error", "hipfact_plan_array", "hipfact_plan_scalar",
 ]
 
@@ -175,6 +178,21 @@ def load() -> C.CDLL:
         lib.hipfact_debug_block_items.argtypes = [ci, ci, vp, vp, ci, vp, vp]
         lib.hipfact_debug_block_values.argtypes = [ci, ci, ci, vp, vp, vp, ci, C.c_longlong]
         lib.hipfact_debug_qn_block_terms.argtypes = [ci, ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "hipfact_qn_ring_create"):
+        lib.hipfact_qn_ring_create.argtypes = [vp, ci, ci, ci, C.POINTER(vp)]
+        lib.hipfact_qn_ring_push_device.argtypes = [vp, vp, vp]
+        lib.hipfact_qn_ring_push.argtypes = [vp, vp, vp]
+        lib.hipfact_qn_ring_reset.argtypes = [vp]
+        lib.hipfact_qn_ring_build.argtypes = [vp, vp, vp]
+        lib.hipfact_qn_ring_gram.argtypes = [vp, vp]
+        lib.hipfact_qn_ring_free.argtypes = [C.POINTER(vp)]
+        lib.hipfact_debug_qn_gram_terms.argtypes = [ci, ci, ci, ci, vp, vp, C.POINTER(cd), vp, vp, C.POINTER(ci),
+                                                    C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
+        lib.hipfact_debug_qn_gram_rule.argtypes = [ci, ci, vp, C.POINTER(cd), vp, vp, C.POINTER(ci), C.POINTER(C.c_uint),
+                                                   C.POINTER(C.c_uint)]
+        lib.hipfact_debug_qn_gram_shape.argtypes = [ci, vp]
+        lib.hipfact_debug_qn_ring_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                                      C.POINTER(C.c_longlong), vp]
     if hasattr(lib, "hipfact_projected_eig"):
         lib.hipfact_projected_eig_device.argtypes = [vp, vp, vp, ci, vp, vp, vp]
         lib.hipfact_projected_eig.argtypes = [vp, vp, vp, ci, vp, vp, vp]

@@ -811,6 +811,7 @@ size_t hipfact_debug_sizeof(const char* name) {
   if (!strcmp(name, "hipfact_hess_op")) return sizeof(hipfact_hess_op);
   if (!strcmp(name, "hipfact_low_rank")) return sizeof(hipfact_low_rank);
   if (!strcmp(name, "hipfact_tr_extra")) return sizeof(hipfact_tr_extra);
+  if (!strcmp(name, "hipfact_qn_info")) return sizeof(hipfact_qn_info);
   return 0;
 }
 

@@ -518,6 +518,7 @@ int hipfact_get_info(const hipfact_handle* h, const char* name, double* value) {
   INFO("hess_op_solves", h->hess_op_solves) INFO("hess_op_products", h->hess_op_products)
   INFO("hess_lr_products", h->hess_lr_products) INFO("hess_lr_rank", h->hess_lr_rank)
   INFO("hess_blk_products", h->hess_blk_products) INFO("hess_blk_blocks", h->hess_blk_blocks)
+  INFO("qn_ring_pushes", h->qn_ring_pushes) INFO("qn_ring_builds", h->qn_ring_builds) INFO("qn_ring_rank", h->qn_ring_rank)
   INFO("dprod_solves", h->dprod_solves) INFO("dprod_calls", h->dprod_calls)
   INFO("spmv_last_lanes", h->spmv_last_lanes) INFO("spmv_stream_runs", (double)h->spmv_stream_runs)
   INFO("boundary_fast", h->boundary_fast) INFO("bd_count", h->bd_count) INFO("bd_stage_us", h->bd_stage_us) INFO("bd_queue_us", h->bd_queue_us) INFO("bd_rhs_us", h->bd_rhs_us) INFO("bd_device_us", h->bd_device_us) INFO("bd_d2h_us", h->bd_d2h_us) INFO("bd_wait_us", h->bd_wait_us) INFO("bd_copyout_us", h->bd_copyout_us)

@@ -5,7 +5,7 @@
 // state.  All numerics run on the device; there is no CPU fallback: without a
 // usable GPU hipfact_create fails with HIPFACT_EDEVICE.
 //
-// The host translation unit (the kernels are compiled separately: kernels_factor.hip / kernels_solve.hip / kernels_extra.hip / kernels_nullspace.hip / kernels_selinv.hip / kernels_gmres.hip / kernels_border.hip / kernels_ritz.hip, declared in the
+// The host translation unit (the kernels are compiled separately: kernels_factor.hip / kernels_solve.hip / kernels_extra.hip / kernels_nullspace.hip / kernels_selinv.hip / kernels_gmres.hip / kernels_border.hip / kernels_ritz.hip / kernels_qn.hip, declared in the
 // generated kernels_decl.h), split by role:
 //   runtime_types.inc   buffers, plan state, the handle          abi_core.inc         create .. solution (SleqpFact)
 //   runtime_plan.inc    upload of a plan, work items             abi_working_set.inc  superset plans, assemble_kkt
@@ -25,6 +25,7 @@
 //   runtime_ritz.inc    extreme eigenpairs of the projected Hessian, restarted Lanczos (ritz_rule.h) abi_ritz.inc hipfact_projected_eig[_device], _debug_ritz_*
 //                       (included by abi_ritz.inc behind abi_krylov.inc: it runs on that file's operator product)
 //   runtime_block_term.inc block-diagonal quasi-Newton term of the operator (block_term_items.h) abi_block_term.inc hipfact_block_term_*, hipfact_tr_solve[_device]_blocks, hipfact_hess_apply_device_blocks
+//   runtime_qn_ring.inc the quasi-Newton term built on the device from pairs kept in HBM (qn_gram_rule.h) abi_qn_ring.inc hipfact_qn_ring_*, _debug_qn_gram_*
 //   refine_cadence.h    refinement cadence of the single solve: passes in the graph, residual checks, deferred verdicts
 //                       (pure host rules, like xcd_place.h and multi_slices.h)
 #include <hip/hip_runtime.h>
@@ -65,6 +66,7 @@
 #include "gmres_rule.h"
 #include "border_rule.h"
 #include "ritz_rule.h"
+#include "qn_gram_rule.h"
 #include "block_term_items.h"
 #include "selinv_types.h"
 #include "selinv_host.h"
@@ -83,6 +85,7 @@
 #include "runtime_gmres.inc"
 #include "runtime_border.inc"
 #include "runtime_block_term.inc"
+#include "runtime_qn_ring.inc"
 
 extern "C" {
 #include "abi_core.inc"
@@ -97,6 +100,7 @@ extern "C" {
 #include "abi_working_set.inc"
 #include "abi_krylov.inc"
 #include "abi_block_term.inc"
+#include "abi_qn_ring.inc"
 #include "abi_ritz.inc"
 #include "abi_options.inc"
 }  // extern "C"

@@ -179,5 +179,10 @@ struct LzCtl {
               // definite), 5 iteration cap
   int kmax;
 };
+// The ring of quasi-Newton pairs (hipfact_qn_ring; kernels_qn.inc): the slot of used pair j (0 = oldest) in the circular
+// column storage of S and Y, by value with the launch
+struct QnSlots {
+  int s[16];
+};
 
 }  // namespace hipfact

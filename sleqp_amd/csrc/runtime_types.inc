@@ -489,6 +489,10 @@ struct hipfact_handle : PlanState, SingleSolveMemo {
   // blocks of the last one
   long hess_blk_products = 0;
   int hess_blk_blocks = 0;
+  // ... the pairs pushed into and the terms built from rings of quasi-Newton pairs (hipfact_qn_ring: the buffers live
+  // in the ring), and the rank of the last build
+  long qn_ring_pushes = 0, qn_ring_builds = 0;
+  int qn_ring_rank = 0;
   long hess_op_solves = 0, hess_op_products = 0;
   bool hess_op_call = false;
   // ... e = H_user x of the caller's queued product (hipfact_device_prod), n doubles, allocated on first use; calls of

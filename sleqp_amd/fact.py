@@ -693,6 +693,11 @@ class HipFact:
         variables (default: that of the factorised saddle matrix).  A new term is the identity on its blocks."""
         return BlockTerm(self, block_end, int(self.info("n")) if n is None else int(n))
 
+    def qn_ring(self, n, kind: int, memory: int = 5):
+        """hipfact_qn_ring_create: a ring of `memory` quasi-Newton pairs of n-vectors in HBM, whose term
+        scale I + V diag(coef) V' is built on the device (`QnRing.build`).  kind: QN_SR1, QN_BFGS, QN_DAMPED_BFGS."""
+        return QnRing(self, int(n), int(kind), int(memory))
+
     def _blocks_op(self, hess, gn_jac, shift, n):
         """the operator beside a block term: NULL when nothing stands beside it"""
         if hess is None and gn_jac is None and shift == 0.0:
@@ -1316,6 +1321,128 @@ class BlockTerm:
         if self._dV:
             C.CDLL("libamdhip64.so").hipFree(self._dV)
             self._dV = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class QnInfo(C.Structure):
+    """hipfact_qn_info (include/hipfact.h)"""
+    _fields_ = [("used", C.c_int), ("rank", C.c_int), ("damped", C.c_uint), ("skipped", C.c_uint), ("scale", C.c_double)]
+
+
+def qn_gram_terms(kind: int, S, Y, memory: int = 5):
+    """hipfact_debug_qn_gram_terms (no GPU): `qn_terms` by the route of the device build - the Gram matrix of the used
+    pairs, the recursion in coefficient space, V = X C.  Returns (scale, V (n x rank), coef, damped, skipped)."""
+    from . import _lib
+
+    lib = _lib.load()
+    S = np.asfortranarray(S, dtype=np.float64)
+    Y = np.asfortranarray(Y, dtype=np.float64)
+    if S.ndim != 2 or S.shape != Y.shape:
+        raise ValueError("qn_gram_terms: S and Y must be n x npairs")
+    n, npairs = S.shape
+    used = min(npairs, memory)
+    V = np.zeros((max(n, 1), 2 * max(used, 1)), order="F")
+    coef = np.zeros(2 * max(used, 1))
+    scale, rank, damped, skipped = C.c_double(), C.c_int(), C.c_uint(), C.c_uint()
+    rc = lib.hipfact_debug_qn_gram_terms(int(kind), n, npairs, int(memory), _ptr(S), _ptr(Y), C.byref(scale), _ptr(V),
+                                         _ptr(coef), C.byref(rank), C.byref(damped), C.byref(skipped))
+    if rc != 0:
+        raise ValueError(f"hipfact_debug_qn_gram_terms: {rc}")
+    r = rank.value
+    bits = lambda w: [bool(w >> j & 1) for j in range(used)]  # noqa: E731
+    return scale.value, np.ascontiguousarray(V[:n, :r]), coef[:r].copy(), bits(damped.value), bits(skipped.value)
+
+
+def qn_gram_rule(kind: int, G):
+    """hipfact_debug_qn_gram_rule (no GPU): the coefficient-space recursion on a Gram matrix G (2L x 2L) of X = [S Y].
+    Returns (scale, C (2L x rank), coef, damped, skipped) with V = X C."""
+    from . import _lib
+
+    lib = _lib.load()
+    G = np.asfortranarray(G, dtype=np.float64)
+    if G.ndim != 2 or G.shape[0] != G.shape[1] or G.shape[0] % 2:
+        raise ValueError("qn_gram_rule: G must be 2L x 2L")
+    m = G.shape[0]
+    L = m // 2
+    Cm = np.zeros((max(m, 1), max(m, 1)), order="F")
+    coef = np.zeros(max(m, 1))
+    scale, rank, damped, skipped = C.c_double(), C.c_int(), C.c_uint(), C.c_uint()
+    rc = lib.hipfact_debug_qn_gram_rule(int(kind), L, _ptr(G), C.byref(scale), _ptr(Cm), _ptr(coef), C.byref(rank),
+                                        C.byref(damped), C.byref(skipped))
+    if rc != 0:
+        raise ValueError(f"hipfact_debug_qn_gram_rule: {rc}")
+    r = rank.value
+    bits = lambda w: [bool(w >> j & 1) for j in range(L)]  # noqa: E731
+    return scale.value, np.ascontiguousarray(Cm[:m, :r]), coef[:r].copy(), bits(damped.value), bits(skipped.value)
+
+
+def qn_gram_shape(n: int) -> dict:
+    """hipfact_debug_qn_gram_shape (no GPU): the launch shape of the Gram kernel for n rows."""
+    from . import _lib
+
+    out = np.zeros(3, dtype=np.int32)
+    rc = _lib.load().hipfact_debug_qn_gram_shape(int(n), _ptr(out))
+    if rc != 0:
+        raise ValueError(f"hipfact_debug_qn_gram_shape: {rc}")
+    return {"tile": int(out[0]), "rows_per_wg": int(out[1]), "workgroups": int(out[2])}
+
+
+class QnRing:
+    """hipfact_qn_ring (include/hipfact.h): the quasi-Newton pairs of one HipFact handle in HBM and the term built from
+    them on the device.  `build` returns a dict with `lr` (a LowRankStruct for the *_lr / *_device entry points, valid
+    until the next build / reset / free), rank, coef, scale, used, damped, skipped."""
+
+    def __init__(self, fact, n: int, kind: int, memory: int):
+        self._fact = fact
+        self._lib = fact._lib
+        self.n, self.kind, self.memory = n, kind, memory
+        self._r = C.c_void_p()
+        fact._check(self._lib.hipfact_qn_ring_create(fact._h, n, kind, memory, C.byref(self._r)))
+
+    def push(self, s, y):
+        s = np.ascontiguousarray(s, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        if s.size != self.n or y.size != self.n:
+            raise ValueError(f"QnRing.push: vectors of n = {self.n}")
+        self._fact._check(self._lib.hipfact_qn_ring_push(self._r, _ptr(s), _ptr(y)))
+
+    def push_device(self, d_s_ptr: int, d_y_ptr: int):
+        self._fact._check(self._lib.hipfact_qn_ring_push_device(self._r, C.c_void_p(d_s_ptr or None),
+                                                                C.c_void_p(d_y_ptr or None)))
+
+    def reset(self):
+        self._fact._check(self._lib.hipfact_qn_ring_reset(self._r))
+
+    def build(self) -> dict:
+        lr, info = LowRankStruct(), QnInfo()
+        self._fact._check(self._lib.hipfact_qn_ring_build(self._r, C.byref(lr), C.byref(info)))
+        coef = np.ctypeslib.as_array(C.cast(lr.coef, C.POINTER(C.c_double)), shape=(max(lr.rank, 1),))[:lr.rank].copy()
+        return {"lr": lr, "rank": info.rank, "coef": coef, "scale": info.scale, "used": info.used,
+                "damped": [bool(info.damped >> j & 1) for j in range(info.used)],
+                "skipped": [bool(info.skipped >> j & 1) for j in range(info.used)]}
+
+    def gram(self, used: int) -> np.ndarray:
+        """the G of the last build, 2 used x 2 used"""
+        G = np.zeros((max(2 * used, 1), max(2 * used, 1)), order="F")
+        self._fact._check(self._lib.hipfact_qn_ring_gram(self._r, _ptr(G)))
+        return np.ascontiguousarray(G[:2 * used, :2 * used])
+
+    def buffers(self) -> dict:
+        """hipfact_debug_qn_ring_buffers: device pointers of S, Y, V, the leading dimension and the slot list"""
+        dS, dY, dV, ld = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_longlong()
+        slots = np.zeros(self.memory, dtype=np.int32)
+        self._lib.hipfact_debug_qn_ring_buffers(self._r, C.byref(dS), C.byref(dY), C.byref(dV), C.byref(ld), _ptr(slots))
+        return {"S": dS.value, "Y": dY.value, "V": dV.value, "ld": ld.value, "slots": slots}
+
+    def free(self):
+        if self._r:
+            self._lib.hipfact_qn_ring_free(C.byref(self._r))
+            self._r = C.c_void_p()
 
     def __del__(self):
         try:
