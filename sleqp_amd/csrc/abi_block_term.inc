@@ -126,18 +126,25 @@ int hipfact_block_term_free(hipfact_block_term** T) {
   return HIPFACT_OK;
 }
 
+// (the operator with the term beside it, required: what the three calls below hand to the bodies of abi_krylov.inc)
+static HessOpArgs block_term_args(const char* who, const hipfact_hess_op* op, const hipfact_block_term* T,
+                                  const hipfact_device_prod* dprod, bool device_entry) {
+  HessOpArgs a{who, op};
+  a.dp = dprod, a.T = T, a.blocks = true, a.device_entry = device_entry;
+  return a;
+}
 int hipfact_tr_solve_blocks(hipfact_handle* h, int method, const hipfact_hess_op* op, const hipfact_block_term* T,
                             const double* gradient, double trust_radius, double rel_tol, int max_iter, double* newton_step,
                             double* tr_dual, int* iterations, hipfact_tr_extra* extra) {
-  return tr_solve_op_lr(h, "hipfact_tr_solve_blocks", method, op, nullptr, gradient, trust_radius, rel_tol, max_iter,
-                        newton_step, tr_dual, iterations, extra, T, true);
+  return tr_solve_op_lr(h, block_term_args("hipfact_tr_solve_blocks", op, T, nullptr, false), method, gradient,
+                        trust_radius, rel_tol, max_iter, newton_step, tr_dual, iterations, extra);
 }
 int hipfact_tr_solve_device_blocks(hipfact_handle* h, int method, const hipfact_hess_op* op, const hipfact_block_term* T,
                                    const hipfact_device_prod* dprod, const double* d_gradient, double trust_radius,
                                    double rel_tol, int max_iter, double* d_step, double* tr_dual, int* iterations,
                                    hipfact_tr_extra* extra) {
-  return tr_solve_device_impl(h, method, op, nullptr, dprod, d_gradient, trust_radius, rel_tol, max_iter, d_step, tr_dual,
-                              iterations, extra, "hipfact_tr_solve_device_blocks", T, true);
+  return tr_solve_device_impl(h, block_term_args("hipfact_tr_solve_device_blocks", op, T, dprod, true), method,
+                              d_gradient, trust_radius, rel_tol, max_iter, d_step, tr_dual, iterations, extra);
 }
 int hipfact_hess_apply_device_blocks(hipfact_handle* h, const hipfact_hess_op* op, const hipfact_block_term* T,
                                      const hipfact_device_prod* dprod, const double* d_x, double* d_y) {
@@ -146,7 +153,7 @@ int hipfact_hess_apply_device_blocks(hipfact_handle* h, const hipfact_hess_op* o
     h->error = std::string(who) + ": called from inside a device product callback";
     return HIPFACT_EINVAL;
   }
-  return hess_op_lr_apply(h, who, op, nullptr, d_x, d_y, dprod, true, T, true);
+  return hess_op_lr_apply(h, block_term_args(who, op, T, dprod, true), d_x, d_y);
 }
 
 // the rule of block_term_items.h (pure host): the items as (class, block, first row, rows), `cap` of them at most, the

@@ -213,7 +213,43 @@ static int cg_dots(hipfact_handle* h, int n, const double* x0, const double* y0,
 #include "krylov_device.inc"
 
 // (dev_vecs: gradient and newton_step are device vectors - hipfact_tr_solve_device -; the same launches, with the upload
-// through the staging buffer and the download replaced by copies on the device)
+// through the staging buffer and the download replaced by copies on the device: the two helpers below)
+// gradient in: the caller's n doubles into d_dst - from the host through the staging buffer, or a copy on the device
+static int tr_vec_in(hipfact_handle* h, const double* src, double* d_dst, size_t nb, bool dev_vecs) {
+  if (dev_vecs) {
+    HCHECK(h, hipMemcpyAsync(d_dst, src, nb, hipMemcpyDeviceToDevice, h->stream));
+  } else {
+    memcpy(h->h_stage.p, src, nb);
+    HCHECK(h, hipMemcpyAsync(d_dst, h->h_stage.p, nb, hipMemcpyHostToDevice, h->stream));
+  }
+  return HIPFACT_OK;
+}
+// step out: the caller's n doubles from d_src (NULL: the zero step of a loop that ran no iteration - nothing to judge).
+// check_info synchronises, and a timed-out sweep invalidates the step: on the device it stands in front of the copy, to
+// the host behind the copy into staging, whose wait it is.
+static int tr_step_out(hipfact_handle* h, const double* d_src, double* step, size_t nb, bool dev_vecs) {
+  hipStream_t st = h->stream;
+  int rc;
+  if (!dev_vecs) {
+    if (!d_src) {
+      memset(step, 0, nb);
+      return HIPFACT_OK;
+    }
+    HCHECK(h, hipMemcpyAsync(h->h_stage.p, d_src, nb, hipMemcpyDeviceToHost, st));
+    if ((rc = check_info(h, Phase::solve))) return rc;
+    memcpy(step, h->h_stage.p, nb);
+    return HIPFACT_OK;
+  }
+  if (!d_src) {
+    HCHECK(h, hipMemsetAsync(step, 0, nb, st));
+  } else {
+    if ((rc = check_info(h, Phase::solve))) return rc;
+    HCHECK(h, hipMemcpyAsync(step, d_src, nb, hipMemcpyDeviceToDevice, st));
+  }
+  HCHECK(h, hipStreamSynchronize(st));
+  return HIPFACT_OK;
+}
+
 static int steihaug_impl(hipfact_handle* h, const HessOp& op, const double* gradient, double trust_radius,
                          double rel_tol, int max_iter, double* newton_step, double* tr_dual, int* iterations,
                          bool dev_vecs = false) {
@@ -239,12 +275,8 @@ static int steihaug_impl(hipfact_handle* h, const HessOp& op, const double* grad
   double* Bd = d + n;
   double* grad = Bd + n;
   HCHECK(h, hipStreamSynchronize(st));
-  if (!dev_vecs) memcpy(h->h_stage.p, gradient, nb);
   HCHECK(h, hipMemsetAsync(h->d_cg_b.p, 0, (size_t)N * sizeof(double), st));
-  if (dev_vecs)
-    HCHECK(h, hipMemcpyAsync(r, gradient, nb, hipMemcpyDeviceToDevice, st));
-  else
-    HCHECK(h, hipMemcpyAsync(r, h->h_stage.p, nb, hipMemcpyHostToDevice, st));
+  if ((rc = tr_vec_in(h, gradient, r, nb, dev_vecs))) return rc;
   HCHECK(h, hipMemcpyAsync(grad, r, nb, hipMemcpyDeviceToDevice, st));
   HCHECK(h, hipMemsetAsync(z, 0, nb, st));
   const int vb = nblocks(n);
@@ -359,16 +391,7 @@ static int steihaug_impl(hipfact_handle* h, const HessOp& op, const double* grad
     *tr_dual = comb < 0.0 ? (-comb) / rad_sq : 0.0;
   }
   HCHECK(h, hipGetLastError());
-  if (dev_vecs) {
-    if ((rc = check_info(h, Phase::solve))) return rc;  // synchronises; a timed-out sweep invalidates the step
-    HCHECK(h, hipMemcpyAsync(newton_step, z, nb, hipMemcpyDeviceToDevice, st));
-    HCHECK(h, hipStreamSynchronize(st));
-    if (iterations) *iterations = it;
-    return HIPFACT_OK;
-  }
-  HCHECK(h, hipMemcpyAsync(h->h_stage.p, z, nb, hipMemcpyDeviceToHost, st));
-  if ((rc = check_info(h, Phase::solve))) return rc;  // synchronises; a timed-out sweep invalidates the step
-  memcpy(newton_step, h->h_stage.p, nb);
+  if ((rc = tr_step_out(h, z, newton_step, nb, dev_vecs))) return rc;
   if (iterations) *iterations = it;
   return HIPFACT_OK;
 }
@@ -461,12 +484,8 @@ static int gltr_impl(hipfact_handle* h, const HessOp& op, const double* gradient
   h->tr.ray_min = h->tr.ray_max = 1.0;
   h->tr.timed_out = false;
   if (n == 0) return HIPFACT_OK;
-  if (!dev_vecs) memcpy(h->h_stage.p, gradient, nb);
   HCHECK(h, hipMemsetAsync(h->d_lz_b.p, 0, (size_t)3 * N * sizeof(double), st));  // the tails [.; 0] stay zero
-  if (dev_vecs)
-    HCHECK(h, hipMemcpyAsync(tb[0], gradient, nb, hipMemcpyDeviceToDevice, st));
-  else
-    HCHECK(h, hipMemcpyAsync(tb[0], h->h_stage.p, nb, hipMemcpyHostToDevice, st));
+  if ((rc = tr_vec_in(h, gradient, tb[0], nb, dev_vecs))) return rc;
   std::vector<double> delta, gamma, hvec;
   double dots[3];
   bool cont = false;
@@ -477,15 +496,7 @@ static int gltr_impl(hipfact_handle* h, const HessOp& op, const double* gradient
     if ((rc = finish_solve(h, &cont))) return rc;
   } while (cont);
   const double gamma0 = dots[0] > 0.0 ? sqrt(dots[0]) : 0.0;
-  auto finish_zero = [&]() -> int {
-    if (dev_vecs) {
-      HCHECK(h, hipMemsetAsync(newton_step, 0, nb, st));
-      HCHECK(h, hipStreamSynchronize(st));
-    } else {
-      memset(newton_step, 0, nb);
-    }
-    return HIPFACT_OK;
-  };
+  auto finish_zero = [&]() -> int { return tr_step_out(h, nullptr, newton_step, nb, dev_vecs); };
   if (!(gamma0 > 0.0) || !(gamma0 < 1.7e308)) {
     if (gamma0 == 0.0) return finish_zero();
     h->error = "hipfact_tr_solve: non-finite projected gradient";
@@ -628,15 +639,7 @@ static int gltr_impl(hipfact_handle* h, const HessOp& op, const double* gradient
   hipLaunchKernelGGL(k_combine, dim3(vb), dim3(FB), 0, st, n, dim, Q, h->d_lz_coef.as<double>(), s);
   HCHECK(h, hipGetLastError());
   HCHECK(h, hipStreamSynchronize(st));
-  if (dev_vecs) {
-    if ((rc = check_info(h, Phase::solve))) return rc;  // synchronises
-    HCHECK(h, hipMemcpyAsync(newton_step, s, nb, hipMemcpyDeviceToDevice, st));
-    HCHECK(h, hipStreamSynchronize(st));
-  } else {
-    HCHECK(h, hipMemcpyAsync(h->h_stage.p, s, nb, hipMemcpyDeviceToHost, st));
-    if ((rc = check_info(h, Phase::solve))) return rc;  // synchronises
-    memcpy(newton_step, h->h_stage.p, nb);
-  }
+  if ((rc = tr_step_out(h, s, newton_step, nb, dev_vecs))) return rc;
   if (tr_dual) *tr_dual = lambda;
   if (iterations) *iterations = h->tr.timed_out ? dim : std::min(k, dim);
   return HIPFACT_OK;
@@ -681,23 +684,16 @@ int hipfact_tr_solve_ex(hipfact_handle* h, int method, hipfact_spmat* hess, hipf
   return tr_solve_run(h, method, op, gradient, trust_radius, rel_tol, max_iter, newton_step, tr_dual, iterations, extra);
 }
 
-// hipfact_tr_solve_op / hipfact_tr_solve_lr, and hipfact_hess_op_apply_device / hipfact_hess_lr_apply_device: one body
-// each, the low-rank term `lr` beside the operator or NULL (NULL or rank 0: no term - the launches and the bits of the
-// operator alone)
-// (T, blocks: the entry points of abi_block_term.inc - a block-diagonal term beside the operator, required there)
-static int no_block_term(hipfact_handle* h, const char* who) {
-  h->error = std::string(who) + ": no block term";
-  return HIPFACT_EINVAL;
-}
-static int tr_solve_op_lr(hipfact_handle* h, const char* who, int method, const hipfact_hess_op* op_in,
-                          const hipfact_low_rank* lr, const double* gradient, double trust_radius, double rel_tol,
-                          int max_iter, double* newton_step, double* tr_dual, int* iterations, hipfact_tr_extra* extra,
-                          const hipfact_block_term* T = nullptr, bool blocks = false) {
-  if (!h) return HIPFACT_EINVAL;
+// hipfact_tr_solve_op / hipfact_tr_solve_lr / hipfact_tr_solve_blocks, hipfact_hess_op_apply_device and its low-rank,
+// device and block forms, hipfact_tr_solve_device / hipfact_tr_solve_device_blocks: one body each, behind the prologue
+// they share (hess_op_enter).  What stands beside the operator comes in the HessOpArgs (a term that is NULL or of rank
+// 0: no term - the launches and the bits of the operator alone).
+static int tr_solve_op_lr(hipfact_handle* h, const HessOpArgs& a, int method, const double* gradient, double trust_radius,
+                          double rel_tol, int max_iter, double* newton_step, double* tr_dual, int* iterations,
+                          hipfact_tr_extra* extra) {
   HessOp op;
-  int rc = hess_op_from_abi(h, op_in, who, &op, lr, nullptr, false, T);  // (in front of the device: a NULL op touches none)
-  if (!rc && blocks && !T) rc = no_block_term(h, who);
-  if (rc || (rc = enter(h))) return rc;
+  int rc = hess_op_enter(h, a, &op);
+  if (rc) return rc;
   ++h->hess_op_solves;
   h->hess_op_call = true;
   rc = tr_solve_run(h, method, op, gradient, trust_radius, rel_tol, max_iter, newton_step, tr_dual, iterations, extra);
@@ -705,17 +701,13 @@ static int tr_solve_op_lr(hipfact_handle* h, const char* who, int method, const 
   return rc;
 }
 
-// (device_entry: hipfact_hess_apply_device_ex, with the queued product `dp` or NULL.  Called from inside a device product
-// callback - dprod_depth > 0 - the call is part of the product in flight: it counts nothing and leaves the flag of the
-// counting call as it is.)
-static int hess_op_lr_apply(hipfact_handle* h, const char* who, const hipfact_hess_op* op_in, const hipfact_low_rank* lr,
-                            const double* d_x, double* d_y, const hipfact_device_prod* dp = nullptr,
-                            bool device_entry = false, const hipfact_block_term* T = nullptr, bool blocks = false) {
-  if (!h) return HIPFACT_EINVAL;
+// (Called from inside a device product callback - dprod_depth > 0 - the call is part of the product in flight: it counts
+// nothing and leaves the flag of the counting call as it is.)
+static int hess_op_lr_apply(hipfact_handle* h, const HessOpArgs& a, const double* d_x, double* d_y) {
+  const char* who = a.who;
   HessOp op;
-  int rc = hess_op_from_abi(h, op_in, who, &op, lr, dp, device_entry, T);  // (in front of the device: a NULL op touches none)
-  if (!rc && blocks && !T) rc = no_block_term(h, who);
-  if (rc || (rc = enter(h))) return rc;
+  int rc = hess_op_enter(h, a, &op);
+  if (rc) return rc;
   if ((rc = require_factor(h, who))) return rc;
   // (n from the factorisation, as in the loops, whose check it shares: the vectors stand in for gradient and step)
   if ((rc = tr_args_ok(h, op, d_x, d_y, 1.0, who))) return rc;
@@ -737,16 +729,13 @@ static int hess_op_lr_apply(hipfact_handle* h, const char* who, const hipfact_he
 }
 
 // hipfact_tr_solve_device: hipfact_tr_solve_lr on device vectors, with the caller's queued product beside the operator
-static int tr_solve_device_impl(hipfact_handle* h, int method, const hipfact_hess_op* op_in, const hipfact_low_rank* lr,
-                                const hipfact_device_prod* dp, const double* d_gradient, double trust_radius,
-                                double rel_tol, int max_iter, double* d_step, double* tr_dual, int* iterations,
-                                hipfact_tr_extra* extra, const char* who = "hipfact_tr_solve_device",
-                                const hipfact_block_term* T = nullptr, bool blocks = false) {
-  if (!h) return HIPFACT_EINVAL;
+static int tr_solve_device_impl(hipfact_handle* h, const HessOpArgs& a, int method, const double* d_gradient,
+                                double trust_radius, double rel_tol, int max_iter, double* d_step, double* tr_dual,
+                                int* iterations, hipfact_tr_extra* extra) {
+  const char* who = a.who;
   HessOp op;
-  int rc = hess_op_from_abi(h, op_in, who, &op, lr, dp, true, T);
-  if (!rc && blocks && !T) rc = no_block_term(h, who);
-  if (rc || (rc = enter(h))) return rc;
+  int rc = hess_op_enter(h, a, &op);
+  if (rc) return rc;
   ++h->hess_op_solves;
   // what the loops refuse, here in their order, so that the checks of the device form stand behind it
   if ((rc = require_factor(h, who))) return rc;
@@ -775,34 +764,37 @@ static int tr_solve_device_impl(hipfact_handle* h, int method, const hipfact_hes
 int hipfact_tr_solve_op(hipfact_handle* h, int method, const hipfact_hess_op* op_in, const double* gradient,
                         double trust_radius, double rel_tol, int max_iter, double* newton_step, double* tr_dual,
                         int* iterations, hipfact_tr_extra* extra) {
-  return tr_solve_op_lr(h, "hipfact_tr_solve_op", method, op_in, nullptr, gradient, trust_radius, rel_tol, max_iter,
-                        newton_step, tr_dual, iterations, extra);
+  return tr_solve_op_lr(h, {"hipfact_tr_solve_op", op_in}, method, gradient, trust_radius, rel_tol, max_iter, newton_step,
+                        tr_dual, iterations, extra);
 }
 int hipfact_tr_solve_lr(hipfact_handle* h, int method, const hipfact_hess_op* op_in, const hipfact_low_rank* lr,
                         const double* gradient, double trust_radius, double rel_tol, int max_iter, double* newton_step,
                         double* tr_dual, int* iterations, hipfact_tr_extra* extra) {
-  return tr_solve_op_lr(h, "hipfact_tr_solve_lr", method, op_in, lr, gradient, trust_radius, rel_tol, max_iter, newton_step,
-                        tr_dual, iterations, extra);
+  return tr_solve_op_lr(h, {"hipfact_tr_solve_lr", op_in, lr}, method, gradient, trust_radius, rel_tol, max_iter,
+                        newton_step, tr_dual, iterations, extra);
 }
 
 int hipfact_hess_op_apply_device(hipfact_handle* h, const hipfact_hess_op* op_in, const double* d_x, double* d_y) {
-  return hess_op_lr_apply(h, "hipfact_hess_op_apply_device", op_in, nullptr, d_x, d_y);
+  return hess_op_lr_apply(h, {"hipfact_hess_op_apply_device", op_in}, d_x, d_y);
 }
 int hipfact_hess_lr_apply_device(hipfact_handle* h, const hipfact_hess_op* op_in, const hipfact_low_rank* lr,
                                  const double* d_x, double* d_y) {
-  return hess_op_lr_apply(h, "hipfact_hess_lr_apply_device", op_in, lr, d_x, d_y);
+  return hess_op_lr_apply(h, {"hipfact_hess_lr_apply_device", op_in, lr}, d_x, d_y);
 }
 
 int hipfact_tr_solve_device(hipfact_handle* h, int method, const hipfact_hess_op* op_in, const hipfact_low_rank* lr,
                             const hipfact_device_prod* dprod, const double* d_gradient, double trust_radius,
                             double rel_tol, int max_iter, double* d_step, double* tr_dual, int* iterations,
                             hipfact_tr_extra* extra) {
-  return tr_solve_device_impl(h, method, op_in, lr, dprod, d_gradient, trust_radius, rel_tol, max_iter, d_step, tr_dual,
-                              iterations, extra);
+  HessOpArgs a{"hipfact_tr_solve_device", op_in, lr, dprod};
+  a.device_entry = true;
+  return tr_solve_device_impl(h, a, method, d_gradient, trust_radius, rel_tol, max_iter, d_step, tr_dual, iterations, extra);
 }
 int hipfact_hess_apply_device_ex(hipfact_handle* h, const hipfact_hess_op* op_in, const hipfact_low_rank* lr,
                                  const hipfact_device_prod* dprod, const double* d_x, double* d_y) {
-  return hess_op_lr_apply(h, "hipfact_hess_apply_device_ex", op_in, lr, d_x, d_y, dprod, true);
+  HessOpArgs a{"hipfact_hess_apply_device_ex", op_in, lr, dprod};
+  a.device_entry = true;
+  return hess_op_lr_apply(h, a, d_x, d_y);
 }
 // sizeof of a struct of the ABI by name, for the mirrors of other languages (0: not a name it knows)
 size_t hipfact_debug_sizeof(const char* name) {

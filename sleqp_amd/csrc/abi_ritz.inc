@@ -11,9 +11,8 @@ extern "C++" {
 // the active factor
 static int projected_eig_enter(hipfact_handle* h, const char* who, const hipfact_hess_op* op_in, const hipfact_low_rank* lr,
                                int which, hipfact_eig_info* info, HessOp* op) {
-  if (!h) return HIPFACT_EINVAL;
-  int rc = hess_op_from_abi(h, op_in, who, op, lr);  // (in front of the device: a NULL op touches none)
-  if (rc || (rc = enter(h))) return rc;
+  int rc = hess_op_enter(h, {who, op_in, lr}, op);
+  if (rc) return rc;
   if ((rc = require_factor(h, who))) return rc;
   if (!h->plan.saddle) {
     h->error = std::string(who) + ": needs a saddle matrix [I A'; A 0] (the generic mode has no null space of a working set)";

@@ -134,6 +134,15 @@ constexpr int LR_BLOCKS = 256;   // most blocks (= partial sums per column) of k
 struct LrCoef {
   double c[LR_MAX_RANK];
 };
+// a symmetric matrix kept as its lower triangle: its rows (ptr / idx / val) and its columns (ptr2 / idx2 / val2)
+struct SymRows {
+  const int* __restrict__ ptr;
+  const int* __restrict__ idx;
+  const double* __restrict__ val;
+  const int* __restrict__ ptr2;
+  const int* __restrict__ idx2;
+  const double* __restrict__ val2;
+};
 struct HessRows {
   const int* __restrict__ hp;
   const int* __restrict__ hi;

@@ -27,10 +27,11 @@
 //   kernels_solve_multi.inc   blocked level-scheduled sweeps: 16 right-hand sides per pass over the factor panels
 //   kernels_solve_tree.inc    k_solve_tree (the whole solve in one launch), solve panels
 //   kernels_saddle.inc        row scaling, right-hand side, x update, residual, refinement verdict
-//   kernels_vector.inc        CSR row product / lane sum / block partial sums shared by the product and Krylov kernels,
-//                             Krylov vector kernels, CSR SpMV, fill_aug_jac on the device
+//   kernels_vector.inc        CSR row product / lane sum / symmetric row sum / block partial sums shared by the product
+//                             and Krylov kernels, Krylov vector kernels, CSR SpMV, fill_aug_jac on the device
 // (dense_cols.inc, krylov_device.inc, krylov_hess_op.inc and krylov_lsqr.inc carry their own kernels next to the host code that launches
-// them; the Krylov ones are built from the shared pieces of kernels_vector.inc.)
+// them; the Krylov ones are built from the shared pieces of kernels_vector.inc, and the product-with-dots kernels of
+// krylov_hess_op.inc are the loops of krylov_device.inc over the operator's rows.)
 #include <hip/hip_runtime.h>
 
 #include "device_types.h"

@@ -3,9 +3,11 @@
 // (part of the translation unit kernels_solve.hip; included from there, in this order)
 
 // ---------------------------------------------------------------------------
-// The pieces every product / Krylov kernel (here, krylov_device.inc, krylov_lsqr.inc) is built from.  Each of them
-// fixes a summation order, and the results are promised bit for bit repeatable: a kernel calls these, it does not
-// restate them.
+// The pieces every product / Krylov kernel (here, krylov_device.inc, krylov_hess_op.inc, krylov_lsqr.inc) is built
+// from.  Each of them fixes a summation order, and the results are promised bit for bit repeatable: a kernel calls
+// these, it does not restate them.  The row of a symmetric matrix from its lower triangle is row_sum(SymRows) below,
+// the row of the Hessian operator row_sum(HessRows) = hess_op_row of krylov_hess_op.inc; the product-with-dots loops
+// over the rows of either are cg_spmv_dots_rows / cg_head_rows / lz_spmv_dot_rows of krylov_device.inc.
 // ---------------------------------------------------------------------------
 
 // Lane `sub` of the LANES lanes of a row adds its share of row `row` of the CSR matrix (ptr, idx, val) times x onto
@@ -35,6 +37,17 @@ __device__ __forceinline__ double lanes_sum(double s) {
 #pragma unroll
   for (int o = LANES / 2; o > 0; o >>= 1) s += __shfl_down(s, o, LANES);
   return s;
+}
+
+// A symmetric matrix kept as its lower triangle (SymRows of kernel_types.h: the rows of the triangle, ptr / idx / val,
+// and its columns, ptr2 / idx2 / val2).  Row `row` of M x from the lane `sub` of its LANES lanes, valid in the row's
+// lane 0: the lane's share of the row of the triangle, onto it its share of the column without the diagonal, then the
+// shuffle tree - the order of k_spmv_csr in mode 2, stated once for the kernels of krylov_device.inc on an explicit
+// Hessian.
+template <int LANES>
+__device__ __forceinline__ double row_sum(const SymRows& m, int row, int sub, const double* x) {
+  const double s = csr_row_add<LANES>(0.0, row, sub, m.ptr, m.idx, m.val, x);
+  return lanes_sum<LANES>(csr_offdiag_add<LANES>(s, row, sub, m.ptr2, m.idx2, m.val2, x));
 }
 
 // block_partials / block_totals: the writer and the reader of per-workgroup partial sums
@@ -167,6 +180,8 @@ __global__ __launch_bounds__(FB) void k_spmv_csr(int nrows, const int* __restric
                                                  const double* __restrict__ x, double* __restrict__ y) {
   const int sub = threadIdx.x % LANES;
   const int rows_per_block = FB / LANES;
+  // (mode 2 is row_sum(SymRows) above with the test of ptr2 between its two walks; a call of it under that test gave
+  // another instruction stream for both modes, so the three lines stay)
   for (int row = blockIdx.x * rows_per_block + threadIdx.x / LANES; row < nrows; row += gridDim.x * rows_per_block) {
     double s = csr_row_add<LANES>(0.0, row, sub, ptr, idx, val, x);
     if (ptr2) s = csr_offdiag_add<LANES>(s, row, sub, ptr2, idx2, val2, x);

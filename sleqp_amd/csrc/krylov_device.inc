@@ -16,6 +16,9 @@
 // its solves); the residual of the last projection is checked at the end and anything else falls back to the host
 // loop.  (A whole-struct copy `CgCtl c = *ci` in a kernel makes the compiler park the struct in LDS per thread -
 // 11 KB per block, and the launch took 28 us instead of 4: the kernels read the fields they need.)
+// The three product-with-dots loops (stop test, beta and the control-block copy, row stride, partials, recurrences) are
+// stated once each, as __device__ templates over the rows of the product (cg_spmv_dots_rows, cg_head_rows,
+// lz_spmv_dot_rows); the kernels here and the _op kernels of krylov_hess_op.inc call them, they do not restate them.
 #ifdef KRYLOV_DEVICE_KERNELS
 namespace hipfact {
 
@@ -37,22 +40,18 @@ __device__ __forceinline__ void cg_ctl_copy(CgCtl* __restrict__ o, const CgCtl* 
   o->max_iter = i->max_iter;
 }
 
-// B d (symmetric product from lower storage, like k_spmv_csr in mode 2) and, on the way, the block partials of
-// d.Bd, z.d, d.d, grad.d, z.Bd: one launch instead of two
-template <int LANES>
-__global__ __launch_bounds__(FB) void k_cg_spmv_dots(int n, const CgCtl* __restrict__ c, const int* __restrict__ ptr,
-                                                     const int* __restrict__ idx, const double* __restrict__ val,
-                                                     const int* __restrict__ ptr2, const int* __restrict__ idx2,
-                                                     const double* __restrict__ val2, const double* __restrict__ d,
-                                                     const double* __restrict__ z, const double* __restrict__ grad,
-                                                     double* __restrict__ Bd, double* __restrict__ out) {
+// B d and, on the way, the block partials of d.Bd, z.d, d.d, grad.d, z.Bd: one launch instead of two.  Like the two
+// loops below it is stated ONCE, over the rows of whatever has a row_sum - an explicit Hessian (SymRows: the symmetric
+// product from lower storage) or the operator (HessRows, krylov_hess_op.inc); the kernels of both are wrappers.
+template <int LANES, class Rows>
+__device__ __forceinline__ void cg_spmv_dots_rows(int n, const CgCtl* c, const Rows R, const double* d, const double* z,
+                                                  const double* grad, double* Bd, double* out) {
   if (c->stop) return;
   const int sub = threadIdx.x % LANES;
   const int rows_per_block = FB / LANES;
   double t[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
   for (int row = blockIdx.x * rows_per_block + threadIdx.x / LANES; row < n; row += gridDim.x * rows_per_block) {
-    double s = csr_row_add<LANES>(0.0, row, sub, ptr, idx, val, d);
-    s = lanes_sum<LANES>(csr_offdiag_add<LANES>(s, row, sub, ptr2, idx2, val2, d));
+    const double s = row_sum<LANES>(R, row, sub, d);
     if (sub == 0) {
       Bd[row] = s;
       const double di = d[row], zi = z[row];
@@ -64,6 +63,15 @@ __global__ __launch_bounds__(FB) void k_cg_spmv_dots(int n, const CgCtl* __restr
     }
   }
   block_partials<5>(t, out);
+}
+template <int LANES>
+__global__ __launch_bounds__(FB) void k_cg_spmv_dots(int n, const CgCtl* __restrict__ c, const int* __restrict__ ptr,
+                                                     const int* __restrict__ idx, const double* __restrict__ val,
+                                                     const int* __restrict__ ptr2, const int* __restrict__ idx2,
+                                                     const double* __restrict__ val2, const double* __restrict__ d,
+                                                     const double* __restrict__ z, const double* __restrict__ grad,
+                                                     double* __restrict__ Bd, double* __restrict__ out) {
+  cg_spmv_dots_rows<LANES>(n, c, SymRows{ptr, idx, val, ptr2, idx2, val2}, d, z, grad, Bd, out);
 }
 
 // steihaug_collect_rayleigh (steihaug_solver.c:150-182): the Rayleigh quotient of the direction whose product has just
@@ -146,15 +154,10 @@ __global__ __launch_bounds__(FB) void k_cg_step_update1(int n, const CgCtl* __re
 // would need all of d first, i.e. a launch boundary), and every row updates its own d and B d in place.  The five
 // partials of k_cg_spmv_dots from the new vectors.  Reads `ci`, block 0 writes `co`.  (B d carries the rounding of
 // its recurrence along: the iterates agree with the four-launch form to rounding, not bit for bit.)
-template <int LANES>
-__global__ __launch_bounds__(FB) void k_cg_head(int n, const CgCtl* __restrict__ ci, CgCtl* __restrict__ co,
-                                                const double* __restrict__ part_rg, int nblk_rg, int stride,
-                                                const int* __restrict__ ptr, const int* __restrict__ idx,
-                                                const double* __restrict__ val, const int* __restrict__ ptr2,
-                                                const int* __restrict__ idx2, const double* __restrict__ val2,
-                                                const double* __restrict__ g, double* __restrict__ d,
-                                                double* __restrict__ Bd, const double* __restrict__ z,
-                                                const double* __restrict__ grad, double* __restrict__ out) {
+template <int LANES, class Rows>
+__device__ __forceinline__ void cg_head_rows(int n, const CgCtl* ci, CgCtl* co, const double* part_rg, int nblk_rg,
+                                             int stride, const Rows R, const double* g, double* d, double* Bd,
+                                             const double* z, const double* grad, double* out) {
   const bool writer = blockIdx.x == 0 && threadIdx.x == 0;
   if (ci->stop) {
     if (writer) cg_ctl_copy(co, ci);
@@ -173,8 +176,7 @@ __global__ __launch_bounds__(FB) void k_cg_head(int n, const CgCtl* __restrict__
   const int rows_per_block = FB / LANES;
   double t[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
   for (int row = blockIdx.x * rows_per_block + threadIdx.x / LANES; row < n; row += gridDim.x * rows_per_block) {
-    double s = csr_row_add<LANES>(0.0, row, sub, ptr, idx, val, g);
-    s = lanes_sum<LANES>(csr_offdiag_add<LANES>(s, row, sub, ptr2, idx2, val2, g));
+    const double s = row_sum<LANES>(R, row, sub, g);
     if (sub == 0) {
       const double bd = -1.0 * s + beta * Bd[row];
       const double di = -1.0 * g[row] + beta * d[row];
@@ -189,6 +191,17 @@ __global__ __launch_bounds__(FB) void k_cg_head(int n, const CgCtl* __restrict__
     }
   }
   block_partials<5>(t, out);
+}
+template <int LANES>
+__global__ __launch_bounds__(FB) void k_cg_head(int n, const CgCtl* __restrict__ ci, CgCtl* __restrict__ co,
+                                                const double* __restrict__ part_rg, int nblk_rg, int stride,
+                                                const int* __restrict__ ptr, const int* __restrict__ idx,
+                                                const double* __restrict__ val, const int* __restrict__ ptr2,
+                                                const int* __restrict__ idx2, const double* __restrict__ val2,
+                                                const double* __restrict__ g, double* __restrict__ d,
+                                                double* __restrict__ Bd, const double* __restrict__ z,
+                                                const double* __restrict__ grad, double* __restrict__ out) {
+  cg_head_rows<LANES>(n, ci, co, part_rg, nblk_rg, stride, SymRows{ptr, idx, val, ptr2, idx2, val2}, g, d, Bd, z, grad, out);
 }
 
 // ---- GLTR, device-controlled phase -----------------------------------------------------------------------------------
@@ -208,25 +221,29 @@ __global__ __launch_bounds__(FB) void k_cg_head(int n, const CgCtl* __restrict__
 // right-hand side and the solution of the last projection are intact (its residual is checked), the host reads
 // delta / gamma, solves the tridiagonal trust-region problem of that dimension ONCE with tridiag_tr_solve and continues
 // its own loop from there if the stop was the boundary or an indefinite T.
-template <int LANES>
-__global__ __launch_bounds__(FB) void k_lz_spmv_dot(int n, const LzCtl* __restrict__ c, const int* __restrict__ ptr,
-                                                    const int* __restrict__ idx, const double* __restrict__ val,
-                                                    const int* __restrict__ ptr2, const int* __restrict__ idx2,
-                                                    const double* __restrict__ val2, const double* __restrict__ y,
-                                                    double* __restrict__ Hy, double* __restrict__ out) {
+template <int LANES, class Rows>
+__device__ __forceinline__ void lz_spmv_dot_rows(int n, const LzCtl* c, const Rows R, const double* y, double* Hy,
+                                                 double* out) {
   if (c->stop) return;
   const int sub = threadIdx.x % LANES;
   const int rows_per_block = FB / LANES;
   double t[1] = {0.0};
   for (int row = blockIdx.x * rows_per_block + threadIdx.x / LANES; row < n; row += gridDim.x * rows_per_block) {
-    double s = csr_row_add<LANES>(0.0, row, sub, ptr, idx, val, y);
-    s = lanes_sum<LANES>(csr_offdiag_add<LANES>(s, row, sub, ptr2, idx2, val2, y));
+    const double s = row_sum<LANES>(R, row, sub, y);
     if (sub == 0) {
       Hy[row] = s;
       t[0] += y[row] * s;
     }
   }
   block_partials<1>(t, out);
+}
+template <int LANES>
+__global__ __launch_bounds__(FB) void k_lz_spmv_dot(int n, const LzCtl* __restrict__ c, const int* __restrict__ ptr,
+                                                    const int* __restrict__ idx, const double* __restrict__ val,
+                                                    const int* __restrict__ ptr2, const int* __restrict__ idx2,
+                                                    const double* __restrict__ val2, const double* __restrict__ y,
+                                                    double* __restrict__ Hy, double* __restrict__ out) {
+  lz_spmv_dot_rows<LANES>(n, c, SymRows{ptr, idx, val, ptr2, idx2, val2}, y, Hy, out);
 }
 
 __device__ __forceinline__ void lz_ctl_copy(LzCtl* __restrict__ o, const LzCtl* __restrict__ i) {
@@ -353,38 +370,51 @@ __global__ __launch_bounds__(FB) void k_lanczos_next_dev(int n, const double* __
 }  // namespace hipfact
 #else
 
-// The launches of the product-with-dots kernels, L lanes per row; they return the number of blocks (= partials).
-static int launch_cg_spmv(hipStream_t st, int L, int n, const CgCtl* c, hipfact_spmat* M, const double* d, const double* z,
+// The launches of the product-with-dots kernels through hess_rows_launch: on an explicit Hessian alone the kernel on
+// the six arrays of its lower triangle, on any other operator stage 1 and the operator form of the kernel.  The grid
+// (= the number of partials) is row_blocks(n, L, CG_BLOCKS) for all three; the Lanczos one hands it out in *nblk.
+#define SYM_ROWS_ARGS(S) (S).ptr, (S).idx, (S).val, (S).ptr2, (S).idx2, (S).val2
+static int launch_cg_spmv(hipfact_handle* h, const HessOp& op, int n, const CgCtl* c, const double* d, const double* z,
                           const double* grad, double* Bd, double* part) {
-  const int nblk = row_blocks(n, L, CG_BLOCKS);
-  with_lanes(L, [&](auto lanes) {
-    hipLaunchKernelGGL(k_cg_spmv_dots<decltype(lanes)::value>, dim3(nblk), dim3(FB), 0, st, n, c, M->tp.as<int>(),
-                       M->ti.as<int>(), M->tval.as<double>(), M->cp.as<int>(), M->ri.as<int>(), M->val.as<double>(), d, z,
-                       grad, Bd, part);
+  return hess_rows_launch(h, op, n, d, [&](auto lanes, int L, auto rows) -> int {
+    constexpr int LN = decltype(lanes)::value;
+    const dim3 grid(row_blocks(n, L, CG_BLOCKS));
+    if constexpr (std::is_same_v<decltype(rows), SymRows>)
+      hipLaunchKernelGGL(k_cg_spmv_dots<LN>, grid, dim3(FB), 0, h->stream, n, c, SYM_ROWS_ARGS(rows), d, z, grad, Bd, part);
+    else
+      hipLaunchKernelGGL(k_cg_spmv_dots_op<LN>, grid, dim3(FB), 0, h->stream, n, c, rows, d, z, grad, Bd, part);
+    return HIPFACT_OK;
   });
-  return nblk;
 }
-static int launch_cg_head(hipStream_t st, int L, int n, const CgCtl* ci, CgCtl* co, const double* part_rg, int nblk_rg,
-                          int stride, hipfact_spmat* M, const double* g, double* d, double* Bd, const double* z,
+static int launch_cg_head(hipfact_handle* h, const HessOp& op, int n, const CgCtl* ci, CgCtl* co, const double* part_rg,
+                          int nblk_rg, int stride, const double* g, double* d, double* Bd, const double* z,
                           const double* grad, double* part) {
-  const int nblk = row_blocks(n, L, CG_BLOCKS);
-  with_lanes(L, [&](auto lanes) {
-    hipLaunchKernelGGL(k_cg_head<decltype(lanes)::value>, dim3(nblk), dim3(FB), 0, st, n, ci, co, part_rg, nblk_rg, stride,
-                       M->tp.as<int>(), M->ti.as<int>(), M->tval.as<double>(), M->cp.as<int>(), M->ri.as<int>(),
-                       M->val.as<double>(), g, d, Bd, z, grad, part);
+  return hess_rows_launch(h, op, n, g, [&](auto lanes, int L, auto rows) -> int {
+    constexpr int LN = decltype(lanes)::value;
+    const dim3 grid(row_blocks(n, L, CG_BLOCKS));
+    if constexpr (std::is_same_v<decltype(rows), SymRows>)
+      hipLaunchKernelGGL(k_cg_head<LN>, grid, dim3(FB), 0, h->stream, n, ci, co, part_rg, nblk_rg, stride,
+                         SYM_ROWS_ARGS(rows), g, d, Bd, z, grad, part);
+    else
+      hipLaunchKernelGGL(k_cg_head_op<LN>, grid, dim3(FB), 0, h->stream, n, ci, co, part_rg, nblk_rg, stride, rows, g, d,
+                         Bd, z, grad, part);
+    return HIPFACT_OK;
   });
-  return nblk;
 }
-static int launch_lz_spmv(hipStream_t st, int L, int n, const LzCtl* c, hipfact_spmat* M, const double* y, double* Hy,
-                          double* part) {
-  const int nblk = row_blocks(n, L, CG_BLOCKS);
-  with_lanes(L, [&](auto lanes) {
-    hipLaunchKernelGGL(k_lz_spmv_dot<decltype(lanes)::value>, dim3(nblk), dim3(FB), 0, st, n, c, M->tp.as<int>(),
-                       M->ti.as<int>(), M->tval.as<double>(), M->cp.as<int>(), M->ri.as<int>(), M->val.as<double>(), y, Hy,
-                       part);
+static int launch_lz_spmv(hipfact_handle* h, const HessOp& op, int n, const LzCtl* c, const double* y, double* Hy,
+                          double* part, int* nblk) {
+  return hess_rows_launch(h, op, n, y, [&](auto lanes, int L, auto rows) -> int {
+    constexpr int LN = decltype(lanes)::value;
+    *nblk = row_blocks(n, L, CG_BLOCKS);
+    if constexpr (std::is_same_v<decltype(rows), SymRows>)
+      hipLaunchKernelGGL(k_lz_spmv_dot<LN>, dim3(*nblk), dim3(FB), 0, h->stream, n, c, SYM_ROWS_ARGS(rows), y, Hy, part);
+    else
+      hipLaunchKernelGGL(k_lz_spmv_dot_op<LN>, dim3(*nblk), dim3(FB), 0, h->stream, n, c, rows, y, Hy, part);
+    return HIPFACT_OK;
   });
-  return nblk;
 }
+
+#undef SYM_ROWS_ARGS
 
 // The device loops run their projections without a residual check (no host in between to continue a refinement):
 // only on a factorisation that has been judged - no correction pass in its solves
@@ -459,7 +489,6 @@ static int lz_device_phase(hipfact_handle* h, const HessOp& op, int n, double ga
   double* part = h->d_cg_dots.as<double>();
   double* part_x = part + 5 * CG_BLOCKS;
   const double* y = h->d_cg_z.as<double>();
-  const int L = hess_op_lanes(op, n);
   // (the solves below go past solve_async: its count of solves towards the dense top block of the tree is kept here)
   int rc;
   h->solves_this_factor += 2;
@@ -474,10 +503,7 @@ static int lz_device_phase(hipfact_handle* h, const HessOp& op, int n, double ga
       LzCtl* co = c + ((k + 1) & 1);
       // (an operator that is more than an explicit Hessian: t = J_r y in front, four launches per iteration)
       int nblk;
-      if (op.plain())
-        nblk = launch_lz_spmv(st, L, n, ci, op.hess, y, Hy, part);
-      else if ((rc = launch_lz_spmv_op(h, op, L, n, ci, y, Hy, part, &nblk)))
-        return rc;
+      if ((rc = launch_lz_spmv(h, op, n, ci, y, Hy, part, &nblk))) return rc;
       ++products;
       double* tn = tb[(k + 1) % 3];
       hipLaunchKernelGGL(k_lz_step, dim3(std::min(vb, 128)), dim3(FB), 0, st, n, ci, co, k, part, nblk, part_x, px.blocks,
@@ -548,16 +574,11 @@ static int cg_chunk_enqueue(hipfact_handle* h, const HessOp& op, int n, CgCtl* c
   // three launches per iteration: tests + z, r | projection | beta, d, B d (by recurrence) and the partials of the NEXT
   // iteration (k_cg_head).  The product of the first iteration was queued in front of the first chunk.
   // (an operator that is more than an explicit Hessian: t = J_r g between the projection and the head, four launches)
-  const int L = hess_op_lanes(op, n);
-  const int nblk = row_blocks(n, L, CG_BLOCKS);
+  const int nblk = row_blocks(n, hess_op_lanes(op, n), CG_BLOCKS);
   int rc;
   DotPartials rg = *rg_io;  // (in: of the projection in front of a leading head; out: of the chunk's last one)
   auto head = [&]() -> int {
-    if (op.plain()) {
-      launch_cg_head(st, L, n, c + 1, c, part2, rg.blocks, rg.stride, op.hess, g, d, Bd, z, grad, part);
-      return HIPFACT_OK;
-    }
-    return launch_cg_head_op(h, op, L, n, c + 1, c, part2, rg.blocks, rg.stride, g, d, Bd, z, grad, part);
+    return launch_cg_head(h, op, n, c + 1, c, part2, rg.blocks, rg.stride, g, d, Bd, z, grad, part);
   };
   for (int k = 0; k < iterations; ++k) {
     if ((k > 0 || head_first) && (rc = head())) return rc;
@@ -598,13 +619,7 @@ static int steihaug_device_loop(hipfact_handle* h, const HessOp& op, int n, doub
   CgCtl host;
   int rc;
   // the product B d of the first iteration (the later ones ride in k_cg_head)
-  if (op.plain()) {
-    launch_cg_spmv(st, hess_lanes(op.hess, n), n, c, op.hess, d, z, grad, Bd, h->d_cg_dots.as<double>());
-  } else {
-    int nblk;
-    if ((rc = launch_cg_spmv_op(h, op, hess_op_lanes(op, n), n, c, d, z, grad, Bd, h->d_cg_dots.as<double>(), &nblk)))
-      return rc;
-  }
+  if ((rc = launch_cg_spmv(h, op, n, c, d, z, grad, Bd, h->d_cg_dots.as<double>()))) return rc;
   const int budget = (max_iter == -1) ? (1 << 20) : max_iter + 1;
   // (a queued product of the caller's: chunks cut in front of the head, the host reads the block the tests wrote)
   const bool cut_at_head = op.dhave;

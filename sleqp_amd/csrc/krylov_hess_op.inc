@@ -9,7 +9,8 @@
 //             (k_spmv_csr, or k_spmv_stream above "spmv_stream_min" - and for a J_r with a very long row, hess_op_jx).
 //             It writes nothing but t, so the device loops queue it unconditionally - also behind a `stop`.
 //   stage 2   per row i of n, with LANES lanes (spmv_lanes of the stage's entries per row, (2 nnz(H0) + nnz(J_r)) / n),
-//             ONE running sum per lane, in this order (hess_op_row below - every kernel here calls it, none restates it):
+//             ONE running sum per lane, in this order (hess_op_row below, the row_sum of HessRows - a kernel calls it,
+//             it does not restate it: the product-with-dots kernels here are the loops of krylov_device.inc over it):
 //               0. the sum of the row's lane 0 starts from e_i = (H_user x)_i instead of 0, if the caller's queued product
 //                  is present (below),
 //               1. the lane's share of row i of the lower triangle of H0, then of column i without the diagonal - what
@@ -47,7 +48,8 @@
 // The same handle state gives the same bits on every call, and the host-driven loops (apply_hess), the device-controlled
 // loops and hipfact_hess_op_apply_device form the product of one vector with the same bits: same stage 1, same row
 // function, same lane count.  An operator that is an explicit Hessian and nothing else does not come here: it runs the
-// kernels of krylov_device.inc, bit for bit what hipfact_tr_solve_ex gives.
+// kernels of krylov_device.inc - the same loops over row_sum(SymRows) -, bit for bit what hipfact_tr_solve_ex gives;
+// hess_rows_launch below is the one place that tells the two apart.
 #ifdef KRYLOV_HESS_OP_KERNELS
 namespace hipfact {
 
@@ -71,6 +73,12 @@ __device__ __forceinline__ double hess_op_row(const HessRows& o, int row, int su
   s = lanes_sum<LANES>(s);
   if (blk >= 0) s = fma(o.bscale[blk], x[row], s);
   return fma(o.shift, x[row], s);
+}
+// (the name under which the loops of krylov_device.inc call it.  They are defined in front of this overload and find it
+// by argument-dependent lookup when they are instantiated: HessRows and this function stay in namespace hipfact.)
+template <int LANES>
+__device__ __forceinline__ double row_sum(const HessRows& o, int row, int sub, const double* x) {
+  return hess_op_row<LANES>(o, row, sub, x);
 }
 
 // stage 1b: the block partials of w_k = V_k . x, k < rank <= RC, part[RC b + k] of block b (columns rank .. RC - 1: zero)
@@ -118,23 +126,7 @@ __global__ __launch_bounds__(FB) void k_cg_spmv_dots_op(int n, const CgCtl* __re
                                                         const double* __restrict__ d, const double* __restrict__ z,
                                                         const double* __restrict__ grad, double* __restrict__ Bd,
                                                         double* __restrict__ out) {
-  if (c->stop) return;
-  const int sub = threadIdx.x % LANES;
-  const int rows_per_block = FB / LANES;
-  double t[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int row = blockIdx.x * rows_per_block + threadIdx.x / LANES; row < n; row += gridDim.x * rows_per_block) {
-    const double s = hess_op_row<LANES>(o, row, sub, d);
-    if (sub == 0) {
-      Bd[row] = s;
-      const double di = d[row], zi = z[row];
-      t[0] += di * s;
-      t[1] += zi * di;
-      t[2] += di * di;
-      t[3] += grad[row] * di;
-      t[4] += zi * s;
-    }
-  }
-  block_partials<5>(t, out);
+  cg_spmv_dots_rows<LANES>(n, c, o, d, z, grad, Bd, out);
 }
 
 // k_cg_head on the operator: beta, d = -g + beta d, B d = -(B g) + beta (B d) and the five partials of the next iteration
@@ -145,39 +137,7 @@ __global__ __launch_bounds__(FB) void k_cg_head_op(int n, const CgCtl* __restric
                                                    HessRows o, const double* __restrict__ g, double* __restrict__ d,
                                                    double* __restrict__ Bd, const double* __restrict__ z,
                                                    const double* __restrict__ grad, double* __restrict__ out) {
-  const bool writer = blockIdx.x == 0 && threadIdx.x == 0;
-  if (ci->stop) {
-    if (writer) cg_ctl_copy(co, ci);
-    return;
-  }
-  double tot[1];
-  block_totals<1>(part_rg, nblk_rg, stride, tot);
-  const double beta = tot[0] / ci->rg;
-  if (writer) {
-    cg_ctl_copy(co, ci);
-    co->beta = beta;
-    co->rg = tot[0];
-    co->it = ci->it + 1;
-  }
-  const int sub = threadIdx.x % LANES;
-  const int rows_per_block = FB / LANES;
-  double t[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int row = blockIdx.x * rows_per_block + threadIdx.x / LANES; row < n; row += gridDim.x * rows_per_block) {
-    const double s = hess_op_row<LANES>(o, row, sub, g);
-    if (sub == 0) {
-      const double bd = -1.0 * s + beta * Bd[row];
-      const double di = -1.0 * g[row] + beta * d[row];
-      Bd[row] = bd;
-      d[row] = di;
-      const double zi = z[row];
-      t[0] += di * bd;
-      t[1] += zi * di;
-      t[2] += di * di;
-      t[3] += grad[row] * di;
-      t[4] += zi * bd;
-    }
-  }
-  block_partials<5>(t, out);
+  cg_head_rows<LANES>(n, ci, co, part_rg, nblk_rg, stride, o, g, d, Bd, z, grad, out);
 }
 
 // k_lz_spmv_dot on the operator: H y and the partials of y . H y
@@ -185,18 +145,7 @@ template <int LANES>
 __global__ __launch_bounds__(FB) void k_lz_spmv_dot_op(int n, const LzCtl* __restrict__ c, HessRows o,
                                                        const double* __restrict__ y, double* __restrict__ Hy,
                                                        double* __restrict__ out) {
-  if (c->stop) return;
-  const int sub = threadIdx.x % LANES;
-  const int rows_per_block = FB / LANES;
-  double t[1] = {0.0};
-  for (int row = blockIdx.x * rows_per_block + threadIdx.x / LANES; row < n; row += gridDim.x * rows_per_block) {
-    const double s = hess_op_row<LANES>(o, row, sub, y);
-    if (sub == 0) {
-      Hy[row] = s;
-      t[0] += y[row] * s;
-    }
-  }
-  block_partials<1>(t, out);
+  lz_spmv_dot_rows<LANES>(n, c, o, y, Hy, out);
 }
 
 }  // namespace hipfact
@@ -232,9 +181,8 @@ struct HessOp {
   bool host_driven() const { return prod || (dhave && !dqueue); }
 };
 
-// lanes per row of the products with the symmetric Hessian (both triangles from lower storage)
-static int hess_lanes(const hipfact_spmat* hess, int n) { return spmv_lanes(2.0 * (double)hess->nnz / std::max(n, 1)); }
-// ... and of stage 2 of the operator: its entries per row (hess_lanes for an explicit Hessian alone)
+// lanes per row of stage 2 of the operator: its entries per row (for an explicit Hessian alone both triangles from
+// lower storage, what hipfact_spmat_mult_device gives the symmetric product)
 static int hess_op_lanes(const HessOp& op, int n) {
   const double ent = (op.hess ? 2.0 * (double)op.hess->nnz : 0.0) + (op.gn_jac ? (double)op.gn_jac->nnz : 0.0);
   // (the terms: `rank` more entries in every row, the dense one and the block-diagonal one alike)
@@ -243,17 +191,31 @@ static int hess_op_lanes(const HessOp& op, int n) {
 // blocks of k_lr_dots (= partials per column of the low-rank term): from n alone
 static int lr_blocks(long long n) { return (int)std::max(1LL, std::min<long long>(LR_BLOCKS, (n + FB - 1) / FB)); }
 
+// What an entry point that takes an operator was called with; its caller fills in by name what it has.
+struct HessOpArgs {
+  const char* who;                          // the entry point, in front of every message
+  const hipfact_hess_op* op_in = nullptr;   // the operator
+  const hipfact_low_rank* lr = nullptr;     // a low-rank term beside it (NULL or rank 0: none)
+  const hipfact_device_prod* dp = nullptr;  // the caller's queued product beside it (device entry points)
+  const hipfact_block_term* T = nullptr;    // a block-diagonal term beside it
+  bool blocks = false;                      // ... which the entry point requires (abi_block_term.inc)
+  bool device_entry = false;                // vectors on the device: dp or a term may stand for the operator
+};
+
 // The caller's hipfact_hess_op as a HessOp, or HIPFACT_EINVAL (what needs n is left to tr_args_ok)
-// (dp: the queued product of the device entry points beside it - there `in` may be NULL when dp or the term stands for
-// the operator, and a host `prod` is refused behind everything else: that caller uses the host entry points)
-static int hess_op_from_abi(hipfact_handle* h, const hipfact_hess_op* in, const char* who, HessOp* op,
-                            const hipfact_low_rank* lr = nullptr, const hipfact_device_prod* dp = nullptr,
-                            bool device_entry = false, const hipfact_block_term* T = nullptr) {
+// (device entry points: `op_in` may be NULL when dp or the term stands for the operator, and a host `prod` is refused
+// behind everything else: that caller uses the host entry points)
+static int hess_op_from_abi(hipfact_handle* h, const HessOpArgs& a, HessOp* op) {
+  const hipfact_hess_op* in = a.op_in;
+  const hipfact_low_rank* lr = a.lr;
+  const hipfact_device_prod* dp = a.dp;
+  const hipfact_block_term* T = a.T;
+  const char* who = a.who;
   const char* bad = nullptr;
   const bool term = lr && lr->rank != 0;
   static const hipfact_hess_op nothing = {nullptr, nullptr, 0.0, nullptr, nullptr};
   // (a block term stands for the operator in the host form too)
-  if (!in && ((device_entry && (dp || term)) || T)) in = &nothing;
+  if (!in && ((a.device_entry && (dp || term)) || T)) in = &nothing;
   if (!in)
     bad = "no operator";
   else if (!in->hess && !in->gn_jac && in->shift == 0.0 && !in->prod && !term && !dp && !T)
@@ -275,7 +237,7 @@ static int hess_op_from_abi(hipfact_handle* h, const hipfact_hess_op* in, const 
       for (int k = 0; k < lr->rank; ++k)
         if (!std::isfinite(lr->coef[k])) bad = "non-finite coefficient of the low-rank term";
   }
-  if (!bad && device_entry && in->prod)
+  if (!bad && a.device_entry && in->prod)
     bad = dp ? "a host product callback beside a device product" : "a host product callback: use the host entry points";
   if (bad) {
     h->error = std::string(who) + ": " + bad;
@@ -307,6 +269,18 @@ static int hess_op_from_abi(hipfact_handle* h, const hipfact_hess_op* in, const 
     op->dqueue = dp->queue_only != 0;
   }
   return HIPFACT_OK;
+}
+
+// The prologue of every entry point that takes an operator: the operator in front of the device (a NULL op touches
+// none), the refusal of a missing block term where one is required, then the handle.
+static int hess_op_enter(hipfact_handle* h, const HessOpArgs& a, HessOp* op) {
+  if (!h) return HIPFACT_EINVAL;
+  int rc = hess_op_from_abi(h, a, op);
+  if (!rc && a.blocks && !a.T) {
+    h->error = std::string(a.who) + ": no block term";
+    rc = HIPFACT_EINVAL;
+  }
+  return rc ? rc : enter(h);
 }
 
 // The caller's queued product of x, e = H_user x in the handle's n-vector for it (allocated on first use, kept with the
@@ -428,21 +402,44 @@ static void hess_op_count(hipfact_handle* h, const HessOp& op, long products) {
   }
 }
 
+// From an operator and the vector x of a product to "these rows, this many lanes, launch" - the ONE place that knows
+// which kernels an operator runs.  An explicit Hessian alone: launch(lanes, L, rows) with the SymRows of its lower
+// triangle - the kernels of krylov_device.inc, nothing queued in front.  Anything else (never a host callback): stage 1
+// of the product with x is queued, then launch(lanes, L, rows) with the HessRows of stage 2 - the kernels above.
+// `lanes` is an std::integral_constant of L; returns what stage 1 or the launch returns.
+extern "C++" {
+template <class Launch>
+static int hess_rows_launch(hipfact_handle* h, const HessOp& op, int n, const double* x, Launch&& launch) {
+  const int L = hess_op_lanes(op, n);
+  int rc = HIPFACT_OK;
+  if (op.plain()) {
+    hipfact_spmat* M = op.hess;
+    const SymRows S = {M->tp.as<int>(), M->ti.as<int>(), M->tval.as<double>(),
+                       M->cp.as<int>(), M->ri.as<int>(), M->val.as<double>()};
+    with_lanes(L, [&](auto lanes) { rc = launch(lanes, L, S); });
+    return rc;
+  }
+  HessRows R;
+  if ((rc = hess_op_stage1(h, op, n, x, &R))) return rc;
+  with_lanes(L, [&](auto lanes) { rc = launch(lanes, L, R); });
+  return rc;
+}
+}  // extern "C++"
+
 static int apply_hess(hipfact_handle* h, const HessOp& op, int n, const double* d_in, double* d_out) {
   hess_op_count(h, op, 1);
-  if (op.plain()) return hipfact_spmat_mult_device(op.hess, 2, d_in, d_out);
-  if (!op.prod) {
-    HessRows R;
-    int rc;
-    if ((rc = hess_op_stage1(h, op, n, d_in, &R))) return rc;
-    const int L = hess_op_lanes(op, n);
-    with_lanes(L, [&](auto lanes) {
-      hipLaunchKernelGGL(k_hess_op_apply<decltype(lanes)::value>, dim3(row_blocks(n, L, 8192)), dim3(FB), 0, h->stream, n,
-                         R, d_in, d_out);
+  if (!op.prod)
+    return hess_rows_launch(h, op, n, d_in, [&](auto lanes, int L, auto rows) -> int {
+      // (an explicit Hessian alone: the symmetric product of the matrix, which also leaves "spmv_last_lanes")
+      if constexpr (std::is_same_v<decltype(rows), SymRows>) {
+        return hipfact_spmat_mult_device(op.hess, 2, d_in, d_out);
+      } else {
+        hipLaunchKernelGGL(k_hess_op_apply<decltype(lanes)::value>, dim3(row_blocks(n, L, 8192)), dim3(FB), 0, h->stream, n,
+                           rows, d_in, d_out);
+        HCHECK(h, hipGetLastError());
+        return HIPFACT_OK;
+      }
     });
-    HCHECK(h, hipGetLastError());
-    return HIPFACT_OK;
-  }
   const size_t nb = (size_t)n * sizeof(double);
   HCHECK(h, h->h_hv.ensure(2 * nb + 16));
   double* hv = h->h_hv.as<double>();
@@ -476,45 +473,6 @@ static int tr_args_ok(hipfact_handle* h, const HessOp& op, const double* gradien
     h->error = std::string(who) + ": leading dimension of the low-rank term below n";
     return HIPFACT_EINVAL;
   }
-  return HIPFACT_OK;
-}
-
-// The product-with-dots launches of the device loops on an operator that is more than an explicit Hessian: stage 1 and
-// the operator form of the kernel, L lanes per row; *nblk = the number of blocks (= partials).
-static int launch_cg_spmv_op(hipfact_handle* h, const HessOp& op, int L, int n, const CgCtl* c, const double* d,
-                             const double* z, const double* grad, double* Bd, double* part, int* nblk) {
-  HessRows R;
-  int rc;
-  if ((rc = hess_op_stage1(h, op, n, d, &R))) return rc;
-  *nblk = row_blocks(n, L, CG_BLOCKS);
-  with_lanes(L, [&](auto lanes) {
-    hipLaunchKernelGGL(k_cg_spmv_dots_op<decltype(lanes)::value>, dim3(*nblk), dim3(FB), 0, h->stream, n, c, R, d, z, grad,
-                       Bd, part);
-  });
-  return HIPFACT_OK;
-}
-static int launch_cg_head_op(hipfact_handle* h, const HessOp& op, int L, int n, const CgCtl* ci, CgCtl* co,
-                             const double* part_rg, int nblk_rg, int stride, const double* g, double* d, double* Bd,
-                             const double* z, const double* grad, double* part) {
-  HessRows R;
-  int rc;
-  if ((rc = hess_op_stage1(h, op, n, g, &R))) return rc;
-  with_lanes(L, [&](auto lanes) {
-    hipLaunchKernelGGL(k_cg_head_op<decltype(lanes)::value>, dim3(row_blocks(n, L, CG_BLOCKS)), dim3(FB), 0, h->stream, n,
-                       ci, co, part_rg, nblk_rg, stride, R, g, d, Bd, z, grad, part);
-  });
-  return HIPFACT_OK;
-}
-static int launch_lz_spmv_op(hipfact_handle* h, const HessOp& op, int L, int n, const LzCtl* c, const double* y, double* Hy,
-                             double* part, int* nblk) {
-  HessRows R;
-  int rc;
-  if ((rc = hess_op_stage1(h, op, n, y, &R))) return rc;
-  *nblk = row_blocks(n, L, CG_BLOCKS);
-  with_lanes(L, [&](auto lanes) {
-    hipLaunchKernelGGL(k_lz_spmv_dot_op<decltype(lanes)::value>, dim3(*nblk), dim3(FB), 0, h->stream, n, c, R, y, Hy,
-                       part);
-  });
   return HIPFACT_OK;
 }
 #endif
